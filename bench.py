@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: joint VAE+seg train-step throughput (volumes/s) on synthetic 96^3 volumes, batch 2 per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` (one rank per GPU), or as
 plain `python bench.py --gpus N`, in which case this process spawns that launcher itself — before it touches the GPU — and
@@ -10,12 +10,16 @@ relays rank 0's single JSON line.
 A step = zero_grad -> Segmentation fwd -> frozen VAE fwd -> Dice losses -> backward -> [RCCL all-reduces, overlapped with the
 weight-gradient kernels] -> SGD(momentum)  (the `joint_train` method of the reference, main_source.py:449-471,660-661),
 bf16 activations / fp32 accumulate, inputs resident in HBM, HIP-graph replay.  Rank 0 prints ONE JSON line:
-  value/ms_per_step  whole-job volumes/s over all ranks (barrier + synchronize on both sides, max over ranks)
+  value/ms_per_step  whole-job volumes/s over all ranks (barrier + synchronize on both sides, max over ranks); ms_per_step = one of the K timed steps
   roofline           the WHOLE STEP against its binding roofline: algorithmic bytes per step (1.28 GB per volume,
                      every activation touched once per pass) / ms_per_step against HBM peak — recomputable from this line alone;
-                     `families` lists the per-kernel-family figures from live HIP-event timing (or --no-families)
-  fp32_parity_mode   the same step with the fp32 kernels (the mode that meets the 1e-3 parity gate), N=1 only
-  cpu_baseline       the same step on the host cores with the CPU oracle (plain eager PyTorch fp32), bounded sample, N=1 only.
+                     with --full, `families` lists the per-kernel-family figures from live HIP-event timing (or --no-families)
+  fp32_parity_mode   with --full: the same step with the fp32 kernels (the mode that meets the 1e-3 parity gate), N=1 only
+  cpu_baseline       with --full: the same step on the host cores with the CPU oracle (plain eager PyTorch fp32), bounded sample, N=1 only
+  other_configs      with --full: configs[3] and one GPU's share of configs[4] on short legs, N=1 only.
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write the last step's outputs (--dump-outputs DIR:
+the same inputs on every run, so two builds compare output for output) and print the line.  --full adds the entries marked above and, for
+N > 1, the exchange legs (config.exchange); the --no-* options leave out single entries of a --full run.
 """
 import argparse
 import json
@@ -81,7 +85,15 @@ def parse():
     ap.add_argument("--no-other-configs", action="store_true", help="N = 1, default workload: skip the configs[3] / configs[4] entries (`other_configs`)")
     ap.add_argument("--legs-budget-s", type=float, default=60.0, help="N > 1: the other exchange form is timed only if everything before it "
                     "(set-up, main timing, the no-exchange leg) took less than this on every rank: rank 0's line must not wait for it")
+    ap.add_argument("--full", action="store_true", help="after the headline timing, also measure what the headline figure does not need: the per-kernel-family "
+                    "timing pass, the fp32 parity mode, the other configurations, the CPU baseline (N = 1) and the exchange legs (N > 1); the --no-* "
+                    "options above leave out single entries of such a run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step handed its caller "
+                    "(loss and loss terms, the networks' outputs, the trained weights after the update) to DIR/<name>.npy as float32, at most 64 MB "
+                    "in all (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = CONFIGS[a.config]
     a.dtype = a.dtype or cfg["dtype"]
     a.side = a.side or cfg["side"]
@@ -213,6 +225,7 @@ def make_step(a, dtype, rank, use_dist, overlap=None, info=None):
     if info is not None:
         info["buckets"] = len(sync.buckets) if sync is not None else 0
         info["tail_in_graph"] = False
+    last = {}                            # no-graph steps: the last step's (loss, aux)
 
     def loss_fn():
         if teacher is not None:          # main_target.py:520-596, loss type 0, lambda_vae 1.0 (scripts/target/domain_msd_dh.bash:12-13); the schedule stays on the device
@@ -223,7 +236,8 @@ def make_step(a, dtype, rank, use_dist, overlap=None, info=None):
         def step():
             for p in seg_params:
                 p.grad = None
-            loss, _ = loss_fn()
+            loss, aux = loss_fn()
+            last.update(loss=loss, aux=aux)
             if scaler is not None:
                 loss.backward(gradient=scaler.seed)
             else:
@@ -240,6 +254,20 @@ def make_step(a, dtype, rank, use_dist, overlap=None, info=None):
         if info is not None:
             info["tail_in_graph"] = bool(gs.tail)
 
+    def outputs():
+        """-> {name: tensor}: what the last step handed its caller — the loss and its terms, every tensor the networks wrote into the batch
+        (the batch's inputs and one-hot label left out) and the Segmentation weights after the update"""
+        import torch
+        loss, aux = (last["loss"], last["aux"]) if a.no_graph else (gs.loss, gs.aux)
+        out = {"loss": loss}
+        out.update((k, v) for k, v in aux.items() if torch.is_tensor(v))
+        out.update(("batch." + k, v) for k, v in aux["batch"].items() if torch.is_tensor(v) and k not in ("img", "label", "gt"))
+        out.update(("seg." + k, v) for k, v in joint.Seg.named_parameters())
+        return out
+
+    if info is not None:
+        info["outputs"] = outputs
+
     def closer():
         """before the eager family-timing passes: gradients back to ordinary tensors, and the captured step's autograd graph and gradient
         accumulators (created on its warm-up stream) released — eager passes on the default stream would otherwise reuse them and pay
@@ -254,6 +282,28 @@ def make_step(a, dtype, rank, use_dist, overlap=None, info=None):
 
 
 HOST_ISSUE = {"s": 0.0}
+DUMP_BYTES = 64 * 10**6
+
+
+def dump_outputs(outputs, path):
+    """{name: tensor} -> path/<name>.npy in float32, DUMP_BYTES in all.  When the whole tensors do not fit, the smaller ones are written whole and
+    each of the others, flattened, as a sample of an equal share of what is left: positions drawn with a fixed seed (the same positions in every
+    run with the same arguments) and kept in ascending order."""
+    import numpy as np
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
+    left = (DUMP_BYTES - 512 * len(arrs)) // 4            # float32 elements, room for the .npy headers
+    order = sorted(arrs, key=lambda k: (arrs[k].size, k))
+    os.makedirs(path, exist_ok=True)
+    sampled = []
+    for i, k in enumerate(order):
+        x, keep = arrs[k], min(arrs[k].size, left // (len(order) - i))
+        if keep < x.size:
+            x = x.reshape(-1)[np.sort(np.random.default_rng(0).choice(x.size, keep, replace=False))]
+            sampled.append(k)
+        left -= x.size
+        np.save(os.path.join(path, k + ".npy"), np.asarray(x, dtype=np.float32))
+    print("bench.py: %d outputs of the last step written to %s%s" % (len(arrs), path, " (sampled: %s)" % ", ".join(sampled) if sampled else ""),
+          file=sys.stderr)
 
 
 def timed_steps(step, steps, warmup, fence):
@@ -402,13 +452,15 @@ def main():
     host_issue_ms = 1e3 * HOST_ISSUE["s"] / a.steps
     del loss                                    # the last reference to the captured step's autograd graph (see closer())
     ms_per_step = 1e3 * dt / a.steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(info["outputs"](), a.dump_outputs)
 
     # ---- the exchange, measured in the same run (every rank takes part: these are collective) ----------------------------------------
     # exposed cost of the gradient exchange = this job's step minus the same step without the exchange (replicas drift apart in that leg: it is
     # timed, not trained); and the other exchange form (two buckets, bucket 0 all-reduced under the remaining weight-gradient kernels), so
     # that ONE run decides which form should be the default at this world size.
     exchange = None
-    if use_dist and not a.no_graph and not a.no_exchange_forms:
+    if a.full and use_dist and not a.no_graph and not a.no_exchange_forms:
         n_x = max(10, min(a.steps, 50))
         closer()
         del step, loss_fn, seg_params
@@ -444,7 +496,7 @@ def main():
                                       "ms_per_step": round(1e3 * dt_o / n_x, 4)}
 
     families, fp32_mode, cpu, others = None, None, None, None
-    if rank == 0 and not a.no_families:
+    if rank == 0 and a.full and not a.no_families:
         # per-kernel-family timing: HIP events around every launch inside real (eager) forward+backward passes
         closer()                                 # gradients back to ordinary tensors for the eager profiling pass
         families = profiling.kernel_families(lambda: (loss_fn()[0]).backward(), seg_params, a.dtype, steps=2)
@@ -459,7 +511,7 @@ def main():
                 print("%8.1f us  %-42s %-52s %7.1f GB/s %8.2f TF/s" % (ms * 1e3, kid, det, nb / ms / 1e6, fl / ms / 1e9), file=sys.stderr)
     if use_dist:
         dist.barrier()
-    if rank == 0 and world == 1 and not a.no_fp32_mode and a.dtype != "fp32":
+    if rank == 0 and world == 1 and a.full and not a.no_fp32_mode and a.dtype != "fp32":
         del step, loss_fn, seg_params
         torch.cuda.empty_cache()
         step32, _, _, closer32 = make_step(a, "fp32", rank, False)
@@ -473,11 +525,11 @@ def main():
                              "round 3 ran it on the exact-f32 MFMA at 9.83 ms"}
         closer32()
         del step32
-    if rank == 0 and world == 1 and not use_dist and a.config == "joint96" and a.side == CONFIGS["joint96"]["side"] and not a.no_other_configs \
-            and not a.no_graph and not a.recompute:
+    if rank == 0 and world == 1 and a.full and not use_dist and a.config == "joint96" and a.side == CONFIGS["joint96"]["side"] \
+            and not a.no_other_configs and not a.no_graph and not a.recompute:
         peak_main = round(torch.cuda.max_memory_allocated() / 1e9, 2)
         others = other_configs(a, rank, torch)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(a.side, a.cpu_steps, batch=a.batch, method=CONFIGS[a.config]["method"])
 
     from vae_segmentation_amd import ops as _ops

@@ -273,7 +273,7 @@ def test_two_rank_capturable_agreement_and_loss_scaler_overflow_on_one_rank(tmp_
 def test_bench_spawns_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` (no torchrun) must start its ranks itself and print ONE JSON line with n_gpus = 2."""
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "3",
-                          "--warmup", "1", "--side", "64", "--no-families", "--other-form", "--master-port", "29553"],
+                          "--warmup", "1", "--side", "64", "--full", "--no-families", "--other-form", "--master-port", "29553"],
                          env=dict(os.environ, PYTHONPATH=REPO, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -295,7 +295,7 @@ def test_bench_four_gloo_ranks_rendezvous_and_one_json_line():
     port handling, legs budget and the one-JSON-line contract are rehearsed at FOUR ranks sharing cuda:0 through gloo (VERDICT r05 item 7b asked for 8: not runnable
     here), at the smallest side the VAE admits (64)."""
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "4", "--backend", "gloo", "--share-gpu", "--steps", "3", "--warmup", "1",
-                          "--side", "64", "--no-families", "--legs-budget-s", "120", "--master-port", "29561"],
+                          "--side", "64", "--full", "--no-families", "--legs-budget-s", "120", "--master-port", "29561"],
                          env=dict(os.environ, PYTHONPATH=REPO, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -309,7 +309,7 @@ def test_bench_one_rank_rccl_whole_step_is_one_graph():
     """bench.py --force-dist on one rank through RCCL: the all-reduce, the SGD launch and the weight re-pack are captured into the step's graph
     (config.tail_in_graph) and the line carries the exchange legs."""
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "5", "--warmup", "2", "--side", "64",
-                          "--no-families", "--no-cpu-baseline", "--no-fp32-mode", "--other-form", "--master-port", "29557"],
+                          "--full", "--no-families", "--no-cpu-baseline", "--no-fp32-mode", "--other-form", "--master-port", "29557"],
                          env=dict(os.environ, PYTHONPATH=REPO, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])

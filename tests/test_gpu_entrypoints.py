@@ -117,3 +117,36 @@ def test_pseudo_list_step_losses_follow_the_reference_ladder():
     out = T.pseudo_batch_losses(joint, img, lab)
     assert set(out) == {"recon_loss_pseudo", "dice_loss_pseudo", "final_loss_pseudo"} and not any(v.requires_grad for v in out.values())
     assert out["final_loss_pseudo"].item() == out["dice_loss_pseudo"].item()
+
+
+def _bench_line(args, env):
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + args, env=dict(os.environ, PYTHONPATH=REPO, **env), capture_output=True,
+                         text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain bench.py run times --steps steps and measures nothing else (the extra entries come with --full); --dump-outputs writes what the last
+    timed step handed its caller.  On the deterministic build two runs with the same arguments dump bit-identical arrays (same inputs, same work);
+    the eager (--no-graph) path dumps the same set of arrays."""
+    import numpy as np
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--side", "64"]
+    dumps = []
+    for i, extra in enumerate(([], [], ["--no-graph"])):
+        d = tmp_path / ("out%d" % i)
+        rec = _bench_line(common + extra + ["--dump-outputs", str(d)], {"VS_DETERMINISTIC": "1"})
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["unit"] == "volumes/s" and rec["dtype"] == "bf16"
+        assert abs(rec["value"] - rec["config"]["global_batch"] * 1e3 / rec["ms_per_step"]) < 1e-6 * rec["value"]
+        assert rec["fp32_parity_mode"] is None and rec["cpu_baseline"] is None and rec["other_configs"] is None and rec["config"]["exchange"] is None
+        arrs = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert all(f.endswith(".npy") for f in os.listdir(d)) and sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 * 10**6
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["batch.pred"].shape == (2, 2, 64, 64, 64) and arrs["batch.recon"].shape == (2, 2, 64, 64, 64)
+        assert {"loss", "recon_loss", "dice_loss", "seg.in_block.conv.0.weight"} <= set(arrs) and "batch.img" not in arrs
+        assert arrs["loss"].size == 1 and arrs["loss"].item() == float(np.float32(rec["config"]["final_loss"]))
+        dumps.append(arrs)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    assert {k: a.shape for k, a in dumps[2].items()} == {k: a.shape for k, a in dumps[0].items()}

@@ -328,3 +328,23 @@ def test_isa_phase_counts_finds_the_tile_loop_of_k3t():
     tot = [ln for ln in out.stdout.splitlines() if ln.startswith("loop total")][0].split()
     valu, packed, mfma = int(tot[2]), int(tot[3]), int(tot[4])
     assert mfma == 72 and 300 <= valu + packed <= 800, out.stdout
+
+
+def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs (no GPU: the writer alone): float32 .npy files, 64 MB in all; outputs that fit are written whole, the larger ones as a
+    sample of positions that are the same in every run (two builds compare output for output), in ascending order."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    n = 2 * 2 * 160 ** 3                         # the prediction of one GPU's share of configs[4]: two of them do not fit
+    outs = {"loss": torch.tensor(0.25, dtype=torch.float64), "w": torch.randn(1000), "pred": torch.randn(n).bfloat16().view(2, 2, 160, 160, 160),
+            "recon": torch.arange(n, dtype=torch.float32).view(2, 2, 160, 160, 160)}          # values = positions (exact below 2^24)
+    for d in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / d))
+    a, b = ({f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)} for d in ("a", "b"))
+    assert set(a) == set(outs) and all(x.dtype == np.float32 for x in a.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BYTES == 64 * 10**6
+    assert a["loss"].shape == () and float(a["loss"]) == 0.25 and np.array_equal(a["w"], outs["w"].numpy())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    r = a["recon"]
+    assert r.ndim == 1 and n // 4 < r.size < n and np.all(np.diff(r) > 0) and np.array_equal(r, np.round(r)) and r[-1] < n

@@ -8,8 +8,8 @@ OUT=$ROOT/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
 Q="--no-cpu-baseline --no-fp32-mode --no-families --no-other-configs"
-# 1. the bench line (+ the live-timed launches behind roofline.families)
-python3 $ROOT/bench.py --dump-launches $OUT/live_launches.json > $OUT/bench.json 2> $OUT/bench.err
+# 1. the full bench line (+ the live-timed launches behind roofline.families)
+python3 $ROOT/bench.py --full --dump-launches $OUT/live_launches.json > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"
 # 2. per-kernel summary and the launches of one replayed step
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $ROOT/bench.py --steps 20 --warmup 3 $Q > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
