@@ -117,8 +117,10 @@ int vs_pack_weight_multi(const vs_pack_desc* descs, int n_desc, int total_blocks
  * transposed-conv weight packed VS_PACK_ROWS_D0).
  *   x_stats  : lazy-activation stats of x or NULL         y_stats : if non-NULL, (sum,sumsq) of y are
  *   bias     : float[m_out] or NULL                                 ACCUMULATED into it (caller zeroes)
- *   c_in     : channels of x (multiple of 8)   m_out : channels of y (multiple of 8; rows beyond the
- *              real weight rows come out as bias/zero)
+ *   c_in     : channels of x: 8, 16 or a multiple of 32 up to 512   m_out : channels of y (multiple of 8, at most 512; rows
+ *              beyond the real weight rows come out as bias/zero)
+ * Layers with more than 256 input or output channels (the deepest levels of the wide models, n_fmaps [16, .., 512]) run the
+ * per-layer kernels only: the fused-apply, epilogue-apply, chain and composed-Up queries answer 0 for them.
  */
 int vs_conv_gather_fwd(const void* x, const double* x_stats, const void* w_packed, const float* bias,
                        void* y, double* y_stats, int n, int d, int h, int w, int c_in, int m_out,
@@ -242,7 +244,7 @@ int vs_conv_s2_bwd_data_applied(const void* x, const void* w_packed, void* y, co
  *   one stream — the deployment model.  Two such launches running at the same time on one device (two processes sharing a GPU, two streams) can each hold part of
  *   the chip and starve the other's waiters; the bounded waits then give up and raise `fault`.  A host that shares a device switches the two forms off first
  *   (vs_set_config: chain = 0, epilogue_apply = 0; Python: ops.device_is_shared()).
- * Shapes: (d+2)(h+2)(w+2) <= 512 (up to 6^3), channels multiples of 32 (c_in) / 8 (m_out), at most 256 workgroups per sample (32 per XCD): vs_conv_k3_chain_supported(n, d, h, w,
+ * Shapes: (d+2)(h+2)(w+2) <= 512 (up to 6^3), channels multiples of 32 (c_in) / 8 (m_out) up to 256, at most 256 workgroups per sample (32 per XCD): vs_conv_k3_chain_supported(n, d, h, w,
  * largest channel count of the chain, dtype) says 1 / 0 (env VS_CHAIN=0: always 0).  All three storage types; results are bit-identical to the per-layer launches
  * in the deterministic build. */
 typedef struct vs_chain_layer {

@@ -14,7 +14,7 @@ static int chain_shape_ok(int n, int d, int h, int w) {
 extern "C" int vs_conv_k3_chain_supported(int n, int d, int h, int w, int c_max, int dtype) {
     const int on = vs_cfg().chain;
     if (!on || !vs_dtype_ok(dtype) || !chain_shape_ok(n, d, h, w)) return 0;
-    if (c_max <= 0 || c_max % 32 || c_max > 1024) return 0;
+    if (c_max <= 0 || c_max % 32 || c_max > 256) return 0;           // the 512-channel layers of the wide models run per layer (conv_api.hip)
     const int v = d * h * w;
     const int cw = ((long long)(d + 2) * (h + 2) * (w + 2) <= 128 && v <= 32) ? 16 * K3S_NCG_SMALL : 16 * K3S_NCG;      // k3s_col_tile()
     const int ctiles = (v + cw - 1) / cw;
@@ -37,7 +37,7 @@ extern "C" int vs_conv_k3_chain(const vs_chain_layer* layers, int n_layers, int 
         G1Params& p = c.p[l];
         if (!L.x || !L.w_packed || !L.y) return VS_EINVAL;
         if (((uintptr_t)L.x & 15) || ((uintptr_t)L.w_packed & 15) || ((uintptr_t)L.y & 15) || (L.mask_x && ((uintptr_t)L.mask_x & 15))) return VS_EALIGN;
-        if (L.c_in <= 0 || L.c_in % 32 || L.m_out <= 0 || L.m_out % 8) return VS_ESHAPE;
+        if (L.c_in <= 0 || L.c_in % 32 || L.c_in > 256 || L.m_out <= 0 || L.m_out % 8 || L.m_out > 256) return VS_ESHAPE;
         if ((double)n * d * h * w * (L.c_in > L.m_out ? L.c_in : L.m_out) * es >= 2147483648.0) return VS_ESHAPE;
         if (backward) {
             if (L.x_stats || L.y_stats) return VS_EINVAL;

@@ -56,10 +56,15 @@ static int pick_mt(int rows16, long long tiles) {
     return 16;
 }
 
+// widest channel count of the conv stack (input or output): the 512-channel layers of the wide models (n_fmaps [16, .., 512]) run the per-layer kernels only
+#define VS_MAX_CHANNELS 512
+// the fused / epilogue-apply / composed / chain paths were sized for the default widths and decline anything wider (ops.py takes the per-layer path)
+static inline bool wide_layer(int c_in, int m_out) { return c_in > 256 || m_out > 256; }
+
 static int check_common(const void* x, const void* w, int n, int d, int h, int w_, int c_in, int dtype) {
     if (!x || !w) return VS_EINVAL;
     if (n <= 0 || d <= 0 || h <= 0 || w_ <= 0) return VS_ESHAPE;
-    if (!(c_in == 8 || c_in == 16 || (c_in % 32 == 0 && c_in > 0 && c_in <= 256))) return VS_ESHAPE;
+    if (!(c_in == 8 || c_in == 16 || (c_in % 32 == 0 && c_in > 0 && c_in <= VS_MAX_CHANNELS))) return VS_ESHAPE;
     if (!vs_dtype_ok(dtype)) return VS_EDTYPE;
     if (((uintptr_t)x & 15) || ((uintptr_t)w & 15)) return VS_EALIGN;
     if ((double)n * d * h * w_ * c_in >= 2147483648.0) return VS_ESHAPE;      // kernels index activations with 32-bit element offsets
@@ -76,7 +81,13 @@ static int gather_impl(const void* x, const double* x_stats, const void* w_packe
     int rc = check_common(x, w_packed, n, d, h, w, c_in, dtype);
     if (rc) return rc;
     if (!y || m_out <= 0 || m_out % 8 || ((uintptr_t)y & 15)) return VS_EINVAL;
+    if (m_out > VS_MAX_CHANNELS) return VS_ESHAPE;
     if (kind != VS_CONV_K3 && kind != VS_CONV_K2S2) return VS_EINVAL;
+    if (wide_layer(c_in, m_out)) {
+        if (ea_query != nullptr) { *ea_query = 0; return VS_OK; }
+        if (fa_query != nullptr) { *fa_query = 0; return VS_OK; }
+        if (ea_sync != nullptr || fa_x != nullptr || wg_ws != nullptr) return VS_ESHAPE;
+    }
     if (kind == VS_CONV_K2S2 && ((d | h | w) & 1)) return VS_ESHAPE;
     G1Params p{};
     p.x = x; p.x_stats = x_stats; p.wp = w_packed; p.bias = bias; p.y = y; p.y_stats = y_stats; p.prob = nullptr;
@@ -257,6 +268,11 @@ static int scatter_impl(const void* x, const double* x_stats, const void* w_pack
     int rc = check_common(x, w_packed, n, d, h, w, c_in, dtype);
     if (rc) return rc;
     if (!y || m_out <= 0 || m_out % 8 || ((uintptr_t)y & 15)) return VS_EINVAL;
+    if (m_out > VS_MAX_CHANNELS) return VS_ESHAPE;
+    if (wide_layer(c_in, m_out)) {
+        if (ea_query != nullptr) { *ea_query = 0; return VS_OK; }
+        if (ea_sync != nullptr) return VS_ESHAPE;
+    }
     G1Params p{};
     p.x = x; p.x_stats = x_stats; p.wp = w_packed; p.bias = bias; p.y = y; p.y_stats = nullptr; p.prob = nullptr;
     p.mask_x = mask_x; p.mask_stats = mask_stats; p.sums = sums;

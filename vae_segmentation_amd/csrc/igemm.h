@@ -68,10 +68,10 @@ struct G1Params {
 };
 
 // LDS carve (bytes)
-#define G1_LDS_MEAN 0       // float[256]
-#define G1_LDS_RSTD 1024    // float[256]
-#define G1_LDS_RED 2048     // float[4][64][2]
-#define G1_LDS_BYTES 4096
+#define G1_LDS_MEAN 0       // float[512] (input channels, or the mask tensor's: up to the 512-channel layers of the wide models)
+#define G1_LDS_RSTD 2048    // float[512]
+#define G1_LDS_RED 4096     // float[4][64][2]
+#define G1_LDS_BYTES 6144
 #define G1_TILE_VOX 648     // 3x3x3 kernels: (4+2)*(4+2)*(16+2) halo voxels
 
 template <typename T, int CK>

@@ -117,7 +117,9 @@ __device__ __forceinline__ void k3s_geometry(K3SGeo<TVC, NW>& geo, const int D, 
 
 template <int TVC> static constexpr int k3s_tile_bytes() { return 2 * TVC * 64 > 16384 ? 2 * TVC * 64 : 16384; }      // two stage buffers; at least 16 KB (the cross-wave partials alias them)
 
-template <bool SUMS, int TVC, bool HS, typename T, bool CH, int XR = 2, int NW = 4>
+// SPL (k3s_split_kernel, layers of more than 256 input channels): this workgroup walks stage slice blockIdx.z of gridDim.z and stores its fp32 partial sums to p.wg_ws
+// ([slice][n][v][M]); k3s_split_reduce_kernel adds the slices in a fixed order and runs the epilogue (bias, rounding, statistics).  SPL = false is the code as before.
+template <bool SUMS, int TVC, bool HS, typename T, bool CH, int XR = 2, int NW = 4, bool SPL = false>
 __device__ __forceinline__ void k3s_body(const G1Params& p, const K3SGeo<TVC, NW>& geo, const int n, const int ct, const int rb0, char* smem, unsigned int* wait_ctr = nullptr,
                                          unsigned int wait_target = 0, unsigned int* fault = nullptr, const int sb = 0 /* CH_STAMP base */) {
     KS_TICK_INIT
@@ -147,7 +149,8 @@ __device__ __forceinline__ void k3s_body(const G1Params& p, const K3SGeo<TVC, NW
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, g = lane >> 4;
     constexpr bool has_stats = HS;
     const i32x4 xrsrc = make_rsrc(p.x, (unsigned int)((long long)p.N * V * p.C * ES));
-    const int nst = p.nch * SPC;                         // stages
+    const int nst = SPL ? p.nch * SPC / (int)gridDim.z : p.nch * SPC;      // stages (of this slice)
+    const int kst0 = SPL ? (int)blockIdx.z * nst : 0;    // first stage of this slice
     const u32x4* __restrict__ wp = (const u32x4*)p.wp;
 
     // ---- staging: fragment b = 16-byte part (tid & 3) of REAL voxel (tid >> 2) + (NT / 4) b of the sample (LDS offsets: geo.loff) ---------------------------
@@ -178,20 +181,20 @@ __device__ __forceinline__ void k3s_body(const G1Params& p, const K3SGeo<TVC, NW
     u32x4 xv[XR][NIT], wv[2][NWI];
     auto load_w = [&](int ch, u32x4 (&wv)[NWI]) {
 #pragma unroll
-        for (int i = 0; i < NWI; ++i) wv[i] = wp[w_off[i] + (ch / SPC) * (27 * 64 * SPC) + (ch % SPC) * 64];
+        for (int i = 0; i < NWI; ++i) wv[i] = wp[w_off[i] + ((ch + kst0) / SPC) * (27 * 64 * SPC) + ((ch + kst0) % SPC) * 64];
     };
     auto load_x = [&](int ch, u32x4 (&xv)[NIT]) {
 #pragma unroll
         for (int b = 0; b < NIT; ++b)
-            xv[b] = __builtin_bit_cast(u32x4, vs_raw_buffer_load_b128(xrsrc, goff[b] >= 0 ? goff[b] + ch * 64 : -1, 0, XAUX));
+            xv[b] = __builtin_bit_cast(u32x4, vs_raw_buffer_load_b128(xrsrc, goff[b] >= 0 ? goff[b] + (ch + kst0) * 64 : -1, 0, XAUX));
     };
     auto write_stage = [&](int ch, const u32x4 (&xv)[NIT], const int buf) {
         f32x2 sc[4], sh[4];                              // 16-bit: 8 channels; fp32: 4 (sc[0..1], sh[0..1])
         if (has_stats) {
 #pragma unroll
             for (int i = 0; i < EPL / 2; ++i) {
-                sc[i] = *(const f32x2*)(s_scale + ch * CHS + part * EPL + 2 * i);
-                sh[i] = *(const f32x2*)(s_shift + ch * CHS + part * EPL + 2 * i);
+                sc[i] = *(const f32x2*)(s_scale + (ch + kst0) * CHS + part * EPL + 2 * i);
+                sh[i] = *(const f32x2*)(s_shift + (ch + kst0) * CHS + part * EPL + 2 * i);
             }
         }
 #pragma unroll
@@ -329,6 +332,11 @@ __device__ __forceinline__ void k3s_body(const G1Params& p, const K3SGeo<TVC, NW
         const f32x4 q = s_part[(w * NCG + fcg) * 64 + lane];
         o[0] += q[0]; o[1] += q[1]; o[2] += q[2]; o[3] += q[3];
     }
+    if constexpr (SPL) {                                 // the slice's partial sums; the epilogue runs in k3s_split_reduce_kernel
+        const int v = ct * CW + wave * 16 + col;
+        if (v < V && row0 < p.M && wave < NCG) *(f32x4*)(p.wg_ws + (((size_t)blockIdx.z * p.N + n) * V + v) * p.M + row0) = o;
+        return;
+    }
 
     // ---- epilogue: column voxel v of sample n, rows row0 .. row0 + 3 ---------------------------------------------------------------------
     const int v = ct * CW + wave * 16 + col;
@@ -415,6 +423,69 @@ __global__ __launch_bounds__(64 * K3SWaves<TVC>::NW) __attribute__((amdgpu_waves
     K3SGeo<TVC, K3SWaves<TVC>::NW> geo;
     k3s_geometry(geo, p.D, p.H, p.W, ct);
     k3s_body<SUMS, TVC, HS, T, false, 2, K3SWaves<TVC>::NW>(p, geo, n, ct, (int)blockIdx.y /* 16-row block */, smem);
+}
+
+// ---- the layers of more than 256 input channels at these volumes (the wide models' 512-channel levels): split over the channel stages -----------------
+// A 512 -> 512 layer at 4^3 streams 14 MB of weights (bf16) against 128 voxels: as one k3s_kernel launch it is 128 workgroups, each walking all 16 stages of its
+// 16 rows.  Here gridDim.z slices split the stages (every workgroup reads 1 / slices of its rows' weights); the slices' fp32 partials go through a workspace and
+// k3s_split_reduce_kernel sums them in slice order — no atomics, the same result on both builds and run to run.
+template <bool SUMS, int TVC, bool HS, typename T = unsigned short>
+__global__ __launch_bounds__(64 * K3SWaves<TVC>::NW) __attribute__((amdgpu_waves_per_eu(K3SWaves<TVC>::NW / 4, 2))) void k3s_split_kernel(const G1Params p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int n = blockIdx.x / p.tiles_per_sample, ct = blockIdx.x - n * p.tiles_per_sample;
+    K3SGeo<TVC, K3SWaves<TVC>::NW> geo;
+    k3s_geometry(geo, p.D, p.H, p.W, ct);
+    k3s_body<SUMS, TVC, HS, T, false, 2, K3SWaves<TVC>::NW, true>(p, geo, n, ct, (int)blockIdx.y, smem);
+}
+
+// one workgroup per (sample, 16-row block): y = sum over the slices in order + bias, rounded to T; the statistics (or the fused IN-backward sums) of the stored
+// values, one (sum, sumsq) pair per row added once
+template <bool SUMS, typename T>
+__global__ __launch_bounds__(256) void k3s_split_reduce_kernel(const G1Params p, const int slices) {
+    __shared__ double s_red[16][16][2];
+    const int n = blockIdx.x, tid = threadIdx.x, r = tid & 15, vg = tid >> 4, row = (int)blockIdx.y * 16 + r;
+    const int V = p.D * p.H * p.W;
+    const bool rok = row < p.M;
+    const float* __restrict__ ws = p.wg_ws;
+    const size_t slice = (size_t)p.N * V * p.M;
+    float mm = 0.f, mr = 0.f, bv = 0.f;
+    if (SUMS && rok) stats_to_mean_rstd(p.mask_stats, (size_t)n * p.M + row, (size_t)p.N * p.M, p.inv_count_out, p.eps, mm, mr);
+    if (p.bias != nullptr && rok) bv = p.bias[row];
+    double s = 0.0, q = 0.0;
+    for (int v = vg; rok && v < V; v += 16) {
+        const size_t e = ((size_t)n * V + v) * p.M + row;
+        float o = ws[e];
+        for (int z = 1; z < slices; ++z) o += ws[z * slice + e];
+        float sv = o + bv;
+        float xv = 0.f;
+        if constexpr (sizeof(T) == 2) {
+            const unsigned int pk = H16<T>::pack2(f32x2{sv, 0.f});
+            ((unsigned short*)p.y)[e] = (unsigned short)(pk & 0xffffu);
+            sv = H16<T>::lo(pk);
+            if constexpr (SUMS) xv = H16<T>::lo((unsigned int)((const unsigned short*)p.mask_x)[e]);
+        } else {
+            ((float*)p.y)[e] = sv;
+            if constexpr (SUMS) xv = ((const float*)p.mask_x)[e];
+        }
+        if constexpr (SUMS) {
+            const float xh = (xv - mm) * mr;
+            const float gm = xh > 0.f ? sv : 0.f;
+            s += gm; q += (double)(gm * xh);
+        } else {
+            s += sv; q += (double)(sv * sv);
+        }
+    }
+    s_red[vg][r][0] = s; s_red[vg][r][1] = q;
+    __syncthreads();
+    double* const dst = SUMS ? p.sums : p.y_stats;
+    if (tid < 32 && dst != nullptr) {
+        const int lr = tid >> 1, st = tid & 1, rw = (int)blockIdx.y * 16 + lr;
+        if (rw < p.M) {
+            double tot = 0.0;
+            for (int k = 0; k < 16; ++k) tot += s_red[k][lr][st];
+            stat_add(dst, (size_t)n * p.M + rw, (size_t)p.N * p.M, st, tot);
+        }
+    }
 }
 
 // ---- chain kernels (chain.h): the convolutions of a DoubleConv at one of these volumes in ONE launch --------------------------------------------
@@ -506,6 +577,51 @@ static int k3s_launch_t(const G1Params& p, int ctiles, hipStream_t stream) {
     return VS_OK;
 }
 
+// the split form's fp32 partials: one library-owned buffer per device, grown outside graph capture only (a captured launch that would need more takes the
+// unsplit kernel); launches of one stream use it one after another.  A grown-out buffer is never freed: a captured graph may still hold its address.
+static float* k3s_split_workspace(size_t bytes, hipStream_t stream) {
+    static float* buf[64] = {};
+    static size_t cap[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    if (cap[dev] >= bytes) return buf[dev];
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return nullptr;
+    float* nb = nullptr;
+    if (hipMalloc((void**)&nb, bytes) != hipSuccess) return nullptr;
+    buf[dev] = nb;
+    cap[dev] = bytes;
+    return nb;
+}
+
+// slices for a layer of more than 256 input channels: the largest power of two <= 8 that divides the stages, leaves >= 2 stages per slice and <= 1024 workgroups
+static inline int k3s_split_slices(const G1Params& p, int spc, long long wgs) {
+    if (p.C <= 256 || p.fa_x != nullptr || p.ea_sync != nullptr || p.wg_ws != nullptr) return 1;
+    const int nst = p.nch * spc;
+    int s = 1;
+    while (s < 8 && nst % (2 * s) == 0 && nst / (2 * s) >= 2 && wgs * 2 * s <= 1024) s *= 2;
+    return s;
+}
+
+template <typename T, bool SUMS, int TVC, bool HS>
+static int k3s_split_launch_t(const G1Params& p_in, int ctiles, int slices, hipStream_t stream) {
+    const size_t lds = K3S_LDS_TILE + (size_t)k3s_tile_bytes<TVC>() + (size_t)2 * p_in.C * sizeof(float);
+    if (lds > 160 * 1024) return VS_ESHAPE;
+    const size_t V = (size_t)p_in.D * p_in.H * p_in.W;
+    float* ws = k3s_split_workspace((size_t)slices * p_in.N * V * p_in.M * sizeof(float), stream);
+    if (ws == nullptr) return VS_ESHAPE;
+    G1Params p = p_in;
+    p.wg_ws = ws;
+    auto kern = k3s_split_kernel<SUMS, TVC, HS, T>;
+    static const hipError_t attr_err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (attr_err != hipSuccess) return (int)attr_err;
+    hipLaunchKernelGGL(kern, dim3(ctiles * p.N, (p.M + 15) / 16, slices), dim3(64 * K3SWaves<TVC>::NW), lds, stream, p);
+    VS_CHECK_LAUNCH();
+    hipLaunchKernelGGL((k3s_split_reduce_kernel<SUMS, T>), dim3(p.N, (p.M + 15) / 16), dim3(256), 0, stream, p, slices);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
 template <typename T, bool SUMS>
 static int k3s_launch(const G1Params& p_in, hipStream_t stream) {
     G1Params p = p_in;
@@ -515,6 +631,15 @@ static int k3s_launch(const G1Params& p_in, hipStream_t stream) {
     const int ctiles = (V + k3s_col_tile(small_v) - 1) / k3s_col_tile(small_v);
     p.tiles_per_sample = ctiles;
     const bool hs = !SUMS && p.x_stats != nullptr;
+    if (p.C > 256) {                                     // the wide models' deep layers: the split form (behind C > 256; the narrower layers never reach it)
+        const int slices = k3s_split_slices(p, sizeof(T) == 4 ? 2 : 1, (long long)ctiles * p.N * ((p.M + 15) / 16));
+        if (slices > 1) {
+            int rc = VS_ESHAPE;
+            if (TV <= 128 && V <= 32) rc = hs ? k3s_split_launch_t<T, SUMS, 128, !SUMS>(p, ctiles, slices, stream) : k3s_split_launch_t<T, SUMS, 128, false>(p, ctiles, slices, stream);
+            else if (TV <= 512) rc = hs ? k3s_split_launch_t<T, SUMS, 512, !SUMS>(p, ctiles, slices, stream) : k3s_split_launch_t<T, SUMS, 512, false>(p, ctiles, slices, stream);
+            if (rc != VS_ESHAPE) return rc;              // no workspace (first use inside a capture): the unsplit kernel below
+        }
+    }
 #define K3S_GO(TVC) return hs ? k3s_launch_t<T, SUMS, TVC, !SUMS>(p, ctiles, stream) : k3s_launch_t<T, SUMS, TVC, false>(p, ctiles, stream)
     if (TV <= 128 && V <= 32) K3S_GO(128);
     if (TV <= 512) K3S_GO(512);

@@ -12,7 +12,7 @@ extern "C" const char* vs_strerror(int code) {
     switch (code) {
         case VS_OK: return "ok";
         case VS_EINVAL: return "invalid argument (null pointer or non-positive size)";
-        case VS_ESHAPE: return "unsupported shape (channels must be 8, 16 or a multiple of 32 up to 256; even dims for stride 2; batch <= 16 for wgrad)";
+        case VS_ESHAPE: return "unsupported shape (channels must be 8, 16 or a multiple of 32 up to 512; even dims for stride 2; batch <= 16 for wgrad)";
         case VS_EDTYPE: return "unsupported dtype (VS_F32, VS_BF16 or VS_F16)";
         case VS_EWORKSPACE: return "workspace too small";
         case VS_EALIGN: return "pointer not 16-byte aligned";

@@ -4,7 +4,7 @@
 // (C/EPL channel fragments) x (voxel sub-rows), fp64 atomics only once per (block, channel, statistic).
 #include "common.h"
 
-#define NB_MAX_C 256
+#define NB_MAX_C 512      // per-(n, c) tables of one sample: up to the 512-channel layers of the wide models
 
 template <typename T>
 struct RowIter {
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const T* __restrict__ g,
 // ---- launchers ---------------------------------------------------------------------------------------
 static int check_cl(const void* a, int n, long long voxels, int c, int dtype) {
     if (!a || n <= 0 || voxels <= 0) return VS_EINVAL;
-    if (c <= 0 || c % 8 || c > NB_MAX_C || (256 % (c / 8)) ) return VS_ESHAPE;
+    if (c <= 0 || c % 8 || c > NB_MAX_C) return VS_ESHAPE;       // RowIter: c / EPL <= 256 fragments per row; threads beyond whole rows sit idle
     if (!vs_dtype_ok(dtype)) return VS_EDTYPE;
     return VS_OK;
 }

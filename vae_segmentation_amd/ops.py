@@ -1313,10 +1313,11 @@ class ConvK3Softmax(torch.autograd.Function):
         n, d, h, w, c = x.shape
         wp = pack_weight_cached(weight, VS_PACK_ROWS_D0, c, k3_pack_dtype(x))
         prob = torch.empty((n, nc, d, h, w), dtype=torch.float32, device=x.device)
-        if nc == 2:
+        ctx.fused2 = nc == 2 and c == 8          # the fused two-class kernel reads 8 stored input channels (n_fmaps[0] = 8); wider inputs: conv + softmax pass
+        if ctx.fused2:
             check(lib.vs_conv_k3_softmax2_dropout_fwd(x.data_ptr(), _p(xs), wp.data_ptr(), _p(bias), prob.data_ptr(), n, d, h, w, c,
                                                       vs_dtype(x), EPS_IN, float(drop_p), drop_seed, _stream()), "conv_k3_softmax2_fwd")
-        else:       # more structures than one (main_source.py:92-93): the plain conv, then the softmax as its own pass
+        else:       # more structures than one (main_source.py:92-93), or a wider out_block input: the plain conv, then the softmax as its own pass
             bias8 = None if bias is None else torch.nn.functional.pad(bias.detach().float(), (0, 8 - nc))      # the conv kernels read one bias per padded row
             logits, _ = conv_gather(x, xs, wp, bias8, 8, VS_CONV_K3, False, real_channels=(weight.shape[1], nc))
             check(lib.vs_softmax_cl_fwd(logits.data_ptr(), prob.data_ptr(), n, d * h * w, 8, nc, vs_dtype(x), float(drop_p), drop_seed, _stream()),
@@ -1341,7 +1342,7 @@ class ConvK3Softmax(torch.autograd.Function):
             if fused is not None:
                 return fused
         gl = torch.empty((n, d, h, w, 8), dtype=x.dtype, device=x.device)
-        if nc == 2:
+        if ctx.fused2:
             check(lib.vs_softmax2_dropout_bwd(prob.data_ptr(), gprob.data_ptr(), gl.data_ptr(), n, d * h * w, 8, vs_dtype(x),
                                               ctx.drop[0], ctx.drop[1], _stream()), "softmax2_bwd")
         else:
@@ -1470,7 +1471,7 @@ def _out_block_bwd_fused(ctx, x, xs, weight, prob, gprob, gcl):
 def out_block_softmax(x, xs, weight, bias, drop_p=0.0, drop_seed=0):
     """out_block + softmax -> planar fp32 probabilities; in bf16 mode the tensor carries its channels-last copy as `_vs_cl`, which a
     network that takes it as input (VAE / Joint) uses instead of re-packing it (set VS_SOFTMAX_CL=0 to disable)."""
-    if x.dtype != torch.float32 and weight.shape[0] == 2 and os.environ.get("VS_SOFTMAX_CL", "1") != "0":
+    if x.dtype != torch.float32 and weight.shape[0] == 2 and x.shape[-1] == 8 and os.environ.get("VS_SOFTMAX_CL", "1") != "0":
         prob, prob_cl = ConvK3SoftmaxCL.apply(x, xs, weight, bias, drop_p, drop_seed)
         prob._vs_cl = prob_cl
         return prob
