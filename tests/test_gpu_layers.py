@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import stats_util as SU
 from tests.test_gpu_ops import TOL, from_cl, in_relu, q, relerr, rnd, to_cl
 
 pytestmark = pytest.mark.gpu
@@ -126,6 +127,8 @@ def _k3_case(case, dtype):
     grow = max(1.0, (s / 96.0) ** 1.5)
     lims = {"y": tol, "stat_sum": 4 * tol * grow, "stat_sq": 4 * tol, "gx": 4 * tol, "gw": 4 * tol}
     _report("k3 %s %s" % (case, dtype), errs, lims)
+    # per (n, c): mean / rstd against each channel's own fp64 two-pass statistics (tests/stats_util.py); lazy input, so the storage type's tolerance
+    SU.check_stats(st, SU.two_pass(yr), "k3 %s %s" % (case, dtype), mean_tol=4 * tol * grow, rstd_tol=4 * tol, sum_tol=4 * tol * grow, rstd_tol_high=4 * tol, rstd_grows_with_r=True)
 
 
 @_last_call

@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import stats_util as SU
+
 pytestmark = pytest.mark.gpu
 
 DT = [torch.float32, torch.bfloat16, torch.float16]
@@ -106,6 +108,10 @@ def test_conv_k3_fwd_bwd(case, lazy, dtype, stat_tol=1.0):
     ref_sum, ref_sq = yr.sum((2, 3, 4)), (yr * yr).sum((2, 3, 4))
     assert float((st[..., 0] - ref_sum).abs().max() / ref_sq.sqrt().max()) < tol * stat_tol
     assert float((st[..., 1] - ref_sq).abs().max() / ref_sq.max()) < tol * stat_tol
+    # per (n, c): mean / rstd as InstanceNorm forms them, each channel against its own fp64 two-pass statistics (tests/stats_util.py)
+    SU.check_stats(st, SU.two_pass(yr), "k3 %s lazy=%s %s" % (case, lazy, dtype), mean_tol=tol * stat_tol, rstd_tol=tol * stat_tol,
+                   sum_tol=tol * stat_tol, rstd_tol_high=tol * stat_tol,
+                   rstd_grows_with_r=lazy)
     if ops.cpad(cout) > cout:
         assert float(y.float()[..., cout:].abs().max()) == 0.0
     y.backward(to_cl(gy, ops.cpad(cout), dtype))

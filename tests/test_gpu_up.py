@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import stats_util as SU
 from tests.test_gpu_ops import TOL, from_cl, in_relu, q, relerr, rnd, to_cl
 
 pytestmark = pytest.mark.gpu
@@ -75,6 +76,8 @@ def test_up_composed_vs_cpu_autograd(case, dtype, lazy):
             "stat_sq": float(((st[..., 1] - own_sq).abs() / own_sq).max()),
             "gx": relerr(from_cl(x_cl.grad, c), xq.grad)}
     lims = {"y": 2 * tol, "stat_sum": 1e-5, "stat_sq": 1e-5, "gx": 4 * tol}
+    # per (n, c): mean / rstd against the fp64 two-pass statistics of the same stored output (tests/stats_util.py)
+    SU.check_stats(st, SU.two_pass(yo), "up %s %s lazy=%s" % (case, dtype, lazy), mean_tol=1e-5, rstd_tol=1e-5, sum_tol=1e-5, rstd_tol_high=1e-5)
     bad = {k: (errs[k], lims[k]) for k in errs if not errs[k] < lims[k]}
     print("\nup %s %s lazy=%s: %s" % (case, dtype, lazy, ", ".join("%s %.2e (<%.1e)" % (k, errs[k], lims[k]) for k in errs)))
     assert not bad, bad

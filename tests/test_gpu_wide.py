@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import golden_util as G
+from tests import stats_util as SU
 from tests.test_gpu_ops import TOL, from_cl, q, rnd, to_cl
 
 pytestmark = pytest.mark.gpu
@@ -89,6 +90,8 @@ def test_k3_wide_layer(case, dtype):
             "gb": _relerr(b_gpu.grad.cpu(), bq.grad)}
     lims = {"y": tol, "stat_sum": 4 * tol, "stat_sq": 4 * tol, "gx": 4 * tol, "gw": 4 * tol, "gb": 4 * tol}
     _report("k3 wide %s %s" % (case, dtype), errs, lims)
+    # per (n, c): mean / rstd against each channel's own fp64 two-pass statistics (tests/stats_util.py); lazy input, so the storage type's tolerance
+    SU.check_stats(st, SU.two_pass(yr), "k3 wide %s %s" % (case, dtype), mean_tol=4 * tol, rstd_tol=4 * tol, sum_tol=4 * tol, rstd_tol_high=4 * tol, rstd_grows_with_r=True)
 
 
 @pytest.mark.parametrize("dtype", DT)

@@ -125,6 +125,64 @@ def test_host_helpers():
         ops._require_cuda(torch.zeros(1))
 
 
+def test_stat_pair_helpers_decode_both_builds_and_match_two_pass_numpy():
+    """tests/stats_util.py, the per-(n, c) statistics gate of the GPU suite: ops.stats_total decodes a hand-built buffer of each build (four
+    fp64 partial copies / four fixed-point limbs), the pair_to_mean_rstd arithmetic on it matches numpy's two-pass mean and rstd at channel
+    offsets R up to 300, and the gate rejects a pair that lost one tile's partial or took its neighbour's."""
+    import numpy as np
+    from vae_segmentation_amd import ops
+    from vae_segmentation_amd._lib import lib
+    from tests import stats_util as SU
+    rng = np.random.default_rng(5)
+    n, c, V = 2, 8, 4096
+    R = np.array([0.0, 4.0, 30.0, 300.0] * 2) * np.array([1, 1, -1, -1, 1, -1, 1, -1])
+    y = rng.standard_normal((n, c, V)) * 0.7
+    y = (y - y.mean(-1, keepdims=True)) / y.std(-1, keepdims=True) * 2.5 + (R * 2.5)[None, :, None]
+    ref = SU.two_pass(torch.from_numpy(y))
+    assert np.allclose(ref["mean"].numpy(), y.mean(-1), rtol=0, atol=1e-12 * np.abs(y).max())
+    assert np.allclose(ref["std"].numpy(), y.std(-1), rtol=1e-12)
+    assert np.allclose(ref["R"].numpy(), np.abs(R)[None, :].repeat(n, 0), rtol=1e-9, atol=1e-9)
+    tot = torch.from_numpy(np.stack([y.sum(-1), (y * y).sum(-1)], -1))
+    m, r = SU.pair_mean_rstd(tot, V)
+    assert np.allclose(m.numpy(), y.mean(-1), rtol=1e-13, atol=1e-13)
+    assert np.abs(r.numpy() * np.sqrt(y.var(-1) + 1e-5) - 1).max() < 1e-9          # one-pass fp64: ~R^2 * 2^-52 relative in var
+    was = ops.is_deterministic()
+    try:
+        ops.set_deterministic(True)
+        det = ops.stats_total(SU.pack_limbs(tot, interleaved=bool(lib.vs_stat_interleaved())))
+        assert det.shape == (n, c, 2) and float(((det - tot).abs() / tot.abs()).max()) < 1e-15
+        ops.set_deterministic(False)
+        parts = torch.stack([tot * 0.5, tot * 0.25, -tot * 0.125, tot * 0.375])         # four partial copies that add up to tot
+        if lib.vs_stat_interleaved():
+            parts = parts.permute(1, 2, 0, 3).contiguous().view(4, n, c, 2)
+        assert float(((ops.stats_total(parts) - tot).abs() / tot.abs()).max()) < 1e-15
+    finally:
+        ops.set_deterministic(was)
+    SU.check_stats(det, ref, "exact pairs")
+    # one 16x16 tile's partial of (0, 2) lost; one of (1, 5) credited to (0, 5) — the R = 30 channels
+    for (nn, cc, src) in ((0, 2, None), (0, 5, 1)):
+        bad = tot.clone()
+        part = torch.from_numpy(np.stack([y[nn if src is None else src, cc, :256].sum(), (y[nn if src is None else src, cc, :256] ** 2).sum()]))
+        bad[nn, cc] += part if src is not None else -part
+        if src is not None:
+            bad[src, cc] -= part
+        with pytest.raises(AssertionError, match="per-\\(n, c\\) statistics off"):
+            SU.check_stats(bad, ref, "lost partial")
+    # at the realistic scale: one 64-voxel tile of 1700 (a 96^3 sample has ~1700 tiles).  At R = 30 the mean and sum bounds fire ten times over;
+    # in a centred channel (R = 0) the same loss moves mean and sum by the tile's noise only, ~1e-5: marginal — why the GPU suite offsets its data
+    V = 64 * 1700
+    z = rng.standard_normal((1, 2, V))
+    z = (z - z.mean(-1, keepdims=True)) / z.std(-1, keepdims=True) + np.array([0.0, 30.0])[None, :, None]
+    zt = torch.from_numpy(np.stack([z.sum(-1), (z * z).sum(-1)], -1))
+    zref = SU.two_pass(torch.from_numpy(z))
+    lost = zt - torch.from_numpy(np.stack([z[..., :64].sum(-1), (z[..., :64] ** 2).sum(-1)], -1))
+    err = SU.stat_errors(lost, zref)
+    assert float(err["mean"][0, 1]) > 1e-5 * 31 * 10 and float(err["sum"][0, 1]) > 1e-5 * 10      # R = 30: 10x over both bounds
+    assert float(err["mean"][0, 0]) < float(err["mean"][0, 1]) / 50 and float(err["sum"][0, 0]) < float(err["sum"][0, 1]) / 50     # R = 0
+    with pytest.raises(AssertionError, match="mean at"):
+        SU.check_stats(lost[:, 1:], {k: (v[:, 1:] if torch.is_tensor(v) else v) for k, v in zref.items()}, "one tile of 1700 lost, R = 30")
+
+
 def test_module_surface_on_cpu_is_constructible_but_not_runnable():
     import joint_model as M
     seg = M.Segmentation(1, 2, norm_type=1)
