@@ -465,6 +465,31 @@ int vs_hard_onehot(const float* x, float* out, int n, int n_class, long long vox
 /* mode 0: (a >= 0.5) ; mode 1: a>hi -> 1, a<lo -> 0, else a        (utils/evaluation.py:9-18) */
 int vs_binarize(const float* a, float* out, long long count, int mode, float lo, float hi, void* stream);
 
+/* ---- connected components of a prediction (csrc/cc.hip) ---------------------------------------------------------------------------------
+ * mask: planar fp32 (n, c, d, h, w), contiguous; foreground is value >= 0.5 (the binarize rule, utils/evaluation.py:9-10); every (n, c)
+ * plane is an independent problem; any d, h, w >= 1 with d*h*w < 2^31 (VS_ESHAPE beyond).  connectivity: 26 (what the reference uses:
+ * utils/utils.py:20-57 Tag scans the 3x3x3 neighbourhood, utils/utils.py:776-796 predict_vol sets SetFullyConnected(True)) or 6; neighbours
+ * never wrap from one row to the next and the volume border is background.
+ * labels: int32 (n, c, d, h, w); 0 = background, components numbered 1..K per plane in the order of their first voxel in raster order
+ * (z slowest, x fastest) — the numbering of scipy.ndimage.label and of the reference's check_connection(np.argwhere(mask), mask).
+ * counts: int32 (n, c) = K.  The per-plane size table — int32 [n * c][maxk], sizes[label - 1] = voxels, zero beyond K — is written to the
+ * START of the workspace; maxk = ceil(d/2) * ceil(h/2) * ceil(w/2) for connectivity 26, ceil(d*h*w / 2) for 6 (the most components a plane can hold).
+ * Only 32-bit integer atomics are used and the result does not depend on their order: both builds of the library give the same bits.
+ * No kernel waits for another workgroup (every phase is a launch, every loop is bounded by the data), nothing is read back: a call is a
+ * straight line of launches that can be captured in a HIP graph.  workspace: vs_cc_workspace_bytes() bytes (negative: VS_E*), 16-byte aligned,
+ * contents undefined on entry; mask / labels / out 16-byte aligned.  Bad arguments are answered on the host: connectivity not 6 / 26, k < 0,
+ * lo_channel outside [0, c): VS_EINVAL; an empty or too large shape: VS_ESHAPE. */
+long long vs_cc_workspace_bytes(int n, int c, int d, int h, int w, int connectivity);
+/* utils/utils.py:20-57 (Tag / check_connection): the component labels of every plane */
+int vs_cc_label(const float* mask, int* labels, int* counts, int n, int c, int d, int h, int w, int connectivity, void* workspace, void* stream);
+/* utils/utils.py:776-796 (predict_vol step 2: ConnectedComponent -> RelabelComponent by size -> drop all but the largest -> re-binarise; it hard-codes
+ * k = 2, min_size = 10000): out[v] = 1.0 where v's component is among the k largest of its plane AND holds at least min_size voxels, 0.0 elsewhere.
+ * Components of equal size rank by label, the lower one (the earlier first voxel) first — a rule of this library: SimpleITK's tie order is unspecified.
+ * Channels below lo_channel are not labelled: they are copied to out; with to_background != 0 and lo_channel >= 1 every removed voxel is added to
+ * channel 0 (a one-hot tensor stays one-hot).  out must not alias mask.  Labels, counts and sizes of the call stay in the workspace. */
+int vs_cc_keep_largest(const float* mask, float* out, int n, int c, int d, int h, int w, int connectivity, int k, int min_size, int lo_channel,
+                       int to_background, void* workspace, void* stream);
+
 /* ---- fully connected (VAE bottleneck, joint_model.py:216-218,242-243,248-253) -------------------- */
 /* y[b][j] = act( bias[j] + sum_k W[j][k] * x[b][phys(k)] )  with phys(k) = (k % pv)*pc + k / pv when pc > 0:
  * x is a channels-last activation [B][pv voxels][pc channels] read in the reference's flatten order

@@ -39,7 +39,8 @@ def parse(argv=None):
     p.add_argument("--test_only", action="store_true")
     p.add_argument("--resume", action="store_true", help="parsed and unused, as in the reference")
     p.add_argument("--save_more_reference", action="store_true")
-    p.add_argument("--save_eval_result", action="store_true")
+    p.add_argument("--save_eval_result", action="store_true", help="every 10th epoch: per validation case the binarised prediction, the image and the "
+                   "one-hot label under result/<prefix>/ (main_source.py:721-727,751-757), plus the component-filtered mask with --val_keep_largest")
     p.add_argument("--no_aug", action="store_true")
     p.add_argument("--adam", action="store_true")
     p.add_argument("--mode", type=int, default=0)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Target-domain trainer — every flag of the reference's main_target.py:29-81 parses (same names, short options and defaults), native step.
-Flags that only drive outputs this entry point does not produce (figures, extra reference dumps: --save_more_reference, --save_eval_result,
---analysis_figure_name, --generate_bounding_boxes, -P) are accepted with a warning.  --pseudo_list (with --pseudo_data_root / --pseudo_pan_index, main_target.py:228-307) adds the second, pseudo-labelled
+Flags that only drive outputs this entry point does not produce (figures, extra reference dumps: --save_more_reference,
+--analysis_figure_name, --generate_bounding_boxes, -P) are accepted with a warning; --save_eval_result writes the per-case volumes of main_target.py:922-930 under result/<prefix>/.  --pseudo_list (with --pseudo_data_root / --pseudo_pan_index, main_target.py:228-307) adds the second, pseudo-labelled
 loader and switches domain_adaptation to the step of main_target.py:615-692 (its own loss ladder, teacher re-loaded from the student, and a logged-only
 forward on one pseudo-labelled batch per iteration).  Methods (all native): vae_train, domain_adaptation (student/teacher Joint nets, binarised or confident pseudo-labels,
 domain_loss_type 0 / 8 / 9 / 11-16, --only_pseudo, --turn_epoch, --lambda_vae_warmup, optional KL term, optional EMA teacher, test-time
@@ -57,7 +57,8 @@ def parse(argv=None):
     p.add_argument("--adam", action="store_true")
     p.add_argument("--resume", action="store_true", help="accepted (main_target.py:58,134: read, never used by the reference either)")
     p.add_argument("--save_more_reference", action="store_true", help="accepted; the extra reference volumes are not written")
-    p.add_argument("--save_eval_result", action="store_true", help="accepted; per-case result volumes are not written")
+    p.add_argument("--save_eval_result", action="store_true", help="every 10th epoch: per validation case the binarised prediction, the image and the one-hot label under result/<prefix>/ "
+                   "(main_target.py:922-930), plus the component-filtered mask with --val_keep_largest")
     p.add_argument("--no_aug", action="store_true", help="no spatial augmentation of the training samples (main_target.py:61,207)")
     p.add_argument("--fix_layer", action="store_true", help="joint_train / domain_adaptation: train only Seg.up5 and Seg.out_block (main_target.py:400-406)")
     p.add_argument("--analysis_figure_name", default=None, help="accepted; scatter plots are not drawn")

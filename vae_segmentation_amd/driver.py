@@ -208,10 +208,17 @@ def save_checkpoint(prefix, epoch_label, model, optimizer, best):
 # validation (main_source.py:688-822): batch 1, hard Dice of the argmax prediction against the label
 # ----------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def validate(method, model, loader, nc):
+def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_dir=None, epoch=0):
     """main_source.py:688-822 / main_target.py:754-805: batch-1 forwards and hard Dice per case.  Forward only (no autograd graph is recorded: nothing is kept
-    for a backward pass — the per-(n, c) statistics the conv epilogues accumulate are the FORWARD's own, the next layer normalises with them)."""
-    scores = {}
+    for a backward pass — the per-(n, c) statistics the conv epilogues accumulate are the FORWARD's own, the next layer normalises with them).
+    keep_largest = k > 0: the hard prediction is cleaned up first as utils/utils.py:776-796 (predict_vol step 2) does — per foreground channel only the k largest
+    26-connected components of at least min_component voxels stay, what is removed becomes background (ops.keep_largest on the device: no host copy and no
+    synchronisation per case beyond the score's .item()) — the returned scores are the filtered ones and the unfiltered mean is printed beside them.
+    save_dir (--save_eval_result; main_source.py:721-727,751-757 / main_target.py:922-930): per case {epoch}_{idx}_pred.join / _pic / _gt (+ _pred_cc, the
+    filtered mask, when the filter is on) are written there with np.save."""
+    scores, raw = {}, {}
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
     for i, batch in enumerate(loader):
         gt = ops.onehot(batch[LABEL_KEY].cuda(non_blocking=True), nc)
         if method == "vae_train":
@@ -225,7 +232,25 @@ def validate(method, model, loader, nc):
         else:
             seg = model.Seg if hasattr(model, "Seg") else model
             pred = seg({IMG_KEY: batch[IMG_KEY].cuda(non_blocking=True)}, IMG_KEY, "pred")["pred"]
-        scores[i] = avg_dsc({"p": pred, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc).item()
+        filtered = None
+        if keep_largest > 0:
+            raw[i] = avg_dsc({"p": pred, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc)
+            filtered = ops.keep_largest(ops.hard_onehot(pred), k=keep_largest, min_size=min_component, connectivity=26,
+                                        lo_channel=min(1, nc - 1), to_background=True)
+            scores[i] = avg_dsc({"p": filtered, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc).item()
+        else:
+            scores[i] = avg_dsc({"p": pred, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc).item()
+        if save_dir is not None:
+            from .evaluation import binarize
+            stem = os.path.join(save_dir, "%d_%d_" % (epoch, i))
+            np.save(stem + "pred.join", binarize(pred).cpu().numpy())
+            np.save(stem + "pic", batch[IMG_KEY].cpu().numpy())
+            np.save(stem + "gt", binarize(gt).cpu().numpy())
+            if filtered is not None:
+                np.save(stem + "pred_cc", filtered.cpu().numpy())
+    if raw:
+        print("validation without the component filter: %f (keeping the %d largest components of at least %d voxels per class)"
+              % (float(np.mean([v.item() for v in raw.values()])), keep_largest, min_component))
     return scores
 
 
@@ -560,7 +585,9 @@ def run(args, side="source"):
                 scores, scores_noft = validate_finetune(runner, val_loader)
                 print("epoch %d validation result without finetuning: %f" % (epoch + 1, float(np.mean(list(scores_noft.values())))))
             else:
-                scores = validate(method, model, val_loader, nc)
+                save_dir = os.path.join("result", args.prefix) if getattr(args, "save_eval_result", False) and epoch % 10 == 0 else None
+                scores = validate(method, model, val_loader, nc, keep_largest=getattr(args, "val_keep_largest", 0),
+                                  min_component=getattr(args, "val_min_component", 0), save_dir=save_dir, epoch=epoch)
             mean = float(np.mean(list(scores.values()))) if scores else 0.0
             os.makedirs(os.path.join("tensorboard", args.prefix), exist_ok=True)
             with open(os.path.join("tensorboard", args.prefix, "score_%d.json" % epoch), "w") as f:
@@ -600,7 +627,7 @@ def check_target_flags(a):
     if a.pseudo_list is not None:
         need(a.method == "domain_adaptation", "--pseudo_list is read by --method domain_adaptation only (main_target.py:615; domain_adaptation_dis runs "
                                               "without it, :689)")
-    ignored = [n for n in ("save_more_reference", "save_eval_result", "analysis_figure_name", "generate_bounding_boxes", "resume") if getattr(a, n)]
+    ignored = [n for n in ("save_more_reference", "analysis_figure_name", "generate_bounding_boxes", "resume") if getattr(a, n)]
     if ignored:
         print("main_target.py: accepted and ignored (they drive figure / volume dumps the native entry point does not write): %s"
               % ", ".join("--" + n for n in ignored), file=sys.stderr)
@@ -620,5 +647,8 @@ def add_native_flags(parser):
     g.add_argument("--no_graph", action="store_true", help="eager launches instead of the HIP-graph replayed step")
     g.add_argument("--recompute", action="store_true", help="activation recomputation (checkpointing) of the Down / Up blocks: interior activations are "
                    "re-computed in backward instead of kept (BASELINE configs[4]); trades bandwidth for memory")
+    g.add_argument("--val_keep_largest", type=int, default=0, help="validation: keep only the K largest 26-connected components of every foreground class of the "
+                   "hard prediction before the Dice score (utils/utils.py:776-796, on the device); 0 = off, the reference's validation")
+    g.add_argument("--val_min_component", type=int, default=0, help="with --val_keep_largest: components of fewer voxels are dropped as well (predict_vol uses 10000)")
     g.add_argument("--train_first_epoch", action="store_true", help="domain_adaptation: also train in epoch 0 (the reference only "
                    "validates there, main_target.py:506)")

@@ -70,3 +70,28 @@ def avg_dsc(data_dict, source_key='align_lung', target_key='source_lung', binary
     else:
         bot, top = 0, 1
     return ops.Dice.apply(source_mask, target_mask, bot, top, eps, return_mean)
+
+
+def keep_largest_components(A, k=1, min_size=0, connectivity=26):
+    """utils/utils.py:776-796 (predict_vol step 2) on the device: per (n, c) plane of a planar (N, C, D, H, W) mask, binarize (>= 0.5), keep the k largest
+    connected components that hold at least min_size voxels, re-binarise.  predict_vol itself hard-codes k=2, min_size=10000, full connectivity."""
+    return ops.keep_largest(A, k=k, min_size=min_size, connectivity=connectivity)
+
+
+def check_connection(tumor_index, image):
+    """utils/utils.py:38-57 with the flood fill on the device: tumor_index is an (L, 3) host array of voxel indices into the volume `image`;
+    -> numpy array of L component numbers (26-connectivity), 1, 2, ... in the order in which tumor_index first reaches each component — the
+    reference's return value."""
+    import numpy as np
+    idx = np.asarray(tumor_index).reshape(-1, 3).astype(np.int64)
+    shape = tuple(np.shape(image))
+    mask = np.zeros(shape, dtype=np.float32)
+    mask[idx[:, 0], idx[:, 1], idx[:, 2]] = 1
+    labels, _, _ = ops.cc_label(torch.from_numpy(mask).cuda().view((1, 1) + shape), connectivity=26)
+    cc = labels.view(shape).cpu().numpy()[idx[:, 0], idx[:, 1], idx[:, 2]]
+    # the device numbers components by their first voxel in raster order; the reference by their first appearance in tumor_index
+    _, first = np.unique(cc, return_index=True)
+    order = np.empty(int(cc.max()) + 1 if cc.size else 1, dtype=np.int64)
+    order[cc[np.sort(first)]] = np.arange(1, len(first) + 1)
+    out = order[cc] if cc.size else cc
+    return out.astype(np.asarray(image).dtype)

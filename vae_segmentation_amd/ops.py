@@ -2368,6 +2368,63 @@ def binarize(a, mode=0, lo=0.2, hi=0.8):
     return out
 
 
+# connected components (csrc/cc.hip).  Workspaces are cached per (shape, connectivity, device) and never freed or moved — as the packed
+# weights are — so a captured graph that holds one stays valid.  Calls that share a workspace must be ordered on one stream.
+_CC_WORKSPACES = {}
+
+
+def cc_max_components(d, h, w, connectivity=26):
+    """rows per plane of the size table (include/vaeseg.h): the most components a (d, h, w) plane can hold"""
+    if connectivity == 26:
+        return ((d + 1) // 2) * ((h + 1) // 2) * ((w + 1) // 2)
+    return (d * h * w + 1) // 2
+
+
+def _cc_prepare(mask, connectivity):
+    _require_cuda(mask)
+    if mask.requires_grad:
+        raise RuntimeError("connected-component labelling is forward only: detach the input")
+    if mask.dim() != 5:
+        raise ValueError("expected a planar (N, C, D, H, W) tensor, got shape %s" % (tuple(mask.shape),))
+    m = _contig(mask.float())
+    if m.data_ptr() % 16:
+        m = m.clone()
+    n, c, d, h, w = m.shape
+    key = (n, c, d, h, w, int(connectivity), m.device)
+    ws = _CC_WORKSPACES.get(key)
+    if ws is None:
+        nbytes = lib.vs_cc_workspace_bytes(n, c, d, h, w, int(connectivity))
+        check(min(nbytes, 0), "cc_workspace_bytes")
+        ws = _CC_WORKSPACES[key] = torch.empty(nbytes, dtype=torch.uint8, device=m.device)
+    return m, ws
+
+
+def cc_label(mask, connectivity=26):
+    """Connected components of every (n, c) plane of a planar (N, C, D, H, W) mask (foreground: value >= 0.5) — utils/utils.py:20-57.
+    -> labels int32 (N, C, D, H, W): 0 background, 1..K in the order of each component's first voxel in raster order (scipy.ndimage.label's
+    numbering); counts int32 (N, C) = K; sizes int32 (N, C, cc_max_components(D, H, W, connectivity)): sizes[..., label - 1] voxels, 0 beyond K."""
+    m, ws = _cc_prepare(mask, connectivity)
+    n, c, d, h, w = m.shape
+    labels = torch.empty(m.shape, dtype=torch.int32, device=m.device)
+    counts = torch.empty((n, c), dtype=torch.int32, device=m.device)
+    check(lib.vs_cc_label(m.data_ptr(), labels.data_ptr(), counts.data_ptr(), n, c, d, h, w, int(connectivity), ws.data_ptr(), _stream()), "cc_label")
+    maxk = cc_max_components(d, h, w, connectivity)
+    sizes = ws[:n * c * maxk * 4].view(torch.int32).view(n, c, maxk).clone()       # the table sits at the start of the workspace
+    return labels, counts, sizes
+
+
+def keep_largest(mask, k=1, min_size=0, connectivity=26, lo_channel=0, to_background=False):
+    """utils/utils.py:776-796 (predict_vol step 2) per (n, c) plane: 1.0 on the k largest components that hold at least min_size voxels (equal
+    sizes: the one whose first voxel comes first), 0.0 elsewhere.  Channels below lo_channel are copied; with to_background (and lo_channel >= 1)
+    channel 0 gains every removed voxel, so a one-hot tensor stays one-hot."""
+    m, ws = _cc_prepare(mask, connectivity)
+    n, c, d, h, w = m.shape
+    out = torch.empty_like(m)
+    check(lib.vs_cc_keep_largest(m.data_ptr(), out.data_ptr(), n, c, d, h, w, int(connectivity), int(k), int(min(max(min_size, 0), 2 ** 31 - 1)),
+                                 int(lo_channel), int(bool(to_background)), ws.data_ptr(), _stream()), "cc_keep_largest")
+    return out
+
+
 def instnorm_stats(x):
     n, c = x.shape[0], x.shape[-1]
     st = _new_stats(n, c, x.device)
