@@ -490,6 +490,45 @@ int vs_cc_label(const float* mask, int* labels, int* counts, int n, int c, int d
 int vs_cc_keep_largest(const float* mask, float* out, int n, int c, int d, int h, int w, int connectivity, int k, int min_size, int lo_channel,
                        int to_background, void* workspace, void* stream);
 
+/* ---- surface distances of two masks (csrc/surface.hip) ---------------------------------------------------------------------------------------
+ * The validation metrics the segmentation literature reports next to Dice — ASSD, Hausdorff distance, HD95 — in medpy's convention
+ * (medpy.metric.binary.assd / hd / hd95 over scipy.ndimage), and their building block, an exact Euclidean distance transform.  The reference has no
+ * such metric.  Masks are planar fp32 (n, c, d, h, w), contiguous, foreground where the value is >= 0.5; every (n, c) plane is its own problem.
+ *   surface   S(X) = X & ~binary_erosion(X, structure, border_value=0): a foreground voxel with a background or out-of-volume neighbour among its 6
+ *             (connectivity 6, the default of medpy) or 26 neighbours.
+ *   distance  dist_F(v)^2 = min over voxels u of F of (sz dz)^2 + (sy dy)^2 + (sx dx)^2; spacing = HOST array {sz, sy, sx}, or NULL for unit spacing.
+ *             spacing == NULL: int32 squared distances, exact, INT32_MAX where the plane has no feature voxel; otherwise doubles, +inf there.
+ *             A min over exact candidates (unit spacing) / over the same rounded candidates (doubles): both builds of the library and every run
+ *             give the same bits; there are no atomics in this file.
+ *   record    per plane, for A = pred, B = gt and the directed sets d(A->B) = { dist_S(B)(v) : v in S(A) }, d(B->A) likewise:
+ *             count_ab, count_ba  their sizes                       sum_ab, sum_ba  the sums of the distances (a fixed summation tree)
+ *             max_sq              the largest squared distance      lo_sq, hi_sq    the squared order statistics v[k]^2, v[k+1]^2 of the union,
+ *                                                                                   k = floor(0.95 (count_ab + count_ba - 1)), 0-based, ascending
+ *             assd = (sum_ab / count_ab + sum_ba / count_ba) / 2    hd = sqrt(max_sq)
+ *             hd95 = numpy.percentile(union, 95), the default linear rule: v[k] + (0.95 (n - 1) - k) (v[k+1] - v[k])
+ *             A plane in which S(A) or S(B) is empty has both counts 0 and every other field NaN (medpy raises; a device op cannot).
+ * Limits: d, h <= 1024 (a line of the y / z passes is staged in LDS), d*h*w < 2^31, and d^2 + h^2 + w^2 < 2^31 - 1 for unit spacing: VS_ESHAPE beyond,
+ * as for an empty shape.  connectivity not 6 / 26, a spacing that is not positive and finite, a null pointer, an output that is one of the inputs:
+ * VS_EINVAL.  mask / out / workspace not 16-byte aligned: VS_EALIGN.  All of this is answered on the host before any launch.
+ * A call is a straight line of launches — no kernel waits for another workgroup, every loop is bounded by the data, nothing is allocated,
+ * synchronised or read back — and can be captured in a HIP graph. */
+typedef struct vs_surface_record {
+    long long count_ab, count_ba;
+    double sum_ab, sum_ba;
+    double max_sq, lo_sq, hi_sq;
+    double assd, hd, hd95;
+} vs_surface_record;
+/* out (fp32, mask's shape) = 1.0 on S(mask), 0.0 elsewhere */
+int vs_surface(const float* mask, float* out, int n, int c, int d, int h, int w, int connectivity, void* stream);
+/* out[v] = dist_F(v)^2 for F = { feature >= 0.5 }: int32 (spacing == NULL) or double, feature's shape.  The transform works in `out`: no workspace. */
+int vs_edt(const float* feature, void* out, int n, int c, int d, int h, int w, const double* spacing, void* stream);
+/* bytes of the workspace of vs_surface_distances (negative: VS_E*); with_spacing != 0: the double path.  Both surfaces as bytes, both distance maps
+ * and the list of surface distances: 18 bytes per voxel of one mask for unit spacing, 34 with a spacing, plus 32 / 40 bytes per 4096 voxels. */
+long long vs_edt_workspace_bytes(int n, int c, int d, int h, int w, int with_spacing);
+/* out: vs_surface_record[n * c].  workspace: 16-byte aligned, contents undefined on entry; the maps and surfaces of the call stay in it. */
+int vs_surface_distances(const float* pred, const float* gt, vs_surface_record* out, int n, int c, int d, int h, int w, int connectivity,
+                         const double* spacing, void* workspace, void* stream);
+
 /* ---- fully connected (VAE bottleneck, joint_model.py:216-218,242-243,248-253) -------------------- */
 /* y[b][j] = act( bias[j] + sum_k W[j][k] * x[b][phys(k)] )  with phys(k) = (k % pv)*pc + k / pv when pc > 0:
  * x is a channels-last activation [B][pv voxels][pc channels] read in the reference's flatten order

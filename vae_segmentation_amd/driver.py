@@ -208,15 +208,20 @@ def save_checkpoint(prefix, epoch_label, model, optimizer, best):
 # validation (main_source.py:688-822): batch 1, hard Dice of the argmax prediction against the label
 # ----------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_dir=None, epoch=0):
+def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_dir=None, epoch=0, surface=False, surface_log=None):
     """main_source.py:688-822 / main_target.py:754-805: batch-1 forwards and hard Dice per case.  Forward only (no autograd graph is recorded: nothing is kept
     for a backward pass — the per-(n, c) statistics the conv epilogues accumulate are the FORWARD's own, the next layer normalises with them).
     keep_largest = k > 0: the hard prediction is cleaned up first as utils/utils.py:776-796 (predict_vol step 2) does — per foreground channel only the k largest
     26-connected components of at least min_component voxels stay, what is removed becomes background (ops.keep_largest on the device: no host copy and no
     synchronisation per case beyond the score's .item()) — the returned scores are the filtered ones and the unfiltered mean is printed beside them.
     save_dir (--save_eval_result; main_source.py:721-727,751-757 / main_target.py:922-930): per case {epoch}_{idx}_pred.join / _pic / _gt (+ _pred_cc, the
-    filtered mask, when the filter is on) are written there with np.save."""
+    filtered mask, when the filter is on) are written there with np.save.
+    surface (--val_surface): additionally ASSD and HD95 (evaluation.surface_metrics: medpy's convention, unit spacing, on the device) of the hard prediction —
+    the filtered one when the filter is on, the unfiltered values are then reported beside them — against the label for every foreground class; their nanmean and
+    the number of undefined (empty-surface) entries are printed, the per-case values go to the dict surface_log.  The returned scores are not affected."""
     scores, raw = {}, {}
+    surf, surf_raw = {}, {}
+    lo = min(1, nc - 1)
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
     for i, batch in enumerate(loader):
@@ -240,6 +245,12 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
             scores[i] = avg_dsc({"p": filtered, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc).item()
         else:
             scores[i] = avg_dsc({"p": pred, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc).item()
+        if surface:
+            hard = ops.hard_onehot(pred)
+            if filtered is not None:
+                surf_raw[i] = ops.surface_distances(hard[:, lo:], gt[:, lo:])
+                hard = filtered
+            surf[i] = ops.surface_distances(hard[:, lo:], gt[:, lo:])
         if save_dir is not None:
             from .evaluation import binarize
             stem = os.path.join(save_dir, "%d_%d_" % (epoch, i))
@@ -251,6 +262,25 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
     if raw:
         print("validation without the component filter: %f (keeping the %d largest components of at least %d voxels per class)"
               % (float(np.mean([v.item() for v in raw.values()])), keep_largest, min_component))
+    if surf:
+        def table(recs, name):                                   # one host copy per metric, after the last case
+            return torch.stack([recs[i][name].reshape(-1) for i in sorted(recs)]).cpu().numpy()
+        for recs, tag in ((surf, ""), (surf_raw, " without the component filter")):
+            if not recs:
+                continue
+            a, h = table(recs, "assd"), table(recs, "hd95")
+            undefined = int(np.isnan(a).sum())
+            if undefined == a.size:
+                print("validation surface distances%s: undefined in all %d entries (an empty surface)" % (tag, a.size))
+            else:
+                print("validation surface distances%s: ASSD %f, HD95 %f voxels (%d of %d case x class entries undefined)"
+                      % (tag, float(np.nanmean(a)), float(np.nanmean(h)), undefined, a.size))
+            if surface_log is not None:
+                suffix = "_unfiltered" if tag else ""
+                for row, i in enumerate(sorted(recs)):
+                    entry = surface_log.setdefault(i, {})
+                    entry["assd" + suffix] = [float(v) for v in a[row]]
+                    entry["hd95" + suffix] = [float(v) for v in h[row]]
     return scores
 
 
@@ -581,17 +611,22 @@ def run(args, side="source"):
                                                                    "graph replay" if stepper is not None else "eager"))
         if rank == 0:
             model.eval()
+            surface_log = {}                                                       # --val_surface: per-case ASSD / HD95, filled by validate
             if runner is not None and (epoch != 0 or args.test_only):             # main_target.py:811
                 scores, scores_noft = validate_finetune(runner, val_loader)
                 print("epoch %d validation result without finetuning: %f" % (epoch + 1, float(np.mean(list(scores_noft.values())))))
             else:
                 save_dir = os.path.join("result", args.prefix) if getattr(args, "save_eval_result", False) and epoch % 10 == 0 else None
                 scores = validate(method, model, val_loader, nc, keep_largest=getattr(args, "val_keep_largest", 0),
-                                  min_component=getattr(args, "val_min_component", 0), save_dir=save_dir, epoch=epoch)
+                                  min_component=getattr(args, "val_min_component", 0), save_dir=save_dir, epoch=epoch,
+                                  surface=bool(getattr(args, "val_surface", False)), surface_log=surface_log)
             mean = float(np.mean(list(scores.values()))) if scores else 0.0
             os.makedirs(os.path.join("tensorboard", args.prefix), exist_ok=True)
             with open(os.path.join("tensorboard", args.prefix, "score_%d.json" % epoch), "w") as f:
                 json.dump(scores, f)
+            if surface_log:
+                with open(os.path.join("tensorboard", args.prefix, "surface_%d.json" % epoch), "w") as f:
+                    json.dump(surface_log, f)
             print("epoch %d validation result: %f, best result %f." % (epoch + 1, mean, best))
             if not args.test_only and (epoch + 1) % max(1, args.save_epoch // args.eval_epoch) == 0:
                 save_checkpoint(args.prefix, (epoch + 1) * args.eval_epoch, model, optimizer, mean > best)
@@ -650,5 +685,7 @@ def add_native_flags(parser):
     g.add_argument("--val_keep_largest", type=int, default=0, help="validation: keep only the K largest 26-connected components of every foreground class of the "
                    "hard prediction before the Dice score (utils/utils.py:776-796, on the device); 0 = off, the reference's validation")
     g.add_argument("--val_min_component", type=int, default=0, help="with --val_keep_largest: components of fewer voxels are dropped as well (predict_vol uses 10000)")
+    g.add_argument("--val_surface", action="store_true", help="validation: also report ASSD and HD95 (medpy's convention, in voxels) of the hard prediction against "
+                   "the label per foreground class, computed on the device; per-case values go to tensorboard/<prefix>/surface_<epoch>.json")
     g.add_argument("--train_first_epoch", action="store_true", help="domain_adaptation: also train in epoch 0 (the reference only "
                    "validates there, main_target.py:506)")

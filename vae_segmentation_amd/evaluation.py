@@ -95,3 +95,38 @@ def check_connection(tumor_index, image):
     order[cc[np.sort(first)]] = np.arange(1, len(first) + 1)
     out = order[cc] if cc.size else cc
     return out.astype(np.asarray(image).dtype)
+
+
+def _planar(X):
+    if X.dim() == 3:
+        return X.reshape((1, 1) + tuple(X.shape)), True
+    if X.dim() == 5:
+        return X, False
+    raise ValueError("expected a (D, H, W) volume or a planar (N, C, D, H, W) tensor, got shape %s" % (tuple(X.shape),))
+
+
+def surface_metrics(A, B, spacing=None, connectivity=6):
+    """ASSD, Hausdorff distance and HD95 of the binarised (>= 0.5) masks A (prediction) against B (label) in medpy's convention
+    (medpy.metric.binary.assd / hd / hd95: surfaces by binary erosion, Euclidean distances under `spacing` = (sz, sy, sx), the 95th percentile of the
+    union of both directed distance sets), per (n, c) plane, on the device (csrc/surface.hip): no host copy, no synchronisation.
+    A, B: (D, H, W) or (N, C, D, H, W).  -> the dict of ops.surface_distances, 0-d tensors for a single volume, (N, C) otherwise; a plane in which
+    either surface is empty gives NaN where medpy raises."""
+    a, single = _planar(A)
+    b, _ = _planar(B)
+    rec = ops.surface_distances(a.detach(), b.detach(), spacing=spacing, connectivity=connectivity)
+    return {k: v.reshape(()) for k, v in rec.items()} if single else rec
+
+
+def assd(A, B, spacing=None, connectivity=6):
+    """average symmetric surface distance (medpy.metric.binary.assd)"""
+    return surface_metrics(A, B, spacing, connectivity)["assd"]
+
+
+def hd(A, B, spacing=None, connectivity=6):
+    """Hausdorff distance (medpy.metric.binary.hd)"""
+    return surface_metrics(A, B, spacing, connectivity)["hd"]
+
+
+def hd95(A, B, spacing=None, connectivity=6):
+    """95th percentile of the Hausdorff distance (medpy.metric.binary.hd95)"""
+    return surface_metrics(A, B, spacing, connectivity)["hd95"]

@@ -2425,6 +2425,83 @@ def keep_largest(mask, k=1, min_size=0, connectivity=26, lo_channel=0, to_backgr
     return out
 
 
+# surface distances (csrc/surface.hip).  The workspace of surface_distances is cached per (shape, path, device) like the CC one.
+_EDT_WORKSPACES = {}
+SURFACE_RECORD_FIELDS = ("count_ab", "count_ba", "sum_ab", "sum_ba", "max_sq", "lo_sq", "hi_sq", "assd", "hd", "hd95")      # vs_surface_record
+
+
+def _spacing_array(spacing):
+    """None, or the (sz, sy, sx) doubles the library reads on the host during the call"""
+    if spacing is None:
+        return None
+    vals = [float(s) for s in spacing]
+    if len(vals) != 3:
+        raise ValueError("spacing is (sz, sy, sx), got %r" % (spacing,))
+    return (_ctypes.c_double * 3)(*vals)
+
+
+def _mask_prepare(mask, what):
+    _require_cuda(mask)
+    if mask.requires_grad:
+        raise RuntimeError("%s is forward only: detach the input" % what)
+    if mask.dim() != 5:
+        raise ValueError("expected a planar (N, C, D, H, W) tensor, got shape %s" % (tuple(mask.shape),))
+    m = _contig(mask.float())
+    if m.data_ptr() % 16:
+        m = m.clone()
+    return m
+
+
+def surface(mask, connectivity=6):
+    """S(X) = X & ~binary_erosion(X) per (n, c) plane of a planar (N, C, D, H, W) mask (foreground: value >= 0.5): fp32, 1.0 on foreground voxels that have a
+    background or out-of-volume neighbour among their 6 (default, medpy's) or 26 neighbours."""
+    m = _mask_prepare(mask, "surface extraction")
+    n, c, d, h, w = m.shape
+    out = torch.empty_like(m)
+    check(lib.vs_surface(m.data_ptr(), out.data_ptr(), n, c, d, h, w, int(connectivity), _stream()), "surface")
+    return out
+
+
+def edt(feature, spacing=None, squared=False):
+    """Exact Euclidean distance of every voxel to the nearest voxel with feature >= 0.5, per (n, c) plane of a planar (N, C, D, H, W) tensor.
+    spacing None and squared: int32 squared distances (2^31 - 1 in a plane without feature voxels).  Otherwise fp64 — squared or not — with
+    spacing = (sz, sy, sx) or unit spacing; +inf in a plane without feature voxels."""
+    m = _mask_prepare(feature, "the distance transform")
+    n, c, d, h, w = m.shape
+    sp = _spacing_array(spacing)
+    out = torch.empty(m.shape, dtype=torch.int32 if sp is None else torch.float64, device=m.device)
+    check(lib.vs_edt(m.data_ptr(), out.data_ptr(), n, c, d, h, w, sp, _stream()), "edt")
+    if sp is None:
+        if squared:
+            return out
+        sq = out.double()
+        return torch.where(out == 2 ** 31 - 1, torch.full_like(sq, float("inf")), sq).sqrt_()
+    return out if squared else out.sqrt_()
+
+
+def surface_distances(pred, gt, spacing=None, connectivity=6):
+    """The surface-distance record of every (n, c) plane (include/vaeseg.h vs_surface_record; A = pred, B = gt): a dict of (N, C) device tensors —
+    count_ab, count_ba (int64), sum_ab, sum_ba, max_sq, lo_sq, hi_sq, assd, hd, hd95 (fp64).  A plane with an empty surface has counts 0 and NaN elsewhere."""
+    a, b = _mask_prepare(pred, "surface distances"), _mask_prepare(gt, "surface distances")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("surface_distances: the two masks differ in shape or device: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+    n, c, d, h, w = a.shape
+    sp = _spacing_array(spacing)
+    key = (n, c, d, h, w, sp is not None, a.device)
+    ws = _EDT_WORKSPACES.get(key)
+    if ws is None:
+        nbytes = lib.vs_edt_workspace_bytes(n, c, d, h, w, int(sp is not None))
+        check(min(nbytes, 0), "edt_workspace_bytes")
+        ws = _EDT_WORKSPACES[key] = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+    rec = torch.empty((n, c, len(SURFACE_RECORD_FIELDS)), dtype=torch.float64, device=a.device)
+    check(lib.vs_surface_distances(a.data_ptr(), b.data_ptr(), rec.data_ptr(), n, c, d, h, w, int(connectivity), sp, ws.data_ptr(), _stream()),
+          "surface_distances")
+    out = {name: rec[..., i] for i, name in enumerate(SURFACE_RECORD_FIELDS)}
+    counts = rec[..., :2].view(torch.int64)                     # the record's first two members are 64-bit integers
+    out["count_ab"], out["count_ba"] = counts[..., 0], counts[..., 1]
+    return out
+
+
 def instnorm_stats(x):
     n, c = x.shape[0], x.shape[-1]
     st = _new_stats(n, c, x.device)
