@@ -529,6 +529,30 @@ long long vs_edt_workspace_bytes(int n, int c, int d, int h, int w, int with_spa
 int vs_surface_distances(const float* pred, const float* gt, vs_surface_record* out, int n, int c, int d, int h, int w, int connectivity,
                          const double* spacing, void* workspace, void* stream);
 
+/* ---- sliding-window prediction of a whole volume (csrc/window.hip; no counterpart in the reference) -------------------------------
+ * A volume (C, D, H, W) is tiled with overlapping cubic windows of side `patch`, a network maps batches (B, C, P, P, P) of them to planar
+ * probabilities (B, K, P, P, P), and the windows are blended: prob[k][v] = sum_i w_i(v) p_i[k](v) / sum_i w_i(v) over the windows i that cover
+ * v, with a separable importance map w = (wz[lz] * wy[ly]) * wx[lx] (fp32, rounded after each product) of the voxel's position in the window.
+ * All tensors are planar fp32, 16-byte aligned.  No call synchronises; none uses atomics: the sums are bit-identical for every batch size,
+ * from run to run and between the two builds of the library.
+ *
+ * vs_sw_plan (host only): per axis step = max(1, floor(patch * (1 - overlap))), n = 1 if S <= patch else ceil((S - patch) / step) + 1, the
+ * origin of window i is min(i * step, max(S - patch, 0)).  -> the number of windows nw (negative: VS_E*); with origins != NULL also the table
+ * int[nw][3] = (z, y, x) of every window, D-major, then H, then W (capacity: the entries origins has room for).  0 <= overlap < 1. */
+int vs_sw_plan(int d, int h, int w, int patch, double overlap, int* origins, int capacity);
+/* batch[s] = window first[0] + s of the plan (origins: the DEVICE copy of the table) for s < b; `first` is a DEVICE word, so a launch captured
+ * into a HIP graph serves every batch.  Slots with first[0] + s >= nw are filled with cval, as are positions past the volume (S < patch). */
+int vs_sw_gather(const float* volume, float* batch, const int* origins, const int* first, int nw, int b, int c, int d, int h, int w, int patch,
+                 float cval, void* stream);
+/* acc[k][v] = fmaf(w, prob[s][k][v - origin], acc[k][v]) and wsum[v] += w for every slot s < b with first[0] + s < nw and every voxel v of its
+ * window inside the volume; a voxel's terms are added in ascending window index (batches must be accumulated in ascending order of `first`).
+ * acc (k, d, h, w) and wsum (d, h, w) start as zeros; wz, wy, wx: `patch` floats each, on the device. */
+int vs_sw_accumulate(const float* prob, float* acc, float* wsum, const int* origins, const int* first, int nw, int b, int k, int d, int h, int w,
+                     int patch, const float* wz, const float* wy, const float* wx, void* stream);
+/* prob = acc / wsum (prob may be acc itself); label (may be NULL): the channel argmax as bytes (k <= 255; ties: the first maximal channel, a
+ * NaN channel wins, as vs_hard_onehot); onehot (may be NULL): the label's planar fp32 one-hot (k, d, h, w). */
+int vs_sw_finalize(const float* acc, const float* wsum, float* prob, unsigned char* label, float* onehot, int k, int d, int h, int w, void* stream);
+
 /* ---- fully connected (VAE bottleneck, joint_model.py:216-218,242-243,248-253) -------------------- */
 /* y[b][j] = act( bias[j] + sum_k W[j][k] * x[b][phys(k)] )  with phys(k) = (k % pv)*pc + k / pv when pc > 0:
  * x is a channels-last activation [B][pv voxels][pc channels] read in the reference's flatten order

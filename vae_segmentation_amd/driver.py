@@ -114,6 +114,12 @@ class DeviceCaseLoader:
     def __len__(self):
         return len(self.names) // self.bs if self.drop_last else (len(self.names) + self.bs - 1) // self.bs
 
+    def whole_cases(self):
+        """--val_whole_volume: every case as it is on disk — (raw image (D, H, W), relabelled label (D, H, W)) on the device, in list order, uncropped"""
+        for name in self.names:
+            merge = torch.from_numpy(np.load(os.path.join(self.root, name)).astype(np.float32)).cuda(non_blocking=True)
+            yield merge[..., 0].contiguous(), self._dg.relabel(merge[..., 1].contiguous(), self.mask_index)
+
     def __iter__(self):
         order = np.arange(len(self.names))
         if self.shuffle:
@@ -294,10 +300,83 @@ def validate_finetune(runner, loader):
     return scores, scores_noft
 
 
+def _hard_dice(pred_hot, gt_hot, lo, nc):
+    """hard Dice of two planar one-hot tensors (K, ...) over the classes [lo, nc), avg_dsc(binary=True)'s arithmetic; the Dice kernel reads whole
+    16-byte quads, so a volume of any size is padded with voxels that belong to no class on either side"""
+    a, b = pred_hot.reshape(1, pred_hot.shape[0], -1), gt_hot.reshape(1, gt_hot.shape[0], -1)
+    pad = (-a.shape[-1]) % 4
+    if pad:
+        a, b = torch.nn.functional.pad(a, (0, pad)), torch.nn.functional.pad(b, (0, pad))
+    return ops.Dice.apply(a, b, lo, nc, EPS_EVALUATION, True)
+
+
+WHOLE_VOLUME_CVAL = (0.0 - 100.0) / 300.0          # what CropResize's zero padding becomes after Clip(-200, 400) and CenterIntensities(100, 300)
+
+
+@torch.no_grad()
+def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="gaussian", keep_largest=0, min_component=0, log=None):
+    """--val_whole_volume: label-free coarse-to-fine inference, scored.  `cases` yields (raw image, relabelled label) (D, H, W) device tensors
+    (DeviceCaseLoader.whole_cases).  Per case:
+      dice_whole       the clipped and centred WHOLE volume is predicted by sliding window with the segmentation network (evaluation.sliding_window_predict,
+                       cubic windows of side `patch`); hard Dice per foreground class of that prediction — after ops.keep_largest when keep_largest > 0 —
+                       against the whole label
+      dice_label_free  the case is cropped by CropResize with the box of the PREDICTION (evaluation.localise -> <field>_pancreas_pred) instead of the
+                       label's, the fine forward runs on the crop, hard Dice in crop space.  A coarse prediction without foreground gives no box: 0.
+    Both means are printed; the per-case values go to the dict `log`.  -> (mean dice_whole, mean dice_label_free)"""
+    from . import data_gpu
+    from .evaluation import localise, segmentation_model_fn, sliding_window_predict
+    seg = model.Seg if hasattr(model, "Seg") else model
+    model_fn = segmentation_model_fn(seg)
+    lo = min(1, nc - 1)
+    whole, free = {}, {}
+    for i, (img, lab) in enumerate(cases):
+        d = {IMG_KEY: img.clone()}
+        d = data_gpu.CenterIntensities([IMG_KEY], subtrahend=100, divisor=300)(data_gpu.Clip([IMG_KEY], new_min=-200, new_max=400)(d))
+        res = sliding_window_predict(model_fn, d[IMG_KEY], patch, overlap=overlap, blend=blend, batch=batch, cval=WHOLE_VOLUME_CVAL)
+        if res["prob"].shape[0] != nc:
+            raise ValueError("whole-volume validation: the network predicts %d classes, the labels have %d" % (res["prob"].shape[0], nc))
+        hard = ops.hard_onehot(res["prob"][None])
+        if keep_largest > 0:
+            hard = ops.keep_largest(hard, k=keep_largest, min_size=min_component, connectivity=26, lo_channel=lo, to_background=True)
+        gt = ops.onehot(lab[None, None], nc)
+        whole[i] = _hard_dice(hard[0], gt[0], lo, nc)
+        mask = localise(res["prob"], keep_largest=max(keep_largest, 1), min_size=min_component, lo_channel=lo)
+        if data_gpu.bounding_box(mask) is None:
+            free[i] = torch.zeros((), device=img.device)
+            continue
+        c = data_gpu.CropResize([IMG_KEY], (patch,) * 3)({IMG_KEY: img, LABEL_KEY: lab, IMG_KEY + "_pancreas_pred": mask})
+        c = data_gpu.CenterIntensities([IMG_KEY], subtrahend=100, divisor=300)(data_gpu.Clip([IMG_KEY], new_min=-200, new_max=400)(c))
+        fine = seg({IMG_KEY: c[IMG_KEY][None, None]}, IMG_KEY, "pred")["pred"]
+        free[i] = avg_dsc({"p": fine, "g": ops.onehot(c[LABEL_KEY][None, None], nc)}, "p", "g", binary=True, botindex=1, topindex=nc)
+    w = {i: float(v.item()) for i, v in whole.items()}                    # host copies after the last case
+    f = {i: float(v.item()) for i, v in free.items()}
+    mw, mf = (float(np.mean(list(x.values()))) if x else 0.0 for x in (w, f))
+    print("validation on whole volumes (sliding window %d^3, overlap %g, %s blend): dice_whole %f, dice_label_free %f over %d cases"
+          % (patch, overlap, blend, mw, mf, len(w)))
+    if log is not None:
+        for i in w:
+            log[i] = {"dice_whole": w[i], "dice_label_free": f[i]}
+    return mw, mf
+
+
+def check_whole_volume_flags(a, script="main_source.py"):
+    """--val_whole_volume reads whole cases from disk and needs a segmentation network"""
+    if not getattr(a, "val_whole_volume", False):
+        return
+    def need(cond, what):
+        if not cond:
+            raise SystemExit("%s: inconsistent flags — %s" % (script, what))
+    need(getattr(a, "real_data", False), "--val_whole_volume predicts whole merge.npy cases: it needs --real_data")
+    need(a.method not in ("vae_train", "discriminator_train", "embed_train", "refine_vae"), "--val_whole_volume needs a segmentation network, --method %s has none" % a.method)
+    need(0.0 <= a.sw_overlap < 1.0, "--sw_overlap must be in [0, 1)")
+    need(a.sw_batch >= 1, "--sw_batch must be at least 1")
+
+
 # ----------------------------------------------------------------------------------------------------
 # the loop
 # ----------------------------------------------------------------------------------------------------
 def run(args, side="source"):
+    check_whole_volume_flags(args, "main_%s.py" % side)
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if not torch.cuda.is_available():
         raise SystemExit("the native kernels need a GPU (there is no CPU path)")
@@ -627,6 +706,12 @@ def run(args, side="source"):
             if surface_log:
                 with open(os.path.join("tensorboard", args.prefix, "surface_%d.json" % epoch), "w") as f:
                     json.dump(surface_log, f)
+            if getattr(args, "val_whole_volume", False):                           # after validation, which it leaves as it is
+                whole_log = {}
+                validate_whole_volume(model, val_loader.whole_cases(), nc, args.size, overlap=args.sw_overlap, batch=args.sw_batch, blend=args.sw_blend,
+                                      keep_largest=getattr(args, "val_keep_largest", 0), min_component=getattr(args, "val_min_component", 0), log=whole_log)
+                with open(os.path.join("tensorboard", args.prefix, "whole_%d.json" % epoch), "w") as f:
+                    json.dump(whole_log, f)
             print("epoch %d validation result: %f, best result %f." % (epoch + 1, mean, best))
             if not args.test_only and (epoch + 1) % max(1, args.save_epoch // args.eval_epoch) == 0:
                 save_checkpoint(args.prefix, (epoch + 1) * args.eval_epoch, model, optimizer, mean > best)
@@ -687,5 +772,11 @@ def add_native_flags(parser):
     g.add_argument("--val_min_component", type=int, default=0, help="with --val_keep_largest: components of fewer voxels are dropped as well (predict_vol uses 10000)")
     g.add_argument("--val_surface", action="store_true", help="validation: also report ASSD and HD95 (medpy's convention, in voxels) of the hard prediction against "
                    "the label per foreground class, computed on the device; per-case values go to tensorboard/<prefix>/surface_<epoch>.json")
+    g.add_argument("--val_whole_volume", action="store_true", help="validation (with --real_data): additionally predict every WHOLE validation case by sliding window "
+                   "with the segmentation network (windows of --size) and report dice_whole — hard Dice against the whole label — and dice_label_free — the fine "
+                   "pass on a crop chosen by the prediction's box instead of the label's; per-case values go to tensorboard/<prefix>/whole_<epoch>.json")
+    g.add_argument("--sw_overlap", type=float, default=0.5, help="--val_whole_volume: overlap of neighbouring windows as a fraction of the window, in [0, 1)")
+    g.add_argument("--sw_batch", type=int, default=1, help="--val_whole_volume: windows per forward pass")
+    g.add_argument("--sw_blend", default="gaussian", choices=["gaussian", "constant"], help="--val_whole_volume: importance map of a window")
     g.add_argument("--train_first_epoch", action="store_true", help="domain_adaptation: also train in epoch 0 (the reference only "
                    "validates there, main_target.py:506)")

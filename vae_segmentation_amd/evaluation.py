@@ -130,3 +130,131 @@ def hd(A, B, spacing=None, connectivity=6):
 def hd95(A, B, spacing=None, connectivity=6):
     """95th percentile of the Hausdorff distance (medpy.metric.binary.hd95)"""
     return surface_metrics(A, B, spacing, connectivity)["hd95"]
+
+
+# ----------------------------------------------------------------------------------------------------
+# whole-volume inference: sliding-window prediction on the device (csrc/window.hip).  The reference has no counterpart
+# (utils/utils.py:predict_vol is a 2D slice loop); tests/sliding_util.py restates the algorithm in numpy.
+# ----------------------------------------------------------------------------------------------------
+class SlidingWindow:
+    """Sliding-window predictor for volumes of one shape: the plan, the importance map, the window counter and every buffer are made once, so the
+    object can be called for one volume after another.  model_fn maps a (B, C, P, P, P) fp32 batch to planar probabilities (B, K, P, P, P).
+
+    One batch is gather -> model_fn -> accumulate -> bump the window counter.  The counter is a DEVICE word (as the captured optimiser's
+    hyperparameters are), so with graph=True that batch is captured once into a HIP graph and replayed ceil(nw / B) times per volume; eagerly the
+    same launches are issued in a loop.  Either way the host never waits for the device between windows.  The sums are formed without atomics in
+    ascending window order: the result does not depend on B, and graph replay equals eager launches bit for bit."""
+
+    def __init__(self, model_fn, shape, patch, overlap=0.5, blend="gaussian", batch=1, cval=0.0, graph=False, device="cuda"):
+        shape = tuple(int(s) for s in shape)
+        if len(shape) == 3:
+            shape = (1,) + shape
+        if len(shape) != 4 or int(batch) < 1:
+            raise ValueError("SlidingWindow: shape is (C, D, H, W) or (D, H, W) and batch >= 1, got %r, %r" % (shape, batch))
+        self.model_fn, self.shape, self.patch, self.batch, self.cval = model_fn, shape, int(patch), int(batch), float(cval)
+        self.device = torch.device(device)
+        self.origins, self.nw = ops.sw_plan(shape[1:], self.patch, overlap, device=self.device)
+        self.weights = ops.sw_weights(self.patch, blend, device=self.device)
+        self.n_batches = (self.nw + self.batch - 1) // self.batch
+        self.volume = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self.first = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.windows = torch.empty((self.batch, shape[0]) + (self.patch,) * 3, dtype=torch.float32, device=self.device)
+        self.acc = self.wsum = None
+        self.use_graph, self.graph = bool(graph), None
+
+    def _one_batch(self):
+        ops.sw_gather(self.volume, self.origins, self.first, self.batch, cval=self.cval, out=self.windows)
+        prob = self.model_fn(self.windows)
+        if prob.dim() != 5 or prob.shape[0] != self.batch or tuple(prob.shape[2:]) != (self.patch,) * 3:
+            raise ValueError("sliding window: model_fn must return (B, K, P, P, P) = (%d, K, %d, %d, %d), got %s"
+                             % ((self.batch,) + (self.patch,) * 3 + (tuple(prob.shape),)))
+        if self.acc is None:                                     # K is known once the model has answered
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("sliding window: the accumulators must exist before a capture starts")
+            self.acc = torch.zeros((prob.shape[1],) + self.shape[1:], dtype=torch.float32, device=self.device)
+            self.wsum = torch.zeros(self.shape[1:], dtype=torch.float32, device=self.device)
+        ops.sw_accumulate(prob, self.acc, self.wsum, self.origins, self.first, self.weights)
+        self.first.add_(self.batch)
+
+    def _reset(self):
+        self.first.zero_()
+        if self.acc is not None:
+            self.acc.zero_()
+            self.wsum.zero_()
+
+    def _capture(self):
+        """one batch run eagerly on a side stream (the model's caches and K), its sums discarded, then the same batch captured"""
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            self._one_batch()
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        self._reset()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._one_batch()
+        self.graph = graph
+
+    @torch.no_grad()
+    def __call__(self, volume, onehot=False):
+        ops._require_cuda(volume)
+        vol = volume.detach()
+        if vol.dim() == 3:
+            vol = vol[None]
+        if tuple(vol.shape) != self.shape:
+            raise ValueError("sliding window: built for volumes of shape %s, got %s" % (self.shape, tuple(volume.shape)))
+        with torch.cuda.device(self.device):
+            self.volume.copy_(vol)
+            if self.use_graph and self.graph is None:
+                self._capture()
+            self._reset()
+            for _ in range(self.n_batches):
+                if self.graph is not None:
+                    self.graph.replay()
+                else:
+                    self._one_batch()
+            prob, label, hot = ops.sw_finalize(self.acc, self.wsum, label=True, onehot=onehot)
+        out = {"prob": prob, "label": label, "wsum": self.wsum.clone()}
+        if onehot:
+            out["onehot"] = hot
+        return out
+
+
+def sliding_window_predict(model_fn, volume, patch, overlap=0.5, blend="gaussian", batch=1, cval=0.0, graph=False):
+    """Whole-volume prediction of a fully convolutional 3D network: `volume` (C, D, H, W) or (D, H, W) on the device is tiled with overlapping cubic
+    windows of side `patch` (ops.sw_plan), model_fn — (B, C, P, P, P) -> planar probabilities (B, K, P, P, P) — runs on `batch` windows at a time, the
+    window probabilities are blended with the importance map `blend` ("gaussian" or "constant", ops.sw_weights) and normalised.  Runs under
+    torch.no_grad().  -> {"prob": (K, D, H, W) fp32, "label": (D, H, W) uint8 (argmax, ties to the first channel), "wsum": (D, H, W) fp32}.
+    graph=True captures one batch into a HIP graph and replays it (SlidingWindow, which also serves further volumes of the same shape)."""
+    ops._require_cuda(volume)
+    return SlidingWindow(model_fn, tuple(volume.shape), patch, overlap=overlap, blend=blend, batch=batch, cval=cval, graph=graph, device=volume.device)(volume)
+
+
+def segmentation_model_fn(seg):
+    """model_fn of sliding_window_predict for a modules.Segmentation (or a model that has one as .Seg), in whatever storage dtype it is set to"""
+    net = seg.Seg if hasattr(seg, "Seg") else seg
+
+    def model_fn(batch):
+        return net({"image": batch}, "image", "prob")["prob"]
+    return model_fn
+
+
+@torch.no_grad()
+def localise(prob_or_label, keep_largest=1, min_size=0, lo_channel=1):
+    """A coarse whole-volume prediction -> the (D, H, W) fp32 mask of where the organ is, ready to be put into a data dict as <field>_pancreas_pred for
+    data_gpu.CropResize.  prob_or_label: probabilities (K, D, H, W) — hardened by argmax — or a label map (D, H, W), whose labels >= lo_channel count as one
+    foreground class.  Per foreground class (channels from lo_channel on) only the keep_largest largest 26-connected components of at least min_size voxels
+    stay (ops.keep_largest; 0: no filter); the mask is the union of the classes."""
+    ops._require_cuda(prob_or_label)
+    x = prob_or_label.detach()
+    if x.dim() == 4:
+        hard = ops.hard_onehot(x[None])
+    elif x.dim() == 3:
+        k = max(int(lo_channel) + 1, 2)
+        hard = torch.stack([(x == c).float() if c < k - 1 else (x >= c).float() for c in range(k)])[None]
+    else:
+        raise ValueError("localise: expected probabilities (K, D, H, W) or a label map (D, H, W), got shape %s" % (tuple(x.shape),))
+    lo = min(int(lo_channel), hard.shape[1] - 1)
+    if keep_largest > 0:
+        hard = ops.keep_largest(hard, k=int(keep_largest), min_size=int(min_size), connectivity=26, lo_channel=lo)
+    return hard[0, lo:].amax(0).contiguous()

@@ -2502,6 +2502,109 @@ def surface_distances(pred, gt, spacing=None, connectivity=6):
     return out
 
 
+# sliding-window prediction (csrc/window.hip).  evaluation.sliding_window_predict drives these; nothing here synchronises.
+SW_BLENDS = ("constant", "gaussian")
+SW_GAUSSIAN_FLOOR = 1e-3
+
+
+def sw_plan_host(shape, patch, overlap):
+    """vs_sw_plan on the host: the window origins of a (D, H, W) volume tiled with cubic `patch` windows -> numpy int32 (nw, 3), D-major, then H, then W.
+    Per axis step = max(1, floor(patch (1 - overlap))), n = 1 if S <= patch else ceil((S - patch) / step) + 1, origin i = min(i step, max(S - patch, 0))."""
+    import numpy as np
+    d, h, w = (int(s) for s in shape)
+    nw = lib.vs_sw_plan(d, h, w, int(patch), float(overlap), None, 0)
+    check(min(nw, 0), "sw_plan")
+    table = np.empty((nw, 3), dtype=np.int32)
+    check(min(lib.vs_sw_plan(d, h, w, int(patch), float(overlap), table.ctypes.data, nw), 0), "sw_plan")
+    return table
+
+
+def sw_plan(shape, patch, overlap, device="cuda"):
+    """-> (origins: int32 (nw, 3) tensor on `device`, nw) — sw_plan_host's table where the kernels read it"""
+    table = sw_plan_host(shape, patch, overlap)
+    return torch.from_numpy(table).to(device), int(table.shape[0])
+
+
+def sw_weights(patch, blend="gaussian", device="cuda"):
+    """The separable importance map of a window as an fp32 (3, patch) tensor (rows: z, y, x; a voxel's weight is their fp32 product).
+    "constant": ones.  "gaussian": exp(-((i - (patch - 1) / 2) / sigma)^2 / 2) with sigma = patch / 8 per axis, computed in float64, floored at
+    1e-3 and rounded to fp32."""
+    import numpy as np
+    p = int(patch)
+    if p <= 0:
+        raise ValueError("sw_weights: patch must be positive, got %r" % (patch,))
+    if blend == "constant":
+        row = np.ones(p, dtype=np.float64)
+    elif blend == "gaussian":
+        i = np.arange(p, dtype=np.float64)
+        row = np.maximum(np.exp(-0.5 * ((i - (p - 1) / 2.0) / (p / 8.0)) ** 2), SW_GAUSSIAN_FLOOR)
+    else:
+        raise ValueError("sw_weights: blend is one of %s, got %r" % (SW_BLENDS, blend))
+    return torch.from_numpy(np.stack([row, row, row]).astype(np.float32)).to(device)
+
+
+def _sw_common(origins, first, weights, patch):
+    if origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 3 or not origins.is_contiguous():
+        raise ValueError("sw: origins is the contiguous int32 (nw, 3) table of sw_plan")
+    if first.dtype != torch.int32 or first.numel() != 1:
+        raise ValueError("sw: first is one int32 device word")
+    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (3, patch) or not weights.is_contiguous()):
+        raise ValueError("sw: weights is the contiguous fp32 (3, %d) tensor of sw_weights" % patch)
+
+
+def sw_gather(volume, origins, first, batch, patch=None, cval=0.0, out=None):
+    """Windows [first, first + batch) of the plan, cut from the planar fp32 volume (C, D, H, W) -> (batch, C, P, P, P).  `first`: an int32 device word.
+    Slots past the plan and positions past the volume read cval.  out: the batch tensor to fill (a fixed address for a captured launch)."""
+    _require_cuda(volume, origins, first, out)
+    if volume.dim() != 4 or volume.dtype != torch.float32 or not volume.is_contiguous() or volume.data_ptr() % 16:
+        raise ValueError("sw_gather: expected a contiguous, 16-byte aligned fp32 (C, D, H, W) volume, got %s %s" % (tuple(volume.shape), volume.dtype))
+    c, d, h, w = volume.shape
+    if out is None:
+        out = torch.empty((int(batch), c) + (int(patch),) * 3, dtype=torch.float32, device=volume.device)
+    p = out.shape[-1]
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (int(batch), c, p, p, p) or (patch is not None and p != int(patch)):
+        raise ValueError("sw_gather: out must be a contiguous fp32 (%d, %d, P, P, P) tensor, got %s" % (int(batch), c, tuple(out.shape)))
+    _sw_common(origins, first, None, p)
+    check(lib.vs_sw_gather(volume.data_ptr(), out.data_ptr(), origins.data_ptr(), first.data_ptr(), origins.shape[0], int(batch), c, d, h, w, p,
+                           float(cval), _stream()), "sw_gather")
+    return out
+
+
+def sw_accumulate(prob, acc, wsum, origins, first, weights):
+    """acc (K, D, H, W) += w * prob (B, K, P, P, P) and wsum (D, H, W) += w for the windows [first, first + B) that lie in the plan, in place, every voxel's
+    terms in ascending window index and without atomics: bit-identical for every B.  Batches are accumulated in ascending order of `first`."""
+    _require_cuda(prob, acc, wsum, origins, first, weights)
+    pr = _contig(prob.detach().float())
+    if pr.data_ptr() % 16:
+        pr = pr.clone()
+    if pr.dim() != 5 or acc.dim() != 4 or wsum.dim() != 3 or pr.shape[1] != acc.shape[0] or tuple(acc.shape[1:]) != tuple(wsum.shape) or \
+            not (pr.shape[2] == pr.shape[3] == pr.shape[4]):
+        raise ValueError("sw_accumulate: prob (B, K, P, P, P), acc (K, D, H, W), wsum (D, H, W); got %s, %s, %s" % (tuple(prob.shape), tuple(acc.shape), tuple(wsum.shape)))
+    for t in (acc, wsum):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("sw_accumulate: acc and wsum are contiguous fp32 tensors (they are updated in place)")
+    b, k, p = pr.shape[0], pr.shape[1], pr.shape[2]
+    _sw_common(origins, first, weights, p)
+    d, h, w = wsum.shape
+    check(lib.vs_sw_accumulate(pr.data_ptr(), acc.data_ptr(), wsum.data_ptr(), origins.data_ptr(), first.data_ptr(), origins.shape[0], b, k, d, h, w, p,
+                               weights[0].data_ptr(), weights[1].data_ptr(), weights[2].data_ptr(), _stream()), "sw_accumulate")
+
+
+def sw_finalize(acc, wsum, label=True, onehot=False):
+    """-> (prob = acc / wsum (K, D, H, W) fp32, label (D, H, W) uint8 or None, onehot (K, D, H, W) fp32 or None) in one pass.  The label is the channel
+    argmax of prob, ties to the first maximal channel (vs_hard_onehot's rule)."""
+    _require_cuda(acc, wsum)
+    if acc.dim() != 4 or tuple(acc.shape[1:]) != tuple(wsum.shape) or acc.dtype != torch.float32 or wsum.dtype != torch.float32 or \
+            not acc.is_contiguous() or not wsum.is_contiguous():
+        raise ValueError("sw_finalize: acc (K, D, H, W) and wsum (D, H, W) are contiguous fp32 tensors; got %s, %s" % (tuple(acc.shape), tuple(wsum.shape)))
+    k, d, h, w = acc.shape
+    prob = torch.empty_like(acc)
+    lab = torch.empty((d, h, w), dtype=torch.uint8, device=acc.device) if label else None
+    hot = torch.empty_like(acc) if onehot else None
+    check(lib.vs_sw_finalize(acc.data_ptr(), wsum.data_ptr(), prob.data_ptr(), _p(lab), _p(hot), k, d, h, w, _stream()), "sw_finalize")
+    return prob, lab, hot
+
+
 def instnorm_stats(x):
     n, c = x.shape[0], x.shape[-1]
     st = _new_stats(n, c, x.device)
