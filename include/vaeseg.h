@@ -553,6 +553,25 @@ int vs_sw_accumulate(const float* prob, float* acc, float* wsum, const int* orig
  * NaN channel wins, as vs_hard_onehot); onehot (may be NULL): the label's planar fp32 one-hot (k, d, h, w). */
 int vs_sw_finalize(const float* acc, const float* wsum, float* prob, unsigned char* label, float* onehot, int k, int d, int h, int w, void* stream);
 
+/* ---- a crop-space prediction pasted back into scan geometry (csrc/uncrop.hip; no counterpart in the reference) ---------------------
+ * data_gpu.CropResize cuts the scan rows [lo, hi) of every axis, places them at [off, off + hi - lo) of a zero cube of side `side` and resizes the
+ * cube to patch^3 (data_gpu.crop_geometry gives lo, hi, off, side for a box).  vs_uncrop is the way back for the network's answer on that patch:
+ * prob (k, patch, patch, patch), planar fp32, 1 <= k <= 8, is resampled onto the scan grid (d, h, w).
+ *   A scan voxel v with lo <= v < hi on every axis has cube index u = v - lo + off and patch coordinate q = (u + 0.5) * patch / side - 0.5 per axis,
+ *   the inverse of vs_data_zoom's grid (skimage / scipy.ndimage.zoom(grid_mode=True)), computed in fp64.
+ *   interp 1 (linear): q is clamped to [0, patch - 1] (edge replicate) and each class is interpolated trilinearly, weights and the eight products
+ *   in fp64, the sum rounded to fp32 once: scipy.ndimage.zoom(prob[c], side / patch, order=1, mode='nearest', grid_mode=True) on the cube rows that
+ *   exist in the scan.  interp 0 (nearest): the sample at index floor(q + 0.5), clamped - the rounding of vs_data_zoom's order 0.
+ *   Every other voxel lies outside the cube: probability 1 in channel 0 and 0 in the others.
+ * label (d, h, w) bytes: the channel argmax of those fp32 probabilities, ties to the first maximal channel, a NaN channel wins (vs_hard_onehot,
+ * vs_sw_finalize); 0 outside the cube.  prob_out (may be NULL): the resampled probabilities, planar fp32 (k, d, h, w).
+ * One launch writes every element of label and prob_out exactly once: no memset before it, no atomics, bit-identical from run to run and between
+ * the two builds.  It does not synchronise.  Pointers are 16-byte aligned (VS_EALIGN); a geometry with lo < 0, hi < lo, hi > the scan's size,
+ * off < 0 or off + hi - lo > side, side <= 0, k outside [1, 8] or interp outside {0, 1}: VS_EINVAL, on the host before any launch.  The kernel
+ * clamps every patch index itself and bounds its stores by (d, h, w) alone. */
+int vs_uncrop(const float* prob, unsigned char* label, float* prob_out, int k, int patch, int d, int h, int w, int lo_z, int lo_y, int lo_x,
+              int hi_z, int hi_y, int hi_x, int off_z, int off_y, int off_x, int side, int interp, void* stream);
+
 /* ---- fully connected (VAE bottleneck, joint_model.py:216-218,242-243,248-253) -------------------- */
 /* y[b][j] = act( bias[j] + sum_k W[j][k] * x[b][phys(k)] )  with phys(k) = (k % pv)*pc + k / pv when pc > 0:
  * x is a channels-last activation [B][pv voxels][pc channels] read in the reference's flatten order

@@ -67,6 +67,20 @@ def crop_pad_cube(vol, centre, L, pad, shift=0):
     return out
 
 
+def crop_geometry(box, shape, shift=0):
+    """Where CropResize puts a scan of `shape` whose box is `box` = (min[3], max[3]) (bounding_box): -> (lo[3], hi[3], off[3], side), plain ints.  The
+    scan rows [lo, hi) of every axis land at [off, off + hi - lo) of a zero cube of side `side`, which is then resized to the patch — the integers of
+    CropResize.__call__ and crop_pad_cube.  Host arithmetic only; ops.uncrop takes the tuple to paste a patch-space prediction back into the scan."""
+    bmin, bmax = (np.asarray(b).astype(np.int64) for b in box)
+    centre, L = (bmax + bmin) // 2, int(np.max(bmax - bmin))
+    pad = int(L * 0.1)
+    lo = [max(int(centre[d]) - L // 2 - pad + shift, 0) for d in range(3)]
+    hi = [min(int(centre[d]) + L // 2 + pad + shift, int(shape[d])) for d in range(3)]
+    side = L + 2 * pad
+    off = [int((side - (hi[d] - lo[d])) / 2) for d in range(3)]
+    return lo, hi, off, side
+
+
 def resize(vol, output_size, order=1, anti_aliasing=None):
     """skimage.transform.resize(vol, output_size, order=order, anti_aliasing=anti_aliasing) with its other defaults, for a float volume
     (see oracle/data_cpu.py:skimage_resize for the restated algorithm)"""

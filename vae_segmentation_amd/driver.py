@@ -359,6 +359,55 @@ def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="
     return mw, mf
 
 
+@torch.no_grad()
+def validate_fine_whole(model, cases, nc, patch, overlap=0.5, batch=1, blend="gaussian", keep_largest=0, min_component=0, interp="linear", log=None,
+                        save_dir=None, names=None):
+    """--val_fine_whole: the label-free FINE prediction scored where the scan lives.  `cases` as for validate_whole_volume.  Per case
+    evaluation.coarse_to_fine_predict returns the fine pass pasted back onto the scan grid (ops.uncrop); dice_fine_whole is the hard Dice per foreground
+    class of that label — after ops.keep_largest when keep_largest > 0 — against the whole label, so it compares with dice_whole and with scores
+    published on the scan grid.  A case whose coarse prediction is empty scores its all-background label.  The mean is printed, the per-case values
+    go to the dict `log`; with save_dir the scored label of case i is written to <save_dir>/<names[i] without its extension>.npy (uint8, scan shape).
+    -> mean dice_fine_whole"""
+    from .evaluation import coarse_to_fine_predict
+    seg = model.Seg if hasattr(model, "Seg") else model
+    lo = min(1, nc - 1)
+    fine, found = {}, {}
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+    for i, (img, lab) in enumerate(cases):
+        res = coarse_to_fine_predict(seg, img, patch, overlap=overlap, blend=blend, batch=batch, keep_largest=max(keep_largest, 1), min_size=min_component,
+                                     interp=interp)
+        label = res["label"]
+        hard = ops.onehot(label.float()[None, None], nc)
+        if keep_largest > 0:
+            hard = ops.keep_largest(hard, k=keep_largest, min_size=min_component, connectivity=26, lo_channel=lo, to_background=True)
+            label = hard[0].argmax(0).to(torch.uint8)
+        fine[i] = _hard_dice(hard[0], ops.onehot(lab[None, None], nc)[0], lo, nc)
+        found[i] = bool(res["found"])
+        if save_dir is not None:
+            stem = os.path.splitext(os.path.basename(names[i]))[0] if names is not None else "case%d" % i
+            np.save(os.path.join(save_dir, stem + ".npy"), label.cpu().numpy())
+    f = {i: float(v.item()) for i, v in fine.items()}                     # host copies after the last case
+    mean = float(np.mean(list(f.values()))) if f else 0.0
+    print("validation of the fine pass on whole volumes (%s paste): dice_fine_whole %f over %d cases, %d without a coarse box"
+          % (interp, mean, len(f), sum(not v for v in found.values())))
+    if log is not None:
+        for i in f:
+            log[i] = {"dice_fine_whole": f[i]}
+    return mean
+
+
+def check_fine_whole_flags(a, script="main_source.py"):
+    """--val_fine_whole rides on the whole-volume pass; --save_whole_pred saves what --val_fine_whole makes"""
+    def need(cond, what):
+        if not cond:
+            raise SystemExit("%s: inconsistent flags — %s" % (script, what))
+    if getattr(a, "val_fine_whole", False):
+        need(getattr(a, "val_whole_volume", False), "--val_fine_whole scores the fine pass of the whole-volume chain: it needs --val_whole_volume")
+    if getattr(a, "save_whole_pred", None):
+        need(getattr(a, "val_fine_whole", False), "--save_whole_pred writes the labels that --val_fine_whole pastes: it needs --val_fine_whole")
+
+
 def check_whole_volume_flags(a, script="main_source.py"):
     """--val_whole_volume reads whole cases from disk and needs a segmentation network"""
     if not getattr(a, "val_whole_volume", False):
@@ -376,6 +425,7 @@ def check_whole_volume_flags(a, script="main_source.py"):
 # the loop
 # ----------------------------------------------------------------------------------------------------
 def run(args, side="source"):
+    check_fine_whole_flags(args, "main_%s.py" % side)
     check_whole_volume_flags(args, "main_%s.py" % side)
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if not torch.cuda.is_available():
@@ -712,6 +762,13 @@ def run(args, side="source"):
                                       keep_largest=getattr(args, "val_keep_largest", 0), min_component=getattr(args, "val_min_component", 0), log=whole_log)
                 with open(os.path.join("tensorboard", args.prefix, "whole_%d.json" % epoch), "w") as f:
                     json.dump(whole_log, f)
+                if getattr(args, "val_fine_whole", False):
+                    fine_log = {}
+                    validate_fine_whole(model, val_loader.whole_cases(), nc, args.size, overlap=args.sw_overlap, batch=args.sw_batch, blend=args.sw_blend,
+                                        keep_largest=getattr(args, "val_keep_largest", 0), min_component=getattr(args, "val_min_component", 0),
+                                        interp=args.fine_interp, log=fine_log, save_dir=getattr(args, "save_whole_pred", None), names=val_loader.names)
+                    with open(os.path.join("tensorboard", args.prefix, "fine_%d.json" % epoch), "w") as f:
+                        json.dump(fine_log, f)
             print("epoch %d validation result: %f, best result %f." % (epoch + 1, mean, best))
             if not args.test_only and (epoch + 1) % max(1, args.save_epoch // args.eval_epoch) == 0:
                 save_checkpoint(args.prefix, (epoch + 1) * args.eval_epoch, model, optimizer, mean > best)
@@ -775,6 +832,11 @@ def add_native_flags(parser):
     g.add_argument("--val_whole_volume", action="store_true", help="validation (with --real_data): additionally predict every WHOLE validation case by sliding window "
                    "with the segmentation network (windows of --size) and report dice_whole — hard Dice against the whole label — and dice_label_free — the fine "
                    "pass on a crop chosen by the prediction's box instead of the label's; per-case values go to tensorboard/<prefix>/whole_<epoch>.json")
+    g.add_argument("--val_fine_whole", action="store_true", help="with --val_whole_volume: also paste the label-free fine prediction back onto the scan grid "
+                   "(evaluation.coarse_to_fine_predict, on the device) and report dice_fine_whole — hard Dice against the whole label, comparable with dice_whole; "
+                   "per-case values go to tensorboard/<prefix>/fine_<epoch>.json")
+    g.add_argument("--fine_interp", default="linear", choices=["linear", "nearest"], help="--val_fine_whole: how the fine probabilities are resampled onto the scan")
+    g.add_argument("--save_whole_pred", default=None, metavar="DIR", help="--val_fine_whole: write every case's pasted label to DIR/<case>.npy (uint8, the scan's shape)")
     g.add_argument("--sw_overlap", type=float, default=0.5, help="--val_whole_volume: overlap of neighbouring windows as a fraction of the window, in [0, 1)")
     g.add_argument("--sw_batch", type=int, default=1, help="--val_whole_volume: windows per forward pass")
     g.add_argument("--sw_blend", default="gaussian", choices=["gaussian", "constant"], help="--val_whole_volume: importance map of a window")

@@ -258,3 +258,48 @@ def localise(prob_or_label, keep_largest=1, min_size=0, lo_channel=1):
     if keep_largest > 0:
         hard = ops.keep_largest(hard, k=int(keep_largest), min_size=int(min_size), connectivity=26, lo_channel=lo)
     return hard[0, lo:].amax(0).contiguous()
+
+
+# the intensity window of the training pipeline (main_source.py:207-208: Clip(-200, 400), CenterIntensities(100, 300)) and what CropResize's zero padding
+# becomes under it: the value a window reads past the scan
+INTENSITY_CLIP = (-200.0, 400.0)
+INTENSITY_CENTRE = (100.0, 300.0)
+_FIELD = "image"
+
+
+def _window_intensities(data_dict):
+    from . import data_gpu
+    return data_gpu.CenterIntensities([_FIELD], subtrahend=INTENSITY_CENTRE[0], divisor=INTENSITY_CENTRE[1])(
+        data_gpu.Clip([_FIELD], new_min=INTENSITY_CLIP[0], new_max=INTENSITY_CLIP[1])(data_dict))
+
+
+@torch.no_grad()
+def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", batch=1, keep_largest=1, min_size=0, interp="linear", graph=False):
+    """Label-free segmentation of a raw scan `image` (D, H, W) on the device, returned in the scan's own geometry.  The composition of the public pieces:
+      coarse   Clip / CenterIntensities -> sliding_window_predict with cubic windows of side `patch` -> localise (keep_largest, min_size) -> data_gpu.bounding_box
+               (the chain's one host synchronisation)
+      fine     data_gpu.crop_geometry and data_gpu.CropResize with the PREDICTION's box -> Clip / CenterIntensities -> the network on the patch^3 crop
+      paste    ops.uncrop(interp): the fine probabilities resampled onto the scan grid, argmax; background outside the crop
+    -> {"label": (D, H, W) uint8, "coarse_label": (D, H, W) uint8 (the sliding-window argmax), "geometry": (lo, hi, off, side) or None, "found": bool}.
+    A coarse prediction without foreground — or with a single-voxel box, of which CropResize can make no crop — gives found False, geometry None and an
+    all-background label."""
+    from . import data_gpu
+    ops._require_cuda(image)
+    if image.dim() != 3:
+        raise ValueError("coarse_to_fine_predict: expected a (D, H, W) scan, got shape %s" % (tuple(image.shape),))
+    img = image.detach().float().contiguous()
+    model_fn = segmentation_model_fn(seg)
+    lo_v, hi_v = INTENSITY_CLIP
+    cval = (min(max(0.0, lo_v), hi_v) - INTENSITY_CENTRE[0]) / INTENSITY_CENTRE[1]
+    whole = _window_intensities({_FIELD: img.clone()})[_FIELD]
+    coarse = sliding_window_predict(model_fn, whole, patch, overlap=overlap, blend=blend, batch=batch, cval=cval, graph=graph)
+    mask = localise(coarse["prob"], keep_largest=keep_largest, min_size=min_size, lo_channel=min(1, coarse["prob"].shape[0] - 1))
+    box = data_gpu.bounding_box(mask)
+    geometry = data_gpu.crop_geometry(box, img.shape) if box is not None else None
+    if geometry is None or geometry[3] < 1:
+        return {"label": torch.zeros(tuple(img.shape), dtype=torch.uint8, device=img.device), "coarse_label": coarse["label"], "geometry": None, "found": False}
+    crop = data_gpu.CropResize([_FIELD], (int(patch),) * 3)({_FIELD: img, _FIELD + "_pancreas": mask, _FIELD + "_pancreas_pred": mask})
+    crop = _window_intensities(crop)
+    fine = model_fn(crop[_FIELD][None, None])
+    label = ops.uncrop(fine[0], geometry, tuple(img.shape), interp=interp)["label"]
+    return {"label": label, "coarse_label": coarse["label"], "geometry": geometry, "found": True}

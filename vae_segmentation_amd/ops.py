@@ -2605,6 +2605,39 @@ def sw_finalize(acc, wsum, label=True, onehot=False):
     return prob, lab, hot
 
 
+# a patch-space prediction pasted back into scan geometry (csrc/uncrop.hip)
+UNCROP_INTERPS = ("nearest", "linear")
+
+
+def uncrop(prob, geometry, shape, interp="linear", want_prob=False):
+    """The probabilities (K, P, P, P), 1 <= K <= 8, that a network gave on a CropResize patch, resampled onto the scan grid `shape` = (D, H, W).
+    geometry = (lo[3], hi[3], off[3], side) of data_gpu.crop_geometry: scan voxel v with lo <= v < hi has cube index u = v - lo + off and patch coordinate
+    (u + 0.5) P / side - 0.5.  interp "linear": trilinear, edge replicate; "nearest": the order-0 zoom's rounding.  Outside the cube: background.
+    -> {"label": (D, H, W) uint8 — argmax, ties to the first channel — and, with want_prob, "prob": (K, D, H, W) fp32, (1, 0, ..., 0) outside the cube}.
+    One launch writes both outputs whole; it does not synchronise."""
+    _require_cuda(prob)
+    if interp not in UNCROP_INTERPS:
+        raise ValueError("uncrop: interp is one of %s, got %r" % (UNCROP_INTERPS, interp))
+    pr = _contig(prob.detach().float())
+    if pr.data_ptr() % 16:
+        pr = pr.clone()
+    if pr.dim() != 4 or not (pr.shape[1] == pr.shape[2] == pr.shape[3]) or not 1 <= pr.shape[0] <= 8:
+        raise ValueError("uncrop: expected probabilities (K, P, P, P) with 1 <= K <= 8, got %s" % (tuple(prob.shape),))
+    lo, hi, off, side = geometry
+    lo, hi, off = ([int(v) for v in t] for t in (lo, hi, off))
+    d, h, w = (int(s) for s in shape)
+    if not (len(lo) == len(hi) == len(off) == 3):
+        raise ValueError("uncrop: geometry is (lo[3], hi[3], off[3], side), got %r" % (geometry,))
+    label = torch.empty((d, h, w), dtype=torch.uint8, device=pr.device)
+    out = torch.empty((pr.shape[0], d, h, w), dtype=torch.float32, device=pr.device) if want_prob else None
+    check(lib.vs_uncrop(pr.data_ptr(), label.data_ptr(), _p(out), pr.shape[0], pr.shape[1], d, h, w, *lo, *hi, *off, int(side),
+                        UNCROP_INTERPS.index(interp), _stream()), "uncrop")
+    res = {"label": label}
+    if want_prob:
+        res["prob"] = out
+    return res
+
+
 def instnorm_stats(x):
     n, c = x.shape[0], x.shape[-1]
     st = _new_stats(n, c, x.device)
