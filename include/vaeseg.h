@@ -549,6 +549,20 @@ int vs_sw_gather(const float* volume, float* batch, const int* origins, const in
  * acc (k, d, h, w) and wsum (d, h, w) start as zeros; wz, wy, wx: `patch` floats each, on the device. */
 int vs_sw_accumulate(const float* prob, float* acc, float* wsum, const int* origins, const int* first, int nw, int b, int k, int d, int h, int w,
                      int patch, const float* wz, const float* wy, const float* wx, void* stream);
+/* Mirror test-time augmentation of the two calls above.  A flip is a 3-bit code: bit 0 mirrors W (x), bit 1 mirrors H (y), bit 2 mirrors D (z), a
+ * mirrored axis reading f(i) = patch - 1 - i.  A pass has nf distinct codes, 1 <= nf <= 8, handed over by value: code i in bits [3 i, 3 i + 3) of
+ * `codes`, nothing set above them (VS_EINVAL otherwise).  first[0] now counts ITEMS: item j is window j / nf under flip code j % nf, there are
+ * nw * nf of them (VS_ESHAPE when nw * nf + b passes INT_MAX), and a batch may hold several flips of one window.
+ * vs_sw_gather_tta: batch[s][c][z][y][x] = window(item first[0] + s)[c][fz(z)][fy(y)][fx(x)] — the whole padded window is mirrored, so positions
+ * past the volume (S < patch) put their cval at the low end; slots with first[0] + s >= nw * nf are cval. */
+int vs_sw_gather_tta(const float* volume, float* batch, const int* origins, const int* first, int nw, int b, int c, int d, int h, int w, int patch,
+                     float cval, int nf, int codes, void* stream);
+/* vs_sw_accumulate_tta: acc[k][v] = fmaf(w(l), prob[s][k][f(l)], acc[k][v]) and wsum[v] += w(l) with l = v - origin: the network's answer is read
+ * mirrored back, the weight is taken at the un-mirrored position.  A voxel's terms are added in ascending item index, one writer per voxel and
+ * no atomics, as vs_sw_accumulate: bit-identical for every b (it need divide neither nf nor nw * nf), from run to run and between the two
+ * builds.  vs_sw_finalize follows unchanged (wsum is nf times larger).  With nf = 1 and code 0 both calls give the bits of the plain ones. */
+int vs_sw_accumulate_tta(const float* prob, float* acc, float* wsum, const int* origins, const int* first, int nw, int b, int k, int d, int h, int w,
+                         int patch, const float* wz, const float* wy, const float* wx, int nf, int codes, void* stream);
 /* prob = acc / wsum (prob may be acc itself); label (may be NULL): the channel argmax as bytes (k <= 255; ties: the first maximal channel, a
  * NaN channel wins, as vs_hard_onehot); onehot (may be NULL): the label's planar fp32 one-hot (k, d, h, w). */
 int vs_sw_finalize(const float* acc, const float* wsum, float* prob, unsigned char* label, float* onehot, int k, int d, int h, int w, void* stream);

@@ -1,4 +1,5 @@
-// Sliding-window prediction of a whole volume (include/vaeseg.h: vs_sw_plan, vs_sw_gather, vs_sw_accumulate, vs_sw_finalize).
+// Sliding-window prediction of a whole volume (include/vaeseg.h: vs_sw_plan, vs_sw_gather, vs_sw_accumulate, vs_sw_finalize, and the mirror
+// test-time augmentation of the middle two, vs_sw_gather_tta, vs_sw_accumulate_tta).
 //
 // The reference has no counterpart (utils/utils.py:predict_vol is a 2D slice loop); this is the standard scheme for fully convolutional 3D
 // networks: tile the volume (C, D, H, W) with overlapping cubic patches of side P, run the network on batches of B windows, blend the window
@@ -19,6 +20,13 @@
 //   finalize    prob = acc / wsum (IEEE fp32 division), optionally the uint8 argmax (ties: the first maximal channel; a NaN channel wins, as
 //               vs_hard_onehot) and its planar one-hot, four voxels of the flat volume per thread.
 //
+//   tta         mirror test-time augmentation: a flip is a 3-bit code (bit 0 mirrors x, bit 1 y, bit 2 z), a pass has nf distinct codes, and the
+//               device word `first` counts ITEMS: item j is window j / nf under flip codes[j % nf].  The codes travel by value, three bits each in
+//               one word.  gather writes the window already mirrored (the whole padded cube: cval lands at the low end), accumulate reads the
+//               network's answer mirrored back and takes the weight at the un-mirrored position.  Both are the kernels above instantiated with
+//               FLIP = true; FLIP = false compiles the item arithmetic and every mirror away.  Slots of one batch may now share an origin: the
+//               first of them covers every voxel of the later ones, so it stays the only writer and adds them in ascending item order.
+//
 // Every term is fmaf(w, p, sum) with w = (wz[lz] * wy[ly]) * wx[lx] rounded to fp32 after each product; wsum takes fmaf(w, 1, sum) = sum + w.
 // All four are bandwidth-bound: no LDS, offsets are 64-bit wherever K D H W or B C P^3 can pass 2^31.
 #include <limits.h>
@@ -31,6 +39,12 @@ namespace {
 struct sw_dims {
     int c, d, h, w, p;
     int nw, b;
+};
+
+// the flips of a TTA pass, by value: nf codes of three bits each, code i in bits [3 i, 3 i + 3) of `codes`
+struct sw_flips {
+    int nf;
+    unsigned codes;
 };
 
 constexpr long long SW_GRID_CAP = 1 << 20;
@@ -55,9 +69,23 @@ __device__ __forceinline__ bool sw_window(const int* __restrict__ origins, int w
     return oz >= 0 && oz <= mz && oy >= 0 && oy <= my && ox >= 0 && ox <= mx;
 }
 
+// item -> (window, flip code); false for an item before the first.  Without FLIP an item is a window and the code is 0.
+template <bool FLIP>
+__device__ __forceinline__ bool sw_item(int item, const sw_flips& f, int& win, int& code) {
+    win = item;
+    code = 0;
+    if (FLIP) {
+        if (item < 0) return false;
+        win = item / f.nf;
+        code = (int)((f.codes >> (3 * (item - win * f.nf))) & 7u);
+    }
+    return true;
+}
+
 // ---- gather ---------------------------------------------------------------------------------------------------------------------------------
+template <bool FLIP>
 __global__ __launch_bounds__(256) void sw_gather_kernel(const float* __restrict__ vol, float* __restrict__ batch, const int* __restrict__ origins,
-                                                        const int* __restrict__ firstp, sw_dims g, float cval, int nq, long long total) {
+                                                        const int* __restrict__ firstp, sw_dims g, float cval, int nq, long long total, sw_flips f) {
     const int first = firstp[0];
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int q = (int)(i % nq);
@@ -69,18 +97,27 @@ __global__ __launch_bounds__(256) void sw_gather_kernel(const float* __restrict_
         const int c = (int)(r % g.c), b = (int)(r / g.c);
         const int lx = 4 * q, n = g.p - lx < 4 ? g.p - lx : 4;
         float v[4] = {cval, cval, cval, cval};
-        int oz, oy, ox;
-        if (sw_window(origins, first + b, g, oz, oy, ox)) {
-            const int z = oz + lz, y = oy + ly, x = ox + lx;
+        int oz, oy, ox, win, code;
+        if (sw_item<FLIP>(first + b, f, win, code) && sw_window(origins, win, g, oz, oy, ox)) {
+            const bool mx = FLIP && (code & 1);                  // a mirrored x: the four outputs are the source quad [P - 4 - lx, P - lx) in reverse
+            const int z = oz + (FLIP && (code & 4) ? g.p - 1 - lz : lz), y = oy + (FLIP && (code & 2) ? g.p - 1 - ly : ly);
+            const int x = ox + (mx ? g.p - 4 - lx : lx);         // n < 4 with mx: x may lie left of the window, the guarded loads skip those
             if (z < g.d && y < g.h) {
-                const float* sp = vol + (((size_t)c * g.d + z) * g.h + y) * g.w + x;
+                const float* sp = vol + (((size_t)c * g.d + z) * g.h + y) * g.w;
+                sp += x;
                 if (n == 4 && x + 4 <= g.w && sw_aligned16(sp)) {
                     const float4 t = *reinterpret_cast<const float4*>(sp);
-                    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+                    if (mx) {
+                        v[0] = t.w; v[1] = t.z; v[2] = t.y; v[3] = t.x;
+                    } else {
+                        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+                    }
                 } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (e < n && x + e < g.w) v[e] = sp[e];
+                    for (int e = 0; e < 4; ++e) {
+                        const int se = mx ? 3 - e : e;           // the source element of output e
+                        if (e < n && x + se < g.w) v[e] = sp[se];
+                    }
                 }
             }
         }
@@ -96,10 +133,11 @@ __global__ __launch_bounds__(256) void sw_gather_kernel(const float* __restrict_
 }
 
 // ---- accumulate -----------------------------------------------------------------------------------------------------------------------------
+template <bool FLIP>
 __global__ __launch_bounds__(256) void sw_accumulate_kernel(const float* __restrict__ prob, float* __restrict__ acc, float* __restrict__ wsum,
                                                             const int* __restrict__ origins, const int* __restrict__ firstp, sw_dims g, int nk,
                                                             const float* __restrict__ wz, const float* __restrict__ wy, const float* __restrict__ wx,
-                                                            int nq, long long total) {
+                                                            int nq, long long total, sw_flips f) {
     const int first = firstp[0];
     const size_t V = (size_t)g.d * g.h * g.w, PV = (size_t)g.p * g.p * g.p;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -108,8 +146,8 @@ __global__ __launch_bounds__(256) void sw_accumulate_kernel(const float* __restr
         const int ly = (int)(r % g.p);
         r /= g.p;
         const int lz = (int)(r % g.p), b = (int)(r / g.p);
-        int oz, oy, ox;
-        if (!sw_window(origins, first + b, g, oz, oy, ox)) continue;
+        int oz, oy, ox, win, code;
+        if (!sw_item<FLIP>(first + b, f, win, code) || !sw_window(origins, win, g, oz, oy, ox)) continue;
         const int z = oz + lz, y = oy + ly;
         if (z >= g.d || y >= g.h) continue;
         const int x0 = (ox & ~3) + 4 * q;                       // a quad aligned in the volume's row
@@ -118,8 +156,8 @@ __global__ __launch_bounds__(256) void sw_accumulate_kernel(const float* __restr
         for (int e = 0; e < 4; ++e)
             if (x0 + e >= ox && x0 + e < ox + g.p && x0 + e < g.w) mine |= 1u << e;
         for (int b2 = 0; b2 < b && mine; ++b2) {                 // ... that no earlier slot of the batch covers: this thread is their only writer
-            int pz, py, px;
-            if (!sw_window(origins, first + b2, g, pz, py, px)) continue;
+            int pz, py, px, w2, c2;
+            if (!sw_item<FLIP>(first + b2, f, w2, c2) || !sw_window(origins, w2, g, pz, py, px)) continue;
             if (z < pz || z >= pz + g.p || y < py || y >= py + g.p) continue;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -141,19 +179,21 @@ __global__ __launch_bounds__(256) void sw_accumulate_kernel(const float* __restr
                     if (mine & (1u << e)) s[e] = plane[e];
             }
             for (int b2 = b; b2 < g.b; ++b2) {
-                int pz = oz, py = oy, px = ox;
+                int pz = oz, py = oy, px = ox, c2 = code;
                 if (b2 != b) {
-                    if (!sw_window(origins, first + b2, g, pz, py, px)) continue;
+                    int w2;
+                    if (!sw_item<FLIP>(first + b2, f, w2, c2) || !sw_window(origins, w2, g, pz, py, px)) continue;
                     if (z < pz || z >= pz + g.p || y < py || y >= py + g.p) continue;
                 }
-                const float wzy = wz[z - pz] * wy[y - py];
-                const float* pp = prob + ((((size_t)b2 * nk + (k < nk ? k : 0)) * g.p + (z - pz)) * g.p + (y - py)) * g.p;
+                const float wzy = wz[z - pz] * wy[y - py];               // the weight belongs to the voxel's own position, the probability to its mirror image
+                const int sz = FLIP && (c2 & 4) ? g.p - 1 - (z - pz) : z - pz, sy = FLIP && (c2 & 2) ? g.p - 1 - (y - py) : y - py;
+                const float* pp = prob + ((((size_t)b2 * nk + (k < nk ? k : 0)) * g.p + sz) * g.p + sy) * g.p;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int lx = x0 + e - px;
                     if ((mine & (1u << e)) && lx >= 0 && lx < g.p) {
                         const float w = wzy * wx[lx];
-                        s[e] = fmaf(w, k < nk ? pp[lx] : 1.f, s[e]);
+                        s[e] = fmaf(w, k < nk ? pp[FLIP && (c2 & 1) ? g.p - 1 - lx : lx] : 1.f, s[e]);
                     }
                 }
             }
@@ -249,6 +289,19 @@ int sw_check(const sw_dims& g) {
     return VS_OK;
 }
 
+// 1 <= nf <= 8 distinct codes, nothing set above them, and first[0] + b stays an int for every item of the pass
+int sw_flips_check(const sw_dims& g, const sw_flips& f) {
+    if (f.nf < 1 || f.nf > 8 || (f.nf < 8 && (f.codes >> (3 * f.nf)) != 0)) return VS_EINVAL;
+    unsigned seen = 0;
+    for (int i = 0; i < f.nf; ++i) {
+        const unsigned bit = 1u << ((f.codes >> (3 * i)) & 7u);
+        if (seen & bit) return VS_EINVAL;
+        seen |= bit;
+    }
+    if ((long long)g.nw * f.nf + g.b > INT_MAX) return VS_ESHAPE;
+    return VS_OK;
+}
+
 }  // namespace
 
 extern "C" int vs_sw_plan(int d, int h, int w, int patch, double overlap, int* origins, int capacity) {
@@ -282,7 +335,24 @@ extern "C" int vs_sw_gather(const float* volume, float* batch, const int* origin
     if (sw_misaligned(volume) || sw_misaligned(batch)) return VS_EALIGN;
     const int nq = (patch + 3) / 4;
     const long long total = (long long)b * c * patch * patch * nq;
-    hipLaunchKernelGGL(sw_gather_kernel, dim3(sw_grid(total)), dim3(256), 0, (hipStream_t)stream, volume, batch, origins, first, g, cval, nq, total);
+    hipLaunchKernelGGL(sw_gather_kernel<false>, dim3(sw_grid(total)), dim3(256), 0, (hipStream_t)stream, volume, batch, origins, first, g, cval, nq, total,
+                       sw_flips{1, 0u});
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
+extern "C" int vs_sw_gather_tta(const float* volume, float* batch, const int* origins, const int* first, int nw, int b, int c, int d, int h, int w, int patch,
+                                float cval, int nf, int codes, void* stream) {
+    const sw_dims g = {c, d, h, w, patch, nw, b};
+    const sw_flips f = {nf, (unsigned)codes};
+    int rc = sw_check(g);
+    if (rc == VS_OK) rc = sw_flips_check(g, f);
+    if (rc != VS_OK) return rc;
+    if (!volume || !batch || !origins || !first || volume == batch) return VS_EINVAL;
+    if (sw_misaligned(volume) || sw_misaligned(batch)) return VS_EALIGN;
+    const int nq = (patch + 3) / 4;
+    const long long total = (long long)b * c * patch * patch * nq;
+    hipLaunchKernelGGL(sw_gather_kernel<true>, dim3(sw_grid(total)), dim3(256), 0, (hipStream_t)stream, volume, batch, origins, first, g, cval, nq, total, f);
     VS_CHECK_LAUNCH();
     return VS_OK;
 }
@@ -297,8 +367,26 @@ extern "C" int vs_sw_accumulate(const float* prob, float* acc, float* wsum, cons
     if (sw_misaligned(prob) || sw_misaligned(acc) || sw_misaligned(wsum)) return VS_EALIGN;
     const int nq = (patch + 3) / 4 + 1;                          // the volume-aligned quads that [ox, ox + P) can touch
     const long long total = (long long)b * patch * patch * nq;
-    hipLaunchKernelGGL(sw_accumulate_kernel, dim3(sw_grid(total)), dim3(256), 0, (hipStream_t)stream, prob, acc, wsum, origins, first, g, k, wz, wy, wx, nq,
-                       total);
+    hipLaunchKernelGGL(sw_accumulate_kernel<false>, dim3(sw_grid(total)), dim3(256), 0, (hipStream_t)stream, prob, acc, wsum, origins, first, g, k, wz, wy, wx,
+                       nq, total, sw_flips{1, 0u});
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
+extern "C" int vs_sw_accumulate_tta(const float* prob, float* acc, float* wsum, const int* origins, const int* first, int nw, int b, int k, int d, int h,
+                                    int w, int patch, const float* wz, const float* wy, const float* wx, int nf, int codes, void* stream) {
+    const sw_dims g = {1, d, h, w, patch, nw, b};
+    const sw_flips f = {nf, (unsigned)codes};
+    int rc = sw_check(g);
+    if (rc == VS_OK) rc = sw_flips_check(g, f);
+    if (rc != VS_OK) return rc;
+    if (k <= 0) return VS_EINVAL;
+    if (!prob || !acc || !wsum || !origins || !first || !wz || !wy || !wx || prob == acc || prob == wsum || acc == wsum) return VS_EINVAL;
+    if (sw_misaligned(prob) || sw_misaligned(acc) || sw_misaligned(wsum)) return VS_EALIGN;
+    const int nq = (patch + 3) / 4 + 1;
+    const long long total = (long long)b * patch * patch * nq;
+    hipLaunchKernelGGL(sw_accumulate_kernel<true>, dim3(sw_grid(total)), dim3(256), 0, (hipStream_t)stream, prob, acc, wsum, origins, first, g, k, wz, wy, wx,
+                       nq, total, f);
     VS_CHECK_LAUNCH();
     return VS_OK;
 }

@@ -314,7 +314,7 @@ WHOLE_VOLUME_CVAL = (0.0 - 100.0) / 300.0          # what CropResize's zero padd
 
 
 @torch.no_grad()
-def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="gaussian", keep_largest=0, min_component=0, log=None):
+def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="gaussian", keep_largest=0, min_component=0, log=None, tta=None):
     """--val_whole_volume: label-free coarse-to-fine inference, scored.  `cases` yields (raw image, relabelled label) (D, H, W) device tensors
     (DeviceCaseLoader.whole_cases).  Per case:
       dice_whole       the clipped and centred WHOLE volume is predicted by sliding window with the segmentation network (evaluation.sliding_window_predict,
@@ -322,9 +322,12 @@ def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="
                        against the whole label
       dice_label_free  the case is cropped by CropResize with the box of the PREDICTION (evaluation.localise -> <field>_pancreas_pred) instead of the
                        label's, the fine forward runs on the crop, hard Dice in crop space.  A coarse prediction without foreground gives no box: 0.
-    Both means are printed; the per-case values go to the dict `log`.  -> (mean dice_whole, mean dice_label_free)"""
+    Both means are printed; the per-case values go to the dict `log`.  -> (mean dice_whole, mean dice_label_free)
+    tta (--val_tta, evaluation.tta_flips): mirror test-time augmentation of the sliding-window pass; the crop-space fine forward stays a single one.
+    The codes are then recorded as log["tta"]."""
     from . import data_gpu
-    from .evaluation import localise, segmentation_model_fn, sliding_window_predict
+    from .evaluation import localise, segmentation_model_fn, sliding_window_predict, tta_flips
+    tta = tta_flips(tta)
     seg = model.Seg if hasattr(model, "Seg") else model
     model_fn = segmentation_model_fn(seg)
     lo = min(1, nc - 1)
@@ -332,7 +335,7 @@ def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="
     for i, (img, lab) in enumerate(cases):
         d = {IMG_KEY: img.clone()}
         d = data_gpu.CenterIntensities([IMG_KEY], subtrahend=100, divisor=300)(data_gpu.Clip([IMG_KEY], new_min=-200, new_max=400)(d))
-        res = sliding_window_predict(model_fn, d[IMG_KEY], patch, overlap=overlap, blend=blend, batch=batch, cval=WHOLE_VOLUME_CVAL)
+        res = sliding_window_predict(model_fn, d[IMG_KEY], patch, overlap=overlap, blend=blend, batch=batch, cval=WHOLE_VOLUME_CVAL, tta=tta)
         if res["prob"].shape[0] != nc:
             raise ValueError("whole-volume validation: the network predicts %d classes, the labels have %d" % (res["prob"].shape[0], nc))
         hard = ops.hard_onehot(res["prob"][None])
@@ -351,24 +354,28 @@ def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="
     w = {i: float(v.item()) for i, v in whole.items()}                    # host copies after the last case
     f = {i: float(v.item()) for i, v in free.items()}
     mw, mf = (float(np.mean(list(x.values()))) if x else 0.0 for x in (w, f))
-    print("validation on whole volumes (sliding window %d^3, overlap %g, %s blend): dice_whole %f, dice_label_free %f over %d cases"
-          % (patch, overlap, blend, mw, mf, len(w)))
+    print("validation on whole volumes (sliding window %d^3, overlap %g, %s blend%s): dice_whole %f, dice_label_free %f over %d cases"
+          % (patch, overlap, blend, ", mirror TTA %s" % (tta,) if tta else "", mw, mf, len(w)))
     if log is not None:
         for i in w:
             log[i] = {"dice_whole": w[i], "dice_label_free": f[i]}
+        if tta:
+            log["tta"] = list(tta)
     return mw, mf
 
 
 @torch.no_grad()
 def validate_fine_whole(model, cases, nc, patch, overlap=0.5, batch=1, blend="gaussian", keep_largest=0, min_component=0, interp="linear", log=None,
-                        save_dir=None, names=None):
+                        save_dir=None, names=None, tta=None):
     """--val_fine_whole: the label-free FINE prediction scored where the scan lives.  `cases` as for validate_whole_volume.  Per case
     evaluation.coarse_to_fine_predict returns the fine pass pasted back onto the scan grid (ops.uncrop); dice_fine_whole is the hard Dice per foreground
     class of that label — after ops.keep_largest when keep_largest > 0 — against the whole label, so it compares with dice_whole and with scores
     published on the scan grid.  A case whose coarse prediction is empty scores its all-background label.  The mean is printed, the per-case values
     go to the dict `log`; with save_dir the scored label of case i is written to <save_dir>/<names[i] without its extension>.npy (uint8, scan shape).
+    tta (--val_tta, evaluation.tta_flips): mirror test-time augmentation of the coarse and the fine pass; the codes are then recorded as log["tta"].
     -> mean dice_fine_whole"""
-    from .evaluation import coarse_to_fine_predict
+    from .evaluation import coarse_to_fine_predict, tta_flips
+    tta = tta_flips(tta)
     seg = model.Seg if hasattr(model, "Seg") else model
     lo = min(1, nc - 1)
     fine, found = {}, {}
@@ -376,7 +383,7 @@ def validate_fine_whole(model, cases, nc, patch, overlap=0.5, batch=1, blend="ga
         os.makedirs(save_dir, exist_ok=True)
     for i, (img, lab) in enumerate(cases):
         res = coarse_to_fine_predict(seg, img, patch, overlap=overlap, blend=blend, batch=batch, keep_largest=max(keep_largest, 1), min_size=min_component,
-                                     interp=interp)
+                                     interp=interp, tta=tta)
         label = res["label"]
         hard = ops.onehot(label.float()[None, None], nc)
         if keep_largest > 0:
@@ -389,11 +396,13 @@ def validate_fine_whole(model, cases, nc, patch, overlap=0.5, batch=1, blend="ga
             np.save(os.path.join(save_dir, stem + ".npy"), label.cpu().numpy())
     f = {i: float(v.item()) for i, v in fine.items()}                     # host copies after the last case
     mean = float(np.mean(list(f.values()))) if f else 0.0
-    print("validation of the fine pass on whole volumes (%s paste): dice_fine_whole %f over %d cases, %d without a coarse box"
-          % (interp, mean, len(f), sum(not v for v in found.values())))
+    print("validation of the fine pass on whole volumes (%s paste%s): dice_fine_whole %f over %d cases, %d without a coarse box"
+          % (interp, ", mirror TTA %s" % (tta,) if tta else "", mean, len(f), sum(not v for v in found.values())))
     if log is not None:
         for i in f:
             log[i] = {"dice_fine_whole": f[i]}
+        if tta:
+            log["tta"] = list(tta)
     return mean
 
 
@@ -409,12 +418,19 @@ def check_fine_whole_flags(a, script="main_source.py"):
 
 
 def check_whole_volume_flags(a, script="main_source.py"):
-    """--val_whole_volume reads whole cases from disk and needs a segmentation network"""
-    if not getattr(a, "val_whole_volume", False):
-        return
+    """--val_whole_volume reads whole cases from disk and needs a segmentation network; --val_tta augments its sliding-window passes"""
     def need(cond, what):
         if not cond:
             raise SystemExit("%s: inconsistent flags — %s" % (script, what))
+    if getattr(a, "val_tta", None):
+        need(getattr(a, "val_whole_volume", False), "--val_tta mirrors the windows of the whole-volume chain: it needs --val_whole_volume")
+        from .evaluation import tta_flips
+        try:
+            tta_flips(a.val_tta)
+        except ValueError as e:
+            need(False, "--val_tta: %s" % e)
+    if not getattr(a, "val_whole_volume", False):
+        return
     need(getattr(a, "real_data", False), "--val_whole_volume predicts whole merge.npy cases: it needs --real_data")
     need(a.method not in ("vae_train", "discriminator_train", "embed_train", "refine_vae"), "--val_whole_volume needs a segmentation network, --method %s has none" % a.method)
     need(0.0 <= a.sw_overlap < 1.0, "--sw_overlap must be in [0, 1)")
@@ -759,14 +775,16 @@ def run(args, side="source"):
             if getattr(args, "val_whole_volume", False):                           # after validation, which it leaves as it is
                 whole_log = {}
                 validate_whole_volume(model, val_loader.whole_cases(), nc, args.size, overlap=args.sw_overlap, batch=args.sw_batch, blend=args.sw_blend,
-                                      keep_largest=getattr(args, "val_keep_largest", 0), min_component=getattr(args, "val_min_component", 0), log=whole_log)
+                                      keep_largest=getattr(args, "val_keep_largest", 0), min_component=getattr(args, "val_min_component", 0), log=whole_log,
+                                      tta=getattr(args, "val_tta", None))
                 with open(os.path.join("tensorboard", args.prefix, "whole_%d.json" % epoch), "w") as f:
                     json.dump(whole_log, f)
                 if getattr(args, "val_fine_whole", False):
                     fine_log = {}
                     validate_fine_whole(model, val_loader.whole_cases(), nc, args.size, overlap=args.sw_overlap, batch=args.sw_batch, blend=args.sw_blend,
                                         keep_largest=getattr(args, "val_keep_largest", 0), min_component=getattr(args, "val_min_component", 0),
-                                        interp=args.fine_interp, log=fine_log, save_dir=getattr(args, "save_whole_pred", None), names=val_loader.names)
+                                        interp=args.fine_interp, log=fine_log, save_dir=getattr(args, "save_whole_pred", None), names=val_loader.names,
+                                        tta=getattr(args, "val_tta", None))
                     with open(os.path.join("tensorboard", args.prefix, "fine_%d.json" % epoch), "w") as f:
                         json.dump(fine_log, f)
             print("epoch %d validation result: %f, best result %f." % (epoch + 1, mean, best))
@@ -837,6 +855,9 @@ def add_native_flags(parser):
                    "per-case values go to tensorboard/<prefix>/fine_<epoch>.json")
     g.add_argument("--fine_interp", default="linear", choices=["linear", "nearest"], help="--val_fine_whole: how the fine probabilities are resampled onto the scan")
     g.add_argument("--save_whole_pred", default=None, metavar="DIR", help="--val_fine_whole: write every case's pasted label to DIR/<case>.npy (uint8, the scan's shape)")
+    g.add_argument("--val_tta", default=None, metavar="AXES", help="--val_whole_volume: mirror test-time augmentation of the sliding-window passes — AXES is a "
+                   "string over \"dhw\"; every window is predicted under each subset of those flips and the un-flipped probabilities are averaged, in the "
+                   "same pass (2^len(AXES) forwards per window); whole_<epoch>.json and fine_<epoch>.json record the flip codes as \"tta\"")
     g.add_argument("--sw_overlap", type=float, default=0.5, help="--val_whole_volume: overlap of neighbouring windows as a fraction of the window, in [0, 1)")
     g.add_argument("--sw_batch", type=int, default=1, help="--val_whole_volume: windows per forward pass")
     g.add_argument("--sw_blend", default="gaussian", choices=["gaussian", "constant"], help="--val_whole_volume: importance map of a window")

@@ -136,6 +136,24 @@ def hd95(A, B, spacing=None, connectivity=6):
 # whole-volume inference: sliding-window prediction on the device (csrc/window.hip).  The reference has no counterpart
 # (utils/utils.py:predict_vol is a 2D slice loop); tests/sliding_util.py restates the algorithm in numpy.
 # ----------------------------------------------------------------------------------------------------
+TTA_AXES = {"w": 1, "h": 2, "d": 4}
+
+
+def tta_flips(axes):
+    """The flip codes of a mirror test-time augmentation (bit 0 mirrors W, bit 1 H, bit 2 D).  axes: a string over "dhw" -> every subset of the named
+    axes, as a tuple of codes in ascending order ("w" -> (0, 1), "d" -> (0, 4), "dhw" -> (0, 1, ..., 7)).  None, "" or () -> None: no augmentation.
+    A sequence of codes passes through as a tuple, validated as ops.sw_flips does.  ValueError for anything else."""
+    if axes is None or (isinstance(axes, (str, tuple, list)) and len(axes) == 0):
+        return None
+    if isinstance(axes, str):
+        if any(a not in TTA_AXES for a in axes) or len(set(axes)) != len(axes):
+            raise ValueError("tta: the axes are distinct letters of \"dhw\", got %r" % (axes,))
+        mask = sum(TTA_AXES[a] for a in axes)
+        return tuple(c for c in range(8) if c & ~mask == 0)
+    ops.sw_flips(axes)
+    return tuple(int(c) for c in axes)
+
+
 class SlidingWindow:
     """Sliding-window predictor for volumes of one shape: the plan, the importance map, the window counter and every buffer are made once, so the
     object can be called for one volume after another.  model_fn maps a (B, C, P, P, P) fp32 batch to planar probabilities (B, K, P, P, P).
@@ -143,9 +161,14 @@ class SlidingWindow:
     One batch is gather -> model_fn -> accumulate -> bump the window counter.  The counter is a DEVICE word (as the captured optimiser's
     hyperparameters are), so with graph=True that batch is captured once into a HIP graph and replayed ceil(nw / B) times per volume; eagerly the
     same launches are issued in a loop.  Either way the host never waits for the device between windows.  The sums are formed without atomics in
-    ascending window order: the result does not depend on B, and graph replay equals eager launches bit for bit."""
+    ascending window order: the result does not depend on B, and graph replay equals eager launches bit for bit.
 
-    def __init__(self, model_fn, shape, patch, overlap=0.5, blend="gaussian", batch=1, cval=0.0, graph=False, device="cuda"):
+    tta (tta_flips: a string over "dhw" or a tuple of flip codes) turns on mirror test-time augmentation inside the kernels: the counter walks over
+    (window, flip) items, nw * nf of them, gather writes each window mirrored and accumulate reads the answer mirrored back, so the normalised
+    result is the blend of the un-flipped answers averaged over the nf flips — in one pass, one set of accumulators and one capture, with the same
+    guarantees.  It costs nf forwards per window.  tta=None issues exactly the launches it always did."""
+
+    def __init__(self, model_fn, shape, patch, overlap=0.5, blend="gaussian", batch=1, cval=0.0, graph=False, device="cuda", tta=None):
         shape = tuple(int(s) for s in shape)
         if len(shape) == 3:
             shape = (1,) + shape
@@ -155,7 +178,9 @@ class SlidingWindow:
         self.device = torch.device(device)
         self.origins, self.nw = ops.sw_plan(shape[1:], self.patch, overlap, device=self.device)
         self.weights = ops.sw_weights(self.patch, blend, device=self.device)
-        self.n_batches = (self.nw + self.batch - 1) // self.batch
+        self.tta = tta_flips(tta)
+        self.n_items = self.nw * (len(self.tta) if self.tta else 1)
+        self.n_batches = (self.n_items + self.batch - 1) // self.batch
         self.volume = torch.zeros(shape, dtype=torch.float32, device=self.device)
         self.first = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.windows = torch.empty((self.batch, shape[0]) + (self.patch,) * 3, dtype=torch.float32, device=self.device)
@@ -163,7 +188,7 @@ class SlidingWindow:
         self.use_graph, self.graph = bool(graph), None
 
     def _one_batch(self):
-        ops.sw_gather(self.volume, self.origins, self.first, self.batch, cval=self.cval, out=self.windows)
+        ops.sw_gather(self.volume, self.origins, self.first, self.batch, cval=self.cval, out=self.windows, flips=self.tta)
         prob = self.model_fn(self.windows)
         if prob.dim() != 5 or prob.shape[0] != self.batch or tuple(prob.shape[2:]) != (self.patch,) * 3:
             raise ValueError("sliding window: model_fn must return (B, K, P, P, P) = (%d, K, %d, %d, %d), got %s"
@@ -173,7 +198,7 @@ class SlidingWindow:
                 raise RuntimeError("sliding window: the accumulators must exist before a capture starts")
             self.acc = torch.zeros((prob.shape[1],) + self.shape[1:], dtype=torch.float32, device=self.device)
             self.wsum = torch.zeros(self.shape[1:], dtype=torch.float32, device=self.device)
-        ops.sw_accumulate(prob, self.acc, self.wsum, self.origins, self.first, self.weights)
+        ops.sw_accumulate(prob, self.acc, self.wsum, self.origins, self.first, self.weights, flips=self.tta)
         self.first.add_(self.batch)
 
     def _reset(self):
@@ -214,20 +239,23 @@ class SlidingWindow:
                 else:
                     self._one_batch()
             prob, label, hot = ops.sw_finalize(self.acc, self.wsum, label=True, onehot=onehot)
-        out = {"prob": prob, "label": label, "wsum": self.wsum.clone()}
+        out = {"prob": prob, "label": label, "wsum": self.wsum.clone(), "tta": self.tta}
         if onehot:
             out["onehot"] = hot
         return out
 
 
-def sliding_window_predict(model_fn, volume, patch, overlap=0.5, blend="gaussian", batch=1, cval=0.0, graph=False):
+def sliding_window_predict(model_fn, volume, patch, overlap=0.5, blend="gaussian", batch=1, cval=0.0, graph=False, tta=None):
     """Whole-volume prediction of a fully convolutional 3D network: `volume` (C, D, H, W) or (D, H, W) on the device is tiled with overlapping cubic
     windows of side `patch` (ops.sw_plan), model_fn — (B, C, P, P, P) -> planar probabilities (B, K, P, P, P) — runs on `batch` windows at a time, the
     window probabilities are blended with the importance map `blend` ("gaussian" or "constant", ops.sw_weights) and normalised.  Runs under
     torch.no_grad().  -> {"prob": (K, D, H, W) fp32, "label": (D, H, W) uint8 (argmax, ties to the first channel), "wsum": (D, H, W) fp32}.
-    graph=True captures one batch into a HIP graph and replays it (SlidingWindow, which also serves further volumes of the same shape)."""
+    graph=True captures one batch into a HIP graph and replays it (SlidingWindow, which also serves further volumes of the same shape).
+    tta: mirror test-time augmentation (tta_flips): every window is predicted under each flip and the un-flipped answers are averaged, inside the same
+    pass; wsum is then nf times larger, the dict's "tta" is the tuple of codes (None without), and the pass costs nf forwards per window."""
     ops._require_cuda(volume)
-    return SlidingWindow(model_fn, tuple(volume.shape), patch, overlap=overlap, blend=blend, batch=batch, cval=cval, graph=graph, device=volume.device)(volume)
+    return SlidingWindow(model_fn, tuple(volume.shape), patch, overlap=overlap, blend=blend, batch=batch, cval=cval, graph=graph, device=volume.device,
+                         tta=tta)(volume)
 
 
 def segmentation_model_fn(seg):
@@ -274,7 +302,7 @@ def _window_intensities(data_dict):
 
 
 @torch.no_grad()
-def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", batch=1, keep_largest=1, min_size=0, interp="linear", graph=False):
+def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", batch=1, keep_largest=1, min_size=0, interp="linear", graph=False, tta=None):
     """Label-free segmentation of a raw scan `image` (D, H, W) on the device, returned in the scan's own geometry.  The composition of the public pieces:
       coarse   Clip / CenterIntensities -> sliding_window_predict with cubic windows of side `patch` -> localise (keep_largest, min_size) -> data_gpu.bounding_box
                (the chain's one host synchronisation)
@@ -282,7 +310,9 @@ def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", bat
       paste    ops.uncrop(interp): the fine probabilities resampled onto the scan grid, argmax; background outside the crop
     -> {"label": (D, H, W) uint8, "coarse_label": (D, H, W) uint8 (the sliding-window argmax), "geometry": (lo, hi, off, side) or None, "found": bool}.
     A coarse prediction without foreground — or with a single-voxel box, of which CropResize can make no crop — gives found False, geometry None and an
-    all-background label."""
+    all-background label.
+    tta (tta_flips): mirror test-time augmentation of both passes.  The coarse pass receives it; the fine pass is a sliding-window pass over the crop
+    itself — one window, constant blend — so its probabilities are the mean of the un-flipped answers, summed in the order of the codes."""
     from . import data_gpu
     ops._require_cuda(image)
     if image.dim() != 3:
@@ -292,7 +322,8 @@ def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", bat
     lo_v, hi_v = INTENSITY_CLIP
     cval = (min(max(0.0, lo_v), hi_v) - INTENSITY_CENTRE[0]) / INTENSITY_CENTRE[1]
     whole = _window_intensities({_FIELD: img.clone()})[_FIELD]
-    coarse = sliding_window_predict(model_fn, whole, patch, overlap=overlap, blend=blend, batch=batch, cval=cval, graph=graph)
+    tta = tta_flips(tta)
+    coarse = sliding_window_predict(model_fn, whole, patch, overlap=overlap, blend=blend, batch=batch, cval=cval, graph=graph, tta=tta)
     mask = localise(coarse["prob"], keep_largest=keep_largest, min_size=min_size, lo_channel=min(1, coarse["prob"].shape[0] - 1))
     box = data_gpu.bounding_box(mask)
     geometry = data_gpu.crop_geometry(box, img.shape) if box is not None else None
@@ -300,6 +331,9 @@ def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", bat
         return {"label": torch.zeros(tuple(img.shape), dtype=torch.uint8, device=img.device), "coarse_label": coarse["label"], "geometry": None, "found": False}
     crop = data_gpu.CropResize([_FIELD], (int(patch),) * 3)({_FIELD: img, _FIELD + "_pancreas": mask, _FIELD + "_pancreas_pred": mask})
     crop = _window_intensities(crop)
-    fine = model_fn(crop[_FIELD][None, None])
-    label = ops.uncrop(fine[0], geometry, tuple(img.shape), interp=interp)["label"]
+    if tta is None:
+        fine = model_fn(crop[_FIELD][None, None])[0]
+    else:
+        fine = sliding_window_predict(model_fn, crop[_FIELD], patch, overlap=0.0, blend="constant", batch=batch, tta=tta)["prob"]
+    label = ops.uncrop(fine, geometry, tuple(img.shape), interp=interp)["label"]
     return {"label": label, "coarse_label": coarse["label"], "geometry": geometry, "found": True}

@@ -2552,9 +2552,25 @@ def _sw_common(origins, first, weights, patch):
         raise ValueError("sw: weights is the contiguous fp32 (3, %d) tensor of sw_weights" % patch)
 
 
-def sw_gather(volume, origins, first, batch, patch=None, cval=0.0, out=None):
+def sw_flips(flips):
+    """The flip codes of a mirror-TTA pass (bit 0 mirrors W, bit 1 H, bit 2 D) -> (nf, the codes packed three bits each, code i in bits [3 i, 3 i + 3)):
+    how vs_sw_gather_tta and vs_sw_accumulate_tta take them.  1 to 8 distinct integers in 0..7, ValueError otherwise."""
+    try:
+        codes = [int(c) for c in flips]
+        exact = all(c == f for c, f in zip(codes, flips))
+    except (TypeError, ValueError):
+        codes, exact = [], False
+    if not exact or not 1 <= len(codes) <= 8 or any(c < 0 or c > 7 for c in codes) or len(set(codes)) != len(codes):
+        raise ValueError("sw: flips is a sequence of 1 to 8 distinct codes in 0..7 (bit 0 mirrors W, bit 1 H, bit 2 D), got %r" % (flips,))
+    return len(codes), sum(c << (3 * i) for i, c in enumerate(codes))
+
+
+def sw_gather(volume, origins, first, batch, patch=None, cval=0.0, out=None, flips=None):
     """Windows [first, first + batch) of the plan, cut from the planar fp32 volume (C, D, H, W) -> (batch, C, P, P, P).  `first`: an int32 device word.
-    Slots past the plan and positions past the volume read cval.  out: the batch tensor to fill (a fixed address for a captured launch)."""
+    Slots past the plan and positions past the volume read cval.  out: the batch tensor to fill (a fixed address for a captured launch).
+    flips (a sequence of codes, sw_flips): `first` counts items — item j is window j // nf mirrored by flips[j % nf] — and each slot is written
+    already mirrored (vs_sw_gather_tta)."""
+    packed = None if flips is None else sw_flips(flips)
     _require_cuda(volume, origins, first, out)
     if volume.dim() != 4 or volume.dtype != torch.float32 or not volume.is_contiguous() or volume.data_ptr() % 16:
         raise ValueError("sw_gather: expected a contiguous, 16-byte aligned fp32 (C, D, H, W) volume, got %s %s" % (tuple(volume.shape), volume.dtype))
@@ -2565,14 +2581,21 @@ def sw_gather(volume, origins, first, batch, patch=None, cval=0.0, out=None):
     if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (int(batch), c, p, p, p) or (patch is not None and p != int(patch)):
         raise ValueError("sw_gather: out must be a contiguous fp32 (%d, %d, P, P, P) tensor, got %s" % (int(batch), c, tuple(out.shape)))
     _sw_common(origins, first, None, p)
-    check(lib.vs_sw_gather(volume.data_ptr(), out.data_ptr(), origins.data_ptr(), first.data_ptr(), origins.shape[0], int(batch), c, d, h, w, p,
-                           float(cval), _stream()), "sw_gather")
+    if packed is None:
+        check(lib.vs_sw_gather(volume.data_ptr(), out.data_ptr(), origins.data_ptr(), first.data_ptr(), origins.shape[0], int(batch), c, d, h, w, p,
+                               float(cval), _stream()), "sw_gather")
+    else:
+        check(lib.vs_sw_gather_tta(volume.data_ptr(), out.data_ptr(), origins.data_ptr(), first.data_ptr(), origins.shape[0], int(batch), c, d, h, w, p,
+                                   float(cval), packed[0], packed[1], _stream()), "sw_gather_tta")
     return out
 
 
-def sw_accumulate(prob, acc, wsum, origins, first, weights):
+def sw_accumulate(prob, acc, wsum, origins, first, weights, flips=None):
     """acc (K, D, H, W) += w * prob (B, K, P, P, P) and wsum (D, H, W) += w for the windows [first, first + B) that lie in the plan, in place, every voxel's
-    terms in ascending window index and without atomics: bit-identical for every B.  Batches are accumulated in ascending order of `first`."""
+    terms in ascending window index and without atomics: bit-identical for every B.  Batches are accumulated in ascending order of `first`.
+    flips (as sw_gather): the slots are items, each probability is read mirrored back and weighted at the voxel's own position, terms in ascending item
+    index (vs_sw_accumulate_tta)."""
+    packed = None if flips is None else sw_flips(flips)
     _require_cuda(prob, acc, wsum, origins, first, weights)
     pr = _contig(prob.detach().float())
     if pr.data_ptr() % 16:
@@ -2586,8 +2609,13 @@ def sw_accumulate(prob, acc, wsum, origins, first, weights):
     b, k, p = pr.shape[0], pr.shape[1], pr.shape[2]
     _sw_common(origins, first, weights, p)
     d, h, w = wsum.shape
-    check(lib.vs_sw_accumulate(pr.data_ptr(), acc.data_ptr(), wsum.data_ptr(), origins.data_ptr(), first.data_ptr(), origins.shape[0], b, k, d, h, w, p,
-                               weights[0].data_ptr(), weights[1].data_ptr(), weights[2].data_ptr(), _stream()), "sw_accumulate")
+    if packed is None:
+        check(lib.vs_sw_accumulate(pr.data_ptr(), acc.data_ptr(), wsum.data_ptr(), origins.data_ptr(), first.data_ptr(), origins.shape[0], b, k, d, h, w, p,
+                                   weights[0].data_ptr(), weights[1].data_ptr(), weights[2].data_ptr(), _stream()), "sw_accumulate")
+    else:
+        check(lib.vs_sw_accumulate_tta(pr.data_ptr(), acc.data_ptr(), wsum.data_ptr(), origins.data_ptr(), first.data_ptr(), origins.shape[0], b, k, d, h, w,
+                                       p, weights[0].data_ptr(), weights[1].data_ptr(), weights[2].data_ptr(), packed[0], packed[1], _stream()),
+              "sw_accumulate_tta")
 
 
 def sw_finalize(acc, wsum, label=True, onehot=False):
