@@ -529,6 +529,31 @@ long long vs_edt_workspace_bytes(int n, int c, int d, int h, int w, int with_spa
 int vs_surface_distances(const float* pred, const float* gt, vs_surface_record* out, int n, int c, int d, int h, int w, int connectivity,
                          const double* spacing, void* workspace, void* stream);
 
+/* ---- binary morphology and hole filling of a prediction (csrc/morph.hip) ------------------------------------------------------------------
+ * scipy.ndimage's binary_dilation / binary_erosion / binary_opening / binary_closing (structure = generate_binary_structure(3, 1) for connectivity
+ * 6, (3, 3) for 26; iterations; border_value; origin 0, no mask) and binary_fill_holes(X, structure).  The reference dilates its bone mask with
+ * binary_dilation(iterations=2) (utils/utils.py:647-655, get_synthesis_mask).  mask: planar fp32 (n, c, d, h, w), contiguous, foreground where the
+ * value is >= 0.5; every (n, c) plane is its own problem; any d, h, w >= 1 with d*h*w < 2^31 (VS_ESHAPE beyond, as for an empty shape).  out: fp32
+ * 0 / 1, mask's shape, must not alias mask.
+ *   vs_morph       voxels outside the volume read as border_value (0 or 1) in BOTH halves of an opening (erode^n then dilate^n) or closing
+ *                  (dilate^n then erode^n), as scipy passes it on.  The mask is packed to one bit per voxel (64-bit words along x); connectivity 26
+ *                  with n iterations is the box of half-width n, done as three axis passes: 5 launches (8 for open / close) whatever n is.
+ *                  Connectivity 6 is the L1 ball, one launch per step: n + 2 launches (2 n + 2), n capped at d + h + w where the result is fixed.
+ *   vs_fill_holes  out = the complement of the background voxels that reach the outside of the volume through `connectivity`-neighbours
+ *                  (scipy's default structure is connectivity 6).  The complement is labelled with the union-find of csrc/cc_core.h, the roots of
+ *                  the background voxels on the six faces are marked, every voxel reads its root's mark: 4 launches.
+ * connectivity not 6 / 26, op outside VS_MORPH_*, iterations < 1, border_value not 0 / 1, a null pointer, out or workspace aliasing mask:
+ * VS_EINVAL; workspace not 16-byte aligned: VS_EALIGN; all answered on the host before any launch.  workspace: vs_*_workspace_bytes() bytes
+ * (negative: VS_E*), contents undefined on entry.  A call is a straight line of launches — no kernel waits for another workgroup, every loop is
+ * bounded by the data, nothing is allocated, synchronised or read back — and can be captured in a HIP graph.  The results are sets: both builds of
+ * the library and every run give the same bits (vs_morph has no atomics; vs_fill_holes only the order-independent atomicMin of the union-find). */
+enum { VS_MORPH_DILATE = 0, VS_MORPH_ERODE = 1, VS_MORPH_OPEN = 2, VS_MORPH_CLOSE = 3 };
+long long vs_morph_workspace_bytes(int n, int c, int d, int h, int w);
+int vs_morph(const float* mask, float* out, int n, int c, int d, int h, int w, int op, int connectivity, int iterations, int border_value,
+             void* workspace, void* stream);
+long long vs_fill_holes_workspace_bytes(int n, int c, int d, int h, int w, int connectivity);
+int vs_fill_holes(const float* mask, float* out, int n, int c, int d, int h, int w, int connectivity, void* workspace, void* stream);
+
 /* ---- sliding-window prediction of a whole volume (csrc/window.hip; no counterpart in the reference) -------------------------------
  * A volume (C, D, H, W) is tiled with overlapping cubic windows of side `patch`, a network maps batches (B, C, P, P, P) of them to planar
  * probabilities (B, K, P, P, P), and the windows are blended: prob[k][v] = sum_i w_i(v) p_i[k](v) / sum_i w_i(v) over the windows i that cover

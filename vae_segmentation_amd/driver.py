@@ -214,7 +214,8 @@ def save_checkpoint(prefix, epoch_label, model, optimizer, best):
 # validation (main_source.py:688-822): batch 1, hard Dice of the argmax prediction against the label
 # ----------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_dir=None, epoch=0, surface=False, surface_log=None):
+def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_dir=None, epoch=0, surface=False, surface_log=None, closing=0,
+             fill_holes=False):
     """main_source.py:688-822 / main_target.py:754-805: batch-1 forwards and hard Dice per case.  Forward only (no autograd graph is recorded: nothing is kept
     for a backward pass — the per-(n, c) statistics the conv epilogues accumulate are the FORWARD's own, the next layer normalises with them).
     keep_largest = k > 0: the hard prediction is cleaned up first as utils/utils.py:776-796 (predict_vol step 2) does — per foreground channel only the k largest
@@ -224,7 +225,11 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
     filtered mask, when the filter is on) are written there with np.save.
     surface (--val_surface): additionally ASSD and HD95 (evaluation.surface_metrics: medpy's convention, unit spacing, on the device) of the hard prediction —
     the filtered one when the filter is on, the unfiltered values are then reported beside them — against the label for every foreground class; their nanmean and
-    the number of undefined (empty-surface) entries are printed, the per-case values go to the dict surface_log.  The returned scores are not affected."""
+    the number of undefined (empty-surface) entries are printed, the per-case values go to the dict surface_log.  The returned scores are not affected.
+    closing (--val_closing N) / fill_holes (--val_fill_holes): evaluation.postprocess runs in the filter's place — per foreground class a binary closing of N
+    iterations (26-neighbourhood), then hole filling (6-connectivity), then the component filter if it is on; everything said of the filter above holds for it."""
+    from .evaluation import postprocess
+    post = keep_largest > 0 or closing > 0 or fill_holes
     scores, raw = {}, {}
     surf, surf_raw = {}, {}
     lo = min(1, nc - 1)
@@ -244,10 +249,10 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
             seg = model.Seg if hasattr(model, "Seg") else model
             pred = seg({IMG_KEY: batch[IMG_KEY].cuda(non_blocking=True)}, IMG_KEY, "pred")["pred"]
         filtered = None
-        if keep_largest > 0:
+        if post:
             raw[i] = avg_dsc({"p": pred, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc)
-            filtered = ops.keep_largest(ops.hard_onehot(pred), k=keep_largest, min_size=min_component, connectivity=26,
-                                        lo_channel=min(1, nc - 1), to_background=True)
+            filtered = postprocess(ops.hard_onehot(pred), closing=closing, fill_holes=fill_holes, keep_largest=keep_largest, min_size=min_component,
+                                   lo_channel=min(1, nc - 1))
             scores[i] = avg_dsc({"p": filtered, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc).item()
         else:
             scores[i] = avg_dsc({"p": pred, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc).item()
@@ -266,8 +271,9 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
             if filtered is not None:
                 np.save(stem + "pred_cc", filtered.cpu().numpy())
     if raw:
-        print("validation without the component filter: %f (keeping the %d largest components of at least %d voxels per class)"
-              % (float(np.mean([v.item() for v in raw.values()])), keep_largest, min_component))
+        print("validation without the component filter: %f (keeping the %d largest components of at least %d voxels per class%s)"
+              % (float(np.mean([v.item() for v in raw.values()])), keep_largest, min_component,
+                 ", after closing %d and hole filling %s" % (closing, "on" if fill_holes else "off") if closing > 0 or fill_holes else ""))
     if surf:
         def table(recs, name):                                   # one host copy per metric, after the last case
             return torch.stack([recs[i][name].reshape(-1) for i in sorted(recs)]).cpu().numpy()
@@ -314,7 +320,8 @@ WHOLE_VOLUME_CVAL = (0.0 - 100.0) / 300.0          # what CropResize's zero padd
 
 
 @torch.no_grad()
-def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="gaussian", keep_largest=0, min_component=0, log=None, tta=None):
+def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="gaussian", keep_largest=0, min_component=0, log=None, tta=None,
+                          closing=0, fill_holes=False):
     """--val_whole_volume: label-free coarse-to-fine inference, scored.  `cases` yields (raw image, relabelled label) (D, H, W) device tensors
     (DeviceCaseLoader.whole_cases).  Per case:
       dice_whole       the clipped and centred WHOLE volume is predicted by sliding window with the segmentation network (evaluation.sliding_window_predict,
@@ -324,9 +331,11 @@ def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="
                        label's, the fine forward runs on the crop, hard Dice in crop space.  A coarse prediction without foreground gives no box: 0.
     Both means are printed; the per-case values go to the dict `log`.  -> (mean dice_whole, mean dice_label_free)
     tta (--val_tta, evaluation.tta_flips): mirror test-time augmentation of the sliding-window pass; the crop-space fine forward stays a single one.
-    The codes are then recorded as log["tta"]."""
+    The codes are then recorded as log["tta"].
+    closing / fill_holes (--val_closing, --val_fill_holes): evaluation.postprocess cleans the sliding-window prediction up before dice_whole — closing, hole
+    filling, then the component filter if it is on; recorded as log["closing"] / log["fill_holes"] when set."""
     from . import data_gpu
-    from .evaluation import localise, segmentation_model_fn, sliding_window_predict, tta_flips
+    from .evaluation import localise, postprocess, segmentation_model_fn, sliding_window_predict, tta_flips
     tta = tta_flips(tta)
     seg = model.Seg if hasattr(model, "Seg") else model
     model_fn = segmentation_model_fn(seg)
@@ -339,8 +348,8 @@ def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="
         if res["prob"].shape[0] != nc:
             raise ValueError("whole-volume validation: the network predicts %d classes, the labels have %d" % (res["prob"].shape[0], nc))
         hard = ops.hard_onehot(res["prob"][None])
-        if keep_largest > 0:
-            hard = ops.keep_largest(hard, k=keep_largest, min_size=min_component, connectivity=26, lo_channel=lo, to_background=True)
+        if keep_largest > 0 or closing > 0 or fill_holes:
+            hard = postprocess(hard, closing=closing, fill_holes=fill_holes, keep_largest=keep_largest, min_size=min_component, lo_channel=lo)
         gt = ops.onehot(lab[None, None], nc)
         whole[i] = _hard_dice(hard[0], gt[0], lo, nc)
         mask = localise(res["prob"], keep_largest=max(keep_largest, 1), min_size=min_component, lo_channel=lo)
@@ -361,20 +370,24 @@ def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="
             log[i] = {"dice_whole": w[i], "dice_label_free": f[i]}
         if tta:
             log["tta"] = list(tta)
+        if closing > 0 or fill_holes:
+            log["closing"], log["fill_holes"] = int(closing), bool(fill_holes)
     return mw, mf
 
 
 @torch.no_grad()
 def validate_fine_whole(model, cases, nc, patch, overlap=0.5, batch=1, blend="gaussian", keep_largest=0, min_component=0, interp="linear", log=None,
-                        save_dir=None, names=None, tta=None):
+                        save_dir=None, names=None, tta=None, closing=0, fill_holes=False):
     """--val_fine_whole: the label-free FINE prediction scored where the scan lives.  `cases` as for validate_whole_volume.  Per case
     evaluation.coarse_to_fine_predict returns the fine pass pasted back onto the scan grid (ops.uncrop); dice_fine_whole is the hard Dice per foreground
     class of that label — after ops.keep_largest when keep_largest > 0 — against the whole label, so it compares with dice_whole and with scores
     published on the scan grid.  A case whose coarse prediction is empty scores its all-background label.  The mean is printed, the per-case values
     go to the dict `log`; with save_dir the scored label of case i is written to <save_dir>/<names[i] without its extension>.npy (uint8, scan shape).
     tta (--val_tta, evaluation.tta_flips): mirror test-time augmentation of the coarse and the fine pass; the codes are then recorded as log["tta"].
+    closing / fill_holes (--val_closing, --val_fill_holes): evaluation.postprocess cleans the pasted label up before it is scored and saved — closing, hole
+    filling, then the component filter if it is on; recorded as log["closing"] / log["fill_holes"] when set.
     -> mean dice_fine_whole"""
-    from .evaluation import coarse_to_fine_predict, tta_flips
+    from .evaluation import coarse_to_fine_predict, postprocess, tta_flips
     tta = tta_flips(tta)
     seg = model.Seg if hasattr(model, "Seg") else model
     lo = min(1, nc - 1)
@@ -386,8 +399,8 @@ def validate_fine_whole(model, cases, nc, patch, overlap=0.5, batch=1, blend="ga
                                      interp=interp, tta=tta)
         label = res["label"]
         hard = ops.onehot(label.float()[None, None], nc)
-        if keep_largest > 0:
-            hard = ops.keep_largest(hard, k=keep_largest, min_size=min_component, connectivity=26, lo_channel=lo, to_background=True)
+        if keep_largest > 0 or closing > 0 or fill_holes:
+            hard = postprocess(hard, closing=closing, fill_holes=fill_holes, keep_largest=keep_largest, min_size=min_component, lo_channel=lo)
             label = hard[0].argmax(0).to(torch.uint8)
         fine[i] = _hard_dice(hard[0], ops.onehot(lab[None, None], nc)[0], lo, nc)
         found[i] = bool(res["found"])
@@ -403,6 +416,8 @@ def validate_fine_whole(model, cases, nc, patch, overlap=0.5, batch=1, blend="ga
             log[i] = {"dice_fine_whole": f[i]}
         if tta:
             log["tta"] = list(tta)
+        if closing > 0 or fill_holes:
+            log["closing"], log["fill_holes"] = int(closing), bool(fill_holes)
     return mean
 
 
@@ -418,10 +433,12 @@ def check_fine_whole_flags(a, script="main_source.py"):
 
 
 def check_whole_volume_flags(a, script="main_source.py"):
-    """--val_whole_volume reads whole cases from disk and needs a segmentation network; --val_tta augments its sliding-window passes"""
+    """--val_whole_volume reads whole cases from disk and needs a segmentation network; --val_tta augments its sliding-window passes;
+    --val_closing counts iterations"""
     def need(cond, what):
         if not cond:
             raise SystemExit("%s: inconsistent flags — %s" % (script, what))
+    need(getattr(a, "val_closing", 0) >= 0, "--val_closing is a number of closing iterations: it cannot be negative")
     if getattr(a, "val_tta", None):
         need(getattr(a, "val_whole_volume", False), "--val_tta mirrors the windows of the whole-volume chain: it needs --val_whole_volume")
         from .evaluation import tta_flips
@@ -764,7 +781,8 @@ def run(args, side="source"):
                 save_dir = os.path.join("result", args.prefix) if getattr(args, "save_eval_result", False) and epoch % 10 == 0 else None
                 scores = validate(method, model, val_loader, nc, keep_largest=getattr(args, "val_keep_largest", 0),
                                   min_component=getattr(args, "val_min_component", 0), save_dir=save_dir, epoch=epoch,
-                                  surface=bool(getattr(args, "val_surface", False)), surface_log=surface_log)
+                                  surface=bool(getattr(args, "val_surface", False)), surface_log=surface_log,
+                                  closing=getattr(args, "val_closing", 0), fill_holes=bool(getattr(args, "val_fill_holes", False)))
             mean = float(np.mean(list(scores.values()))) if scores else 0.0
             os.makedirs(os.path.join("tensorboard", args.prefix), exist_ok=True)
             with open(os.path.join("tensorboard", args.prefix, "score_%d.json" % epoch), "w") as f:
@@ -776,7 +794,8 @@ def run(args, side="source"):
                 whole_log = {}
                 validate_whole_volume(model, val_loader.whole_cases(), nc, args.size, overlap=args.sw_overlap, batch=args.sw_batch, blend=args.sw_blend,
                                       keep_largest=getattr(args, "val_keep_largest", 0), min_component=getattr(args, "val_min_component", 0), log=whole_log,
-                                      tta=getattr(args, "val_tta", None))
+                                      tta=getattr(args, "val_tta", None), closing=getattr(args, "val_closing", 0),
+                                      fill_holes=bool(getattr(args, "val_fill_holes", False)))
                 with open(os.path.join("tensorboard", args.prefix, "whole_%d.json" % epoch), "w") as f:
                     json.dump(whole_log, f)
                 if getattr(args, "val_fine_whole", False):
@@ -784,7 +803,8 @@ def run(args, side="source"):
                     validate_fine_whole(model, val_loader.whole_cases(), nc, args.size, overlap=args.sw_overlap, batch=args.sw_batch, blend=args.sw_blend,
                                         keep_largest=getattr(args, "val_keep_largest", 0), min_component=getattr(args, "val_min_component", 0),
                                         interp=args.fine_interp, log=fine_log, save_dir=getattr(args, "save_whole_pred", None), names=val_loader.names,
-                                        tta=getattr(args, "val_tta", None))
+                                        tta=getattr(args, "val_tta", None), closing=getattr(args, "val_closing", 0),
+                                        fill_holes=bool(getattr(args, "val_fill_holes", False)))
                     with open(os.path.join("tensorboard", args.prefix, "fine_%d.json" % epoch), "w") as f:
                         json.dump(fine_log, f)
             print("epoch %d validation result: %f, best result %f." % (epoch + 1, mean, best))
@@ -845,6 +865,12 @@ def add_native_flags(parser):
     g.add_argument("--val_keep_largest", type=int, default=0, help="validation: keep only the K largest 26-connected components of every foreground class of the "
                    "hard prediction before the Dice score (utils/utils.py:776-796, on the device); 0 = off, the reference's validation")
     g.add_argument("--val_min_component", type=int, default=0, help="with --val_keep_largest: components of fewer voxels are dropped as well (predict_vol uses 10000)")
+    g.add_argument("--val_closing", type=int, default=0, metavar="N", help="validation: binary closing of every foreground class of the hard prediction with N "
+                   "iterations of the 26-neighbourhood (scipy.ndimage.binary_closing, on the device) before the component filter and the score; 0 = off; "
+                   "whole_<epoch>.json and fine_<epoch>.json record it as \"closing\"")
+    g.add_argument("--val_fill_holes", action="store_true", help="validation: fill the holes of every foreground class of the hard prediction "
+                   "(scipy.ndimage.binary_fill_holes, 6-connected background, on the device) after --val_closing and before the component filter; only "
+                   "background voxels change class; recorded as \"fill_holes\"")
     g.add_argument("--val_surface", action="store_true", help="validation: also report ASSD and HD95 (medpy's convention, in voxels) of the hard prediction against "
                    "the label per foreground class, computed on the device; per-case values go to tensorboard/<prefix>/surface_<epoch>.json")
     g.add_argument("--val_whole_volume", action="store_true", help="validation (with --real_data): additionally predict every WHOLE validation case by sliding window "

@@ -133,6 +133,84 @@ def hd95(A, B, spacing=None, connectivity=6):
 
 
 # ----------------------------------------------------------------------------------------------------
+# binary morphology and hole filling on the device (csrc/morph.hip): scipy.ndimage's operators without the host detour
+# ----------------------------------------------------------------------------------------------------
+def _morph(name, X, **kw):
+    x, single = _planar(X)
+    out = getattr(ops, name)(x.detach(), **kw)
+    return out[0, 0] if single else out
+
+
+def binary_dilation(input, iterations=1, connectivity=6, border_value=0):
+    """scipy.ndimage.binary_dilation of the binarised (>= 0.5) mask, (D, H, W) or per plane of (N, C, D, H, W): connectivity 6 is
+    generate_binary_structure(3, 1), 26 is (3, 3).  -> fp32 0 / 1 of the same shape."""
+    return _morph("binary_dilation", input, iterations=iterations, connectivity=connectivity, border_value=border_value)
+
+
+def binary_erosion(input, iterations=1, connectivity=6, border_value=0):
+    """scipy.ndimage.binary_erosion, as binary_dilation"""
+    return _morph("binary_erosion", input, iterations=iterations, connectivity=connectivity, border_value=border_value)
+
+
+def binary_opening(input, iterations=1, connectivity=6, border_value=0):
+    """scipy.ndimage.binary_opening (erode^n then dilate^n), as binary_dilation"""
+    return _morph("binary_opening", input, iterations=iterations, connectivity=connectivity, border_value=border_value)
+
+
+def binary_closing(input, iterations=1, connectivity=6, border_value=0):
+    """scipy.ndimage.binary_closing (dilate^n then erode^n), as binary_dilation"""
+    return _morph("binary_closing", input, iterations=iterations, connectivity=connectivity, border_value=border_value)
+
+
+def fill_holes(input, connectivity=6):
+    """scipy.ndimage.binary_fill_holes of the binarised mask, (D, H, W) or per plane of (N, C, D, H, W): background that does not reach the outside of
+    the volume through `connectivity`-neighbours becomes foreground."""
+    return _morph("fill_holes", input, connectivity=connectivity)
+
+
+def get_synthesis_mask(data_dict, field='venous'):
+    """utils/utils.py:647-655 on device tensors: bone (> 200 HU) dilated twice with the 6-neighbourhood and bowel gas (< 0 HU) are excluded;
+    data_dict[field + '_syn_mask'] = (1 - bowel) * (1 - bone), fp32."""
+    v = data_dict[field]
+    bone = binary_dilation((v > 200).float(), iterations=2)
+    bowel = (v < 0).float()
+    data_dict[field + '_syn_mask'] = ((1 - bowel) * (1 - bone)).float()
+    return data_dict
+
+
+@torch.no_grad()
+def postprocess(hard, closing=0, fill_holes=False, keep_largest=0, min_size=0, lo_channel=1):
+    """The usual clean-up of a one-hot prediction (N, C, D, H, W), on the device.  For every foreground class from lo_channel on, in ascending order:
+    binary closing with `closing` iterations of the 26-neighbourhood (border_value 0; 0: none), then hole filling with 6-connectivity; afterwards
+    ops.keep_largest(k=keep_largest, min_size, 26-connectivity, to_background=True) when keep_largest > 0.  The tensor stays one-hot: a class gains
+    only voxels that are background (channel 0) at that moment — so the lowest class wins a contested voxel — and a voxel a class loses (a closing
+    can erode at the volume border) goes to channel 0.  With closing 0 and fill_holes False this is exactly the keep_largest call."""
+    if isinstance(closing, bool) or int(closing) != closing or closing < 0:
+        raise ValueError("postprocess: closing is a number of iterations >= 0, got %r" % (closing,))
+    lo = int(lo_channel)
+    x = hard
+    if closing > 0 or fill_holes:
+        x = hard.detach().float().clone()
+        for c in range(lo, x.shape[1]):
+            cur = (x[:, c:c + 1] >= 0.5).float()
+            new = cur
+            if closing > 0:
+                new = ops.binary_closing(new, iterations=int(closing), connectivity=26, border_value=0)
+            if fill_holes:
+                new = ops.fill_holes(new, connectivity=6)
+            if lo < 1:                                           # no background channel to trade with
+                x[:, c:c + 1] = new
+                continue
+            gain = new * (1 - cur) * (x[:, 0:1] >= 0.5).float()
+            lose = cur * (1 - new)
+            x[:, c:c + 1] = cur + gain - lose
+            x[:, 0:1] += lose - gain
+    if keep_largest > 0:
+        x = ops.keep_largest(x, k=int(keep_largest), min_size=int(min_size), connectivity=26, lo_channel=lo, to_background=True)
+    return x
+
+
+# ----------------------------------------------------------------------------------------------------
 # whole-volume inference: sliding-window prediction on the device (csrc/window.hip).  The reference has no counterpart
 # (utils/utils.py:predict_vol is a 2D slice loop); tests/sliding_util.py restates the algorithm in numpy.
 # ----------------------------------------------------------------------------------------------------

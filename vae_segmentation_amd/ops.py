@@ -2502,6 +2502,89 @@ def surface_distances(pred, gt, spacing=None, connectivity=6):
     return out
 
 
+# binary morphology and hole filling (csrc/morph.hip).  Workspaces are cached per (shape, connectivity, device) like the CC ones: never freed or moved.
+MORPH_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3}          # VS_MORPH_*
+_MORPH_WORKSPACES = {}
+_FILL_WORKSPACES = {}
+
+
+def _check_connectivity(connectivity, what):
+    if isinstance(connectivity, bool) or connectivity not in (6, 26):
+        raise ValueError("%s: connectivity is 6 (generate_binary_structure(3, 1)) or 26 ((3, 3)), got %r" % (what, connectivity))
+    return int(connectivity)
+
+
+def _workspace(cache, key, query, what, device):
+    ws = cache.get(key)
+    if ws is None:
+        nbytes = query()
+        check(min(nbytes, 0), what)
+        ws = cache[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def morph(mask, op, iterations=1, connectivity=6, border_value=0):
+    """scipy.ndimage.binary_dilation / binary_erosion / binary_opening / binary_closing (op "dilate" / "erode" / "open" / "close") per (n, c) plane of a
+    planar (N, C, D, H, W) mask (foreground: value >= 0.5) -> fp32 0 / 1.  connectivity 6 is generate_binary_structure(3, 1), 26 is (3, 3); the
+    structure is applied `iterations` >= 1 times (opening: erode^n then dilate^n, closing: dilate^n then erode^n); voxels outside the volume read as
+    border_value (0 or 1) in both halves, as scipy passes it on.  Bit-packed on the device (csrc/morph.hip), no synchronisation."""
+    if op not in MORPH_OPS:
+        raise ValueError("morph: op is one of %s, got %r" % (sorted(MORPH_OPS), op))
+    connectivity = _check_connectivity(connectivity, "morph")
+    try:
+        ok = not isinstance(iterations, bool) and int(iterations) == iterations and iterations >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("morph: iterations is an integer >= 1, got %r" % (iterations,))
+    if isinstance(border_value, bool):
+        border_value = int(border_value)
+    if border_value not in (0, 1):
+        raise ValueError("morph: border_value is 0 or 1, got %r" % (border_value,))
+    m = _mask_prepare(mask, "binary morphology")
+    n, c, d, h, w = m.shape
+    ws = _workspace(_MORPH_WORKSPACES, (n, c, d, h, w, connectivity, m.device), lambda: lib.vs_morph_workspace_bytes(n, c, d, h, w),
+                    "morph_workspace_bytes", m.device)
+    out = torch.empty_like(m)
+    check(lib.vs_morph(m.data_ptr(), out.data_ptr(), n, c, d, h, w, MORPH_OPS[op], connectivity, int(min(iterations, 2 ** 31 - 1)), int(border_value),
+                       ws.data_ptr(), _stream()), "morph")
+    return out
+
+
+def binary_dilation(input, iterations=1, connectivity=6, border_value=0):
+    """scipy.ndimage.binary_dilation(input, generate_binary_structure(3, 1 or 3), iterations, border_value=border_value) per plane (morph)"""
+    return morph(input, "dilate", iterations=iterations, connectivity=connectivity, border_value=border_value)
+
+
+def binary_erosion(input, iterations=1, connectivity=6, border_value=0):
+    """scipy.ndimage.binary_erosion per plane (morph)"""
+    return morph(input, "erode", iterations=iterations, connectivity=connectivity, border_value=border_value)
+
+
+def binary_opening(input, iterations=1, connectivity=6, border_value=0):
+    """scipy.ndimage.binary_opening per plane (morph)"""
+    return morph(input, "open", iterations=iterations, connectivity=connectivity, border_value=border_value)
+
+
+def binary_closing(input, iterations=1, connectivity=6, border_value=0):
+    """scipy.ndimage.binary_closing per plane (morph)"""
+    return morph(input, "close", iterations=iterations, connectivity=connectivity, border_value=border_value)
+
+
+def fill_holes(mask, connectivity=6):
+    """scipy.ndimage.binary_fill_holes(X, structure) per (n, c) plane of a planar (N, C, D, H, W) mask (foreground: value >= 0.5) -> fp32 0 / 1: the
+    complement of the background voxels that reach the outside of the volume through `connectivity`-neighbours (6, scipy's default, or 26).
+    The complement is labelled with the connected-component union-find on the device (csrc/morph.hip), no synchronisation."""
+    connectivity = _check_connectivity(connectivity, "fill_holes")
+    m = _mask_prepare(mask, "hole filling")
+    n, c, d, h, w = m.shape
+    ws = _workspace(_FILL_WORKSPACES, (n, c, d, h, w, connectivity, m.device), lambda: lib.vs_fill_holes_workspace_bytes(n, c, d, h, w, connectivity),
+                    "fill_holes_workspace_bytes", m.device)
+    out = torch.empty_like(m)
+    check(lib.vs_fill_holes(m.data_ptr(), out.data_ptr(), n, c, d, h, w, connectivity, ws.data_ptr(), _stream()), "fill_holes")
+    return out
+
+
 # sliding-window prediction (csrc/window.hip).  evaluation.sliding_window_predict drives these; nothing here synchronises.
 SW_BLENDS = ("constant", "gaussian")
 SW_GAUSSIAN_FLOOR = 1e-3
