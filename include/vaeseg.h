@@ -611,6 +611,32 @@ int vs_sw_finalize(const float* acc, const float* wsum, float* prob, unsigned ch
 int vs_uncrop(const float* prob, unsigned char* label, float* prob_out, int k, int patch, int d, int h, int w, int lo_z, int lo_y, int lo_x,
               int hi_z, int hi_y, int hi_x, int off_z, int off_y, int off_x, int side, int interp, void* stream);
 
+/* ---- scan geometry: the array a scanner wrote <-> the re-oriented 1 mm grid every entry point works on (csrc/scan.hip) -------------------
+ * The reference's data/data_process.py:24-33 makes, from raw (x, y, z) and the signed diagonal `spacing` of its affine,
+ *   oriented = transpose(raw, [1, 0, 2])[::ind[1], ::ind[0], ::ind[2]],  ind[i] = +1 if spacing[i] < 0 else -1      shape (y, x, z)
+ * and resizes it to the 1 mm grid (d1, h1, w1) = int((y, x, z) * |spacing|) — the TRANSPOSED shape times the UNTRANSPOSED spacing, as the reference
+ * writes it (data_gpu.ScanGeometry does that arithmetic on the host).  The kernels take the raw shape and three flips in oriented axis order
+ * (flip0 = ind[1] < 0, flip1 = ind[0] < 0, flip2 = ind[2] < 0):
+ *   oriented[o0][o1][o2] = raw[g1(o1)][g0(o0)][g2(o2)],  g_a(o) = flip_a ? n_a - 1 - o : o,  (n_0, n_1, n_2) = (y, x, z).
+ * vs_scan_orient: raw of VS_SCAN_I16 / U8 / I8 / F32 -> out, the contiguous fp32 oriented volume (y, x, z), exact values, one launch.  The contiguous
+ * axis stays contiguous and is at most reversed; a lane moves four of its elements per load and store.
+ * vs_scan_to_native: the way back for an answer on the 1 mm grid.  src: planar fp32 probabilities (k, d1, h1, w1), 1 <= k <= 8 (src_is_label 0), or a
+ * uint8 label (d1, h1, w1) (src_is_label 1: k = 1, interp 0, prob_out NULL).  Raw voxel (i0, i1, i2) has the oriented index (g0(i1), g1(i0), g2(i2))
+ * and per axis the 1 mm coordinate q = (o + 0.5) * n_1mm / n_oriented - 0.5 in fp64.
+ *   interp 0 (nearest): the sample at floor(q + 0.5), clamped to [0, n_1mm - 1].
+ *   interp 1 (linear): q mirrored at the borders (q < 0 -> -q, q > n_1mm - 1 -> 2 (n_1mm - 1) - q), trilinear, weights and products in fp64, the sum
+ *   rounded to fp32 once: scipy.ndimage.zoom(src[c], (y, x, z) / (d1, h1, w1), order=1, mode='mirror', grid_mode=True) carried to the raw axes.
+ * label (x, y, z) bytes: the channel argmax of those fp32 values, ties to the first maximal channel, a NaN channel wins (vs_hard_onehot, vs_uncrop);
+ * for a label source the sample itself.  prob_out (may be NULL): the resampled probabilities, planar fp32 (k, x, y, z).
+ * One launch writes every element of label and prob_out exactly once: no memset before it, no atomics, no synchronisation (capturable), bit-identical
+ * from run to run and between the two builds.  Pointers are 16-byte aligned (VS_EALIGN); an empty shape or one of 2^31 voxels or more: VS_ESHAPE; k
+ * outside [1, 8], interp outside {0, 1}, a label source with k != 1, interp 1 or prob_out: VS_EINVAL; an unknown dtype: VS_EDTYPE — all on the host
+ * before any launch.  The kernels clamp every source index into its axis and bound their stores by (x, y, z) alone. */
+enum { VS_SCAN_I16 = 0, VS_SCAN_U8 = 1, VS_SCAN_I8 = 2, VS_SCAN_F32 = 3 };
+int vs_scan_orient(const void* raw, int dtype, float* out, int x, int y, int z, int flip0, int flip1, int flip2, void* stream);
+int vs_scan_to_native(const void* src, int src_is_label, unsigned char* label, float* prob_out, int k, int d1, int h1, int w1, int x, int y, int z,
+                      int flip0, int flip1, int flip2, int interp, void* stream);
+
 /* ---- fully connected (VAE bottleneck, joint_model.py:216-218,242-243,248-253) -------------------- */
 /* y[b][j] = act( bias[j] + sum_k W[j][k] * x[b][phys(k)] )  with phys(k) = (k % pv)*pc + k / pv when pc > 0:
  * x is a channels-last activation [B][pv voxels][pc channels] read in the reference's flatten order

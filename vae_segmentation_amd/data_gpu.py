@@ -106,6 +106,95 @@ def resize(vol, output_size, order=1, anti_aliasing=None):
     return out
 
 
+# ---- raw scans: the reference's one-off dataset preparation (data/data_process.py) on the device ---------------------------------------------------
+class ScanGeometry:
+    """The integers of data_process.py:24-33 for a scan of `raw_shape` = (X, Y, Z) whose affine has the signed diagonal `affine_diag` (a 4 x 4 or
+    3 x 3 affine is accepted too: its diagonal is taken).  Host arithmetic only, restated exactly as the reference writes it:
+        spacing  = the three diagonal entries, in raw axis order
+        ind[i]   = +1 if spacing[i] < 0 else -1
+        oriented = transpose(raw, [1, 0, 2])[::ind[1], ::ind[0], ::ind[2]]            shape (Y, X, Z)
+        new_size = (oriented_shape * abs(spacing)).astype(int)
+    The last line multiplies the TRANSPOSED shape by the UNTRANSPOSED spacing: with spacing (sx, sy, sz) the 1 mm grid is (int(Y sx), int(X sy),
+    int(Z sz)).  For the square in-plane spacing of CT it makes no difference; it is kept because the reference's volumes are the yardstick.
+    raw_shape, oriented_shape, shape_1mm: int tuples; flips: three bools in oriented axis order (ind[1] < 0, ind[0] < 0, ind[2] < 0);
+    as_tuple(): (x, y, z, flip0, flip1, flip2, d1, h1, w1), the plain-int form ops.scan_orient / ops.to_native take."""
+
+    def __init__(self, raw_shape, affine_diag):
+        shape = tuple(int(s) for s in raw_shape)
+        spacing = np.asarray(affine_diag, dtype=np.float64)
+        if spacing.ndim == 2:
+            spacing = np.diagonal(spacing)[:3]
+        if len(shape) != 3 or spacing.shape != (3,) or min(shape) < 1:
+            raise ValueError("ScanGeometry: raw_shape (X, Y, Z) and three affine diagonal entries, got %r, %r" % (raw_shape, affine_diag))
+        if not np.all(np.isfinite(spacing)) or np.any(spacing == 0):
+            raise ValueError("ScanGeometry: spacing must be finite and non-zero, got %r" % (affine_diag,))
+        ind = [1 if s < 0 else -1 for s in spacing]
+        self.raw_shape = shape
+        self.spacing = tuple(float(s) for s in spacing)
+        self.oriented_shape = (shape[1], shape[0], shape[2])
+        self.flips = (ind[1] < 0, ind[0] < 0, ind[2] < 0)
+        self.shape_1mm = tuple(int(v) for v in (np.array(self.oriented_shape) * np.abs(spacing)).astype(int))
+        if min(self.shape_1mm) < 1:
+            raise ValueError("ScanGeometry: the 1 mm grid %s of shape %s at spacing %s is empty" % (self.shape_1mm, shape, self.spacing))
+
+    def as_tuple(self):
+        return self.raw_shape + tuple(int(f) for f in self.flips) + self.shape_1mm
+
+    def __repr__(self):
+        return "ScanGeometry(raw_shape=%s, spacing=%s, flips=%s, shape_1mm=%s)" % (self.raw_shape, self.spacing, self.flips, self.shape_1mm)
+
+
+def cube_slices(box, shape, pad=32):
+    """The three slices of data_process.py:45-68 for the foreground box `box` = (min[3], max[3]) of a label of `shape`: box -/+ pad clipped to the volume
+    (the upper bound is max + pad, as the reference writes it), center = mean(bbox, 1).astype(int), L = the largest extent, rows
+    [center - int(L / 2), center - int(L / 2) + L) clipped again.  Host arithmetic only."""
+    pad = [int(pad)] * 3 if np.isscalar(pad) else [int(p) for p in pad]
+    shape = [int(s) for s in shape]
+    bbox = np.array([[max(0, int(box[0][d]) - pad[d]), min(shape[d], int(box[1][d]) + pad[d])] for d in range(3)])
+    center = np.mean(bbox, 1).astype(int)
+    L = int(np.max(bbox[:, 1] - bbox[:, 0]))
+    return tuple(slice(max(0, int(center[d]) - int(L / 2)), min(shape[d], int(center[d]) - int(L / 2) + L)) for d in range(3))
+
+
+def foreground_cube(label_1mm, pad=32):
+    """cube_slices of the bounding box of label_1mm > 0 (bounding_box: the one host synchronisation).  An empty label raises ValueError (the reference
+    fails on np.min of an empty array there)."""
+    box = bounding_box(label_1mm)
+    if box is None:
+        raise ValueError("foreground_cube: the label has no foreground")
+    return cube_slices(box, label_1mm.shape, pad)
+
+
+def preprocess_scan(raw, affine_diag, label=None, label_affine_diag=None, truncate=False):
+    """data_process.py:23-42 on the device.  raw (X, Y, Z): a CUDA int16 / uint8 / int8 / float32 tensor as the scanner wrote it; affine_diag: the
+    signed diagonal of its affine.  The scan is oriented (ops.scan_orient) and resized to ScanGeometry.shape_1mm with skimage's defaults (order 1,
+    anti-aliasing where an axis shrinks).  label (optional, same dtypes): oriented by ITS affine's diagonal (label_affine_diag, default the image's) and
+    resized with order 0 / no anti-aliasing to the IMAGE's shape_1mm, as the reference does.
+    -> {"image": (D1, H1, W1) fp32, "label": fp32 or None, "geometry": the image's ScanGeometry}, on the device.
+    truncate=True applies the astype(int16) / astype(int8) truncation towards zero that img.npy / label.npy / merge.npy store; the tensors stay float32
+    and hold those integers (values inside the integer types' range, which CT intensities and labels are)."""
+    from . import ops
+    geometry = ScanGeometry(tuple(raw.shape), affine_diag)
+    image = resize(ops.scan_orient(raw, geometry), geometry.shape_1mm)
+    lab = None
+    if label is not None:
+        lgeo = ScanGeometry(tuple(label.shape), affine_diag if label_affine_diag is None else label_affine_diag)
+        lab = resize(ops.scan_orient(label, lgeo), geometry.shape_1mm, order=0, anti_aliasing=False)
+    if truncate:
+        image = image.trunc_()
+        lab = None if lab is None else lab.trunc_()
+    return {"image": image, "label": lab, "geometry": geometry}
+
+
+def make_merge(pre, pad=32):
+    """preprocess_scan's dict -> the (d, h, w, 2) cube of data_process.py:57-75 that merge.npy holds: image and label cut to foreground_cube(label, pad),
+    stacked on a last axis and truncated towards zero (the file's astype(int16)), as a float32 CUDA tensor — what train_sample / DeviceCaseLoader take."""
+    if pre.get("label") is None:
+        raise ValueError("make_merge: the case has no label (data_process.py cuts the cube around the label's foreground)")
+    sl = foreground_cube(pre["label"], pad)
+    return torch.stack((pre["image"][sl], pre["label"][sl]), dim=-1).trunc_()
+
+
 class BaseTransform:
     def __init__(self, fields):
         self.fields = [fields] if isinstance(fields, str) else list(fields)

@@ -380,7 +380,8 @@ def _window_intensities(data_dict):
 
 
 @torch.no_grad()
-def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", batch=1, keep_largest=1, min_size=0, interp="linear", graph=False, tta=None):
+def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", batch=1, keep_largest=1, min_size=0, interp="linear", graph=False, tta=None,
+                           want_prob=False):
     """Label-free segmentation of a raw scan `image` (D, H, W) on the device, returned in the scan's own geometry.  The composition of the public pieces:
       coarse   Clip / CenterIntensities -> sliding_window_predict with cubic windows of side `patch` -> localise (keep_largest, min_size) -> data_gpu.bounding_box
                (the chain's one host synchronisation)
@@ -390,7 +391,9 @@ def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", bat
     A coarse prediction without foreground — or with a single-voxel box, of which CropResize can make no crop — gives found False, geometry None and an
     all-background label.
     tta (tta_flips): mirror test-time augmentation of both passes.  The coarse pass receives it; the fine pass is a sliding-window pass over the crop
-    itself — one window, constant blend — so its probabilities are the mean of the un-flipped answers, summed in the order of the codes."""
+    itself — one window, constant blend — so its probabilities are the mean of the un-flipped answers, summed in the order of the codes.
+    want_prob=True adds "prob": the pasted probabilities (K, D, H, W) fp32 of ops.uncrop(want_prob=True) — (1, 0, ..., 0) outside the crop and
+    everywhere when nothing was found."""
     from . import data_gpu
     ops._require_cuda(image)
     if image.dim() != 3:
@@ -406,12 +409,40 @@ def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", bat
     box = data_gpu.bounding_box(mask)
     geometry = data_gpu.crop_geometry(box, img.shape) if box is not None else None
     if geometry is None or geometry[3] < 1:
-        return {"label": torch.zeros(tuple(img.shape), dtype=torch.uint8, device=img.device), "coarse_label": coarse["label"], "geometry": None, "found": False}
+        res = {"label": torch.zeros(tuple(img.shape), dtype=torch.uint8, device=img.device), "coarse_label": coarse["label"], "geometry": None, "found": False}
+        if want_prob:
+            res["prob"] = torch.zeros((coarse["prob"].shape[0],) + tuple(img.shape), dtype=torch.float32, device=img.device)
+            res["prob"][0] = 1.0
+        return res
     crop = data_gpu.CropResize([_FIELD], (int(patch),) * 3)({_FIELD: img, _FIELD + "_pancreas": mask, _FIELD + "_pancreas_pred": mask})
     crop = _window_intensities(crop)
     if tta is None:
         fine = model_fn(crop[_FIELD][None, None])[0]
     else:
         fine = sliding_window_predict(model_fn, crop[_FIELD], patch, overlap=0.0, blend="constant", batch=batch, tta=tta)["prob"]
-    label = ops.uncrop(fine, geometry, tuple(img.shape), interp=interp)["label"]
-    return {"label": label, "coarse_label": coarse["label"], "geometry": geometry, "found": True}
+    pasted = ops.uncrop(fine, geometry, tuple(img.shape), interp=interp, want_prob=want_prob)
+    res = {"label": pasted["label"], "coarse_label": coarse["label"], "geometry": geometry, "found": True}
+    if want_prob:
+        res["prob"] = pasted["prob"]
+    return res
+
+
+@torch.no_grad()
+def predict_scan(seg, raw, affine_diag, patch, overlap=0.5, blend="gaussian", batch=1, keep_largest=1, min_size=0, interp="linear", graph=False, tta=None,
+                 native_interp="linear", details=False):
+    """A scan as the scanner wrote it in, a label on that scan's own voxel grid out, without leaving the device.  raw (X, Y, Z): CUDA int16 / uint8 /
+    int8 / float32; affine_diag: the signed diagonal of its affine.  By definition the two-step composition of the public pieces:
+      data_gpu.preprocess_scan               orient + resize to the 1 mm grid (data_process.py:23-34)
+      coarse_to_fine_predict(want_prob=True) with the options of that function: probabilities pasted onto the 1 mm grid by ops.uncrop(interp)
+      ops.to_native(native_interp)           those probabilities resampled onto the raw grid, argmax
+    The two resamplings (crop -> 1 mm, 1 mm -> raw) are NOT fused into one map: that would change the values.
+    -> the label (X, Y, Z) uint8; with details=True a dict {"label", "label_1mm", "coarse_label", "geometry" (ScanGeometry), "crop_geometry", "found"}."""
+    from . import data_gpu
+    pre = data_gpu.preprocess_scan(raw, affine_diag)
+    res = coarse_to_fine_predict(seg, pre["image"], patch, overlap=overlap, blend=blend, batch=batch, keep_largest=keep_largest, min_size=min_size,
+                                 interp=interp, graph=graph, tta=tta, want_prob=True)
+    label = ops.to_native(res["prob"], pre["geometry"], interp=native_interp)["label"]
+    if not details:
+        return label
+    return {"label": label, "label_1mm": res["label"], "coarse_label": res["coarse_label"], "geometry": pre["geometry"], "crop_geometry": res["geometry"],
+            "found": res["found"]}

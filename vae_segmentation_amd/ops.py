@@ -2749,6 +2749,84 @@ def uncrop(prob, geometry, shape, interp="linear", want_prob=False):
     return res
 
 
+# scan geometry: the array a scanner wrote <-> the re-oriented 1 mm grid (csrc/scan.hip; data_gpu.ScanGeometry does the host arithmetic)
+SCAN_DTYPES = {torch.int16: _lib.VS_SCAN_I16, torch.uint8: _lib.VS_SCAN_U8, torch.int8: _lib.VS_SCAN_I8, torch.float32: _lib.VS_SCAN_F32}
+
+
+def _scan_geometry(geometry, what):
+    """-> (x, y, z, flip0, flip1, flip2, d1, h1, w1): a data_gpu.ScanGeometry or its as_tuple()"""
+    g = geometry.as_tuple() if hasattr(geometry, "as_tuple") else tuple(geometry)
+    if len(g) != 9:
+        raise ValueError("%s: geometry is a data_gpu.ScanGeometry or its as_tuple() (x, y, z, flip0, flip1, flip2, d1, h1, w1), got %r" % (what, geometry))
+    g = tuple(int(v) for v in g)
+    if min(g[:3] + g[6:]) < 1:
+        raise ValueError("%s: empty shape in geometry %r" % (what, g))
+    return g
+
+
+def _scan_tensor(t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError("%s: expected a CUDA tensor (libvaeseg HIP kernels; there is no CPU fallback), got %s" %
+                        (what, "a %s tensor" % t.device.type if isinstance(t, torch.Tensor) else type(t).__name__))
+    t = _contig(t.detach())
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def scan_orient(raw, geometry):
+    """raw (X, Y, Z) int16 / uint8 / int8 / float32 as the scanner wrote it -> the oriented float32 volume (Y, X, Z) of data_process.py:29-30,
+    transpose(raw, [1, 0, 2])[::ind[1], ::ind[0], ::ind[2]], exact values, one launch (vs_scan_orient)."""
+    r = _scan_tensor(raw, "scan_orient")
+    if r.dtype not in SCAN_DTYPES:
+        raise TypeError("scan_orient: raw is int16, uint8, int8 or float32, got %s" % r.dtype)
+    if r.dim() != 3:
+        raise ValueError("scan_orient: expected a raw scan (X, Y, Z), got shape %s" % (tuple(r.shape),))
+    x, y, z, f0, f1, f2 = _scan_geometry(geometry, "scan_orient")[:6]
+    if tuple(r.shape) != (x, y, z):
+        raise ValueError("scan_orient: the geometry's raw_shape %s is not the tensor's %s" % ((x, y, z), tuple(r.shape)))
+    out = torch.empty((y, x, z), dtype=torch.float32, device=r.device)
+    check(lib.vs_scan_orient(r.data_ptr(), SCAN_DTYPES[r.dtype], out.data_ptr(), x, y, z, f0, f1, f2, _stream()), "scan_orient")
+    return out
+
+
+def to_native(src, geometry, interp="linear", want_prob=False):
+    """An answer on the 1 mm grid put back onto the voxel grid of the scan it came from, in that scan's axis order, orientation and spacing.
+    src: planar probabilities (K, D1, H1, W1), 1 <= K <= 8 (any float dtype; resampled in fp32), or a uint8 label (D1, H1, W1), which is a copy of
+    samples and takes interp="nearest" only.  Raw voxel (i0, i1, i2) has the oriented index (f(i1), f(i0), f(i2)), f the per-axis flip, and per axis the
+    1 mm coordinate q = (o + 0.5) n_1mm / n_oriented - 0.5 (fp64).  "nearest": the sample at floor(q + 0.5) clamped to [0, n_1mm - 1]; "linear":
+    trilinear with q mirrored at the borders, scipy.ndimage.zoom(order=1, mode="mirror", grid_mode=True).
+    -> {"label": (X, Y, Z) uint8 — argmax, ties to the first channel — and, with want_prob, "prob": (K, X, Y, Z) fp32}.  One launch writes both outputs
+    whole (vs_scan_to_native); it does not synchronise and can be captured in a graph."""
+    s = _scan_tensor(src, "to_native")
+    if interp not in UNCROP_INTERPS:
+        raise ValueError("to_native: interp is one of %s, got %r" % (UNCROP_INTERPS, interp))
+    is_label = s.dtype == torch.uint8
+    if is_label:
+        if s.dim() != 3:
+            raise ValueError("to_native: expected a uint8 label (D1, H1, W1), got shape %s" % (tuple(s.shape),))
+        if interp != "nearest" or want_prob:
+            raise ValueError("to_native: a uint8 label is a copy of samples: interp=\"nearest\" and no probabilities")
+        k = 1
+    else:
+        if not s.is_floating_point():
+            raise TypeError("to_native: src is floating-point probabilities (K, D1, H1, W1) or a uint8 label (D1, H1, W1), got %s" % s.dtype)
+        if s.dim() != 4 or not 1 <= s.shape[0] <= 8:
+            raise ValueError("to_native: expected probabilities (K, D1, H1, W1) with 1 <= K <= 8, got shape %s" % (tuple(s.shape),))
+        if s.dtype != torch.float32:
+            s = s.float()
+        k = int(s.shape[0])
+    x, y, z, f0, f1, f2, d1, h1, w1 = _scan_geometry(geometry, "to_native")
+    if tuple(s.shape[-3:]) != (d1, h1, w1):
+        raise ValueError("to_native: the geometry's shape_1mm %s is not the tensor's %s" % ((d1, h1, w1), tuple(s.shape[-3:])))
+    label = torch.empty((x, y, z), dtype=torch.uint8, device=s.device)
+    out = torch.empty((k, x, y, z), dtype=torch.float32, device=s.device) if want_prob else None
+    check(lib.vs_scan_to_native(s.data_ptr(), int(is_label), label.data_ptr(), _p(out), k, d1, h1, w1, x, y, z, f0, f1, f2, UNCROP_INTERPS.index(interp),
+                                _stream()), "scan_to_native")
+    res = {"label": label}
+    if want_prob:
+        res["prob"] = out
+    return res
+
+
 def instnorm_stats(x):
     n, c = x.shape[0], x.shape[-1]
     st = _new_stats(n, c, x.device)
