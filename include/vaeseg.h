@@ -554,6 +554,26 @@ int vs_morph(const float* mask, float* out, int n, int c, int d, int h, int w, i
 long long vs_fill_holes_workspace_bytes(int n, int c, int d, int h, int w, int connectivity);
 int vs_fill_holes(const float* mask, float* out, int n, int c, int d, int h, int w, int connectivity, void* workspace, void* stream);
 
+/* ---- per-component measurements and the contingency table of label volumes (csrc/regions.hip; no counterpart in the reference) -------------
+ * What scipy.ndimage.find_objects / np.bincount give on the host, for int32 label volumes (n, c, d, h, w) as vs_cc_label writes them: 0 is
+ * background, 1..K are components (or classes); every (n, c) plane is its own problem; any d, h, w >= 1 with d*h*w < 2^31.
+ *   vs_region_props  table: int64 (n, c, max_rows, 10), row r for label r + 1, columns
+ *                        count, zmin, ymin, xmin, zmax, ymax, xmax, sum_z, sum_y, sum_x      (box inclusive; sums of the voxel indices)
+ *                    a label that does not occur has count 0, mins (d, h, w), maxes -1, sums 0.
+ *   vs_contingency   table: int64 (n, c, rows_a + 1, rows_b + 1), table[i][j] = voxels with a == i and b == j; row / column 0 are background.
+ *                    (rows_a + 1) * (rows_b + 1) <= 2^22 per plane (VS_ESHAPE beyond).  Tables of at most 4096 cells are summed per workgroup in LDS.
+ *   overflow         int32 (n, c): the voxels whose label (on either side) is negative or above max_rows / rows_a / rows_b.  They are counted
+ *                    there and in no row or cell.
+ * The caller owns every buffer and need not clear them: the first launch of a call writes the initial state, the second accumulates — nothing
+ * is allocated, synchronised or read back, no kernel waits for another workgroup, and a call can be captured in a HIP graph.  Every accumulator is
+ * an integer updated with atomicAdd / atomicMin / atomicMax by vector lanes, one update per RUN of equal labels along x (per wave and chunk of
+ * rows for the label a wave currently carries), so the tables do not depend on the order of arrival: both builds of the library and every run
+ * give the same bits.  a and b may be the same buffer.  A null pointer, max_rows < 1, rows_a or rows_b < 0: VS_EINVAL; an empty or too large
+ * shape or table: VS_ESHAPE; labels not 4-byte, table not 8-byte aligned: VS_EALIGN; all answered on the host before any launch. */
+int vs_region_props(const int* labels, int n, int c, int d, int h, int w, int max_rows, long long* table, int* overflow, void* stream);
+int vs_contingency(const int* a, const int* b, int n, int c, int d, int h, int w, int rows_a, int rows_b, long long* table, int* overflow,
+                   void* stream);
+
 /* ---- sliding-window prediction of a whole volume (csrc/window.hip; no counterpart in the reference) -------------------------------
  * A volume (C, D, H, W) is tiled with overlapping cubic windows of side `patch`, a network maps batches (B, C, P, P, P) of them to planar
  * probabilities (B, K, P, P, P), and the windows are blended: prob[k][v] = sum_i w_i(v) p_i[k](v) / sum_i w_i(v) over the windows i that cover

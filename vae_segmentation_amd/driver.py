@@ -215,7 +215,7 @@ def save_checkpoint(prefix, epoch_label, model, optimizer, best):
 # ----------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_dir=None, epoch=0, surface=False, surface_log=None, closing=0,
-             fill_holes=False):
+             fill_holes=False, lesion=False, lesion_log=None):
     """main_source.py:688-822 / main_target.py:754-805: batch-1 forwards and hard Dice per case.  Forward only (no autograd graph is recorded: nothing is kept
     for a backward pass — the per-(n, c) statistics the conv epilogues accumulate are the FORWARD's own, the next layer normalises with them).
     keep_largest = k > 0: the hard prediction is cleaned up first as utils/utils.py:776-796 (predict_vol step 2) does — per foreground channel only the k largest
@@ -227,8 +227,13 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
     the filtered one when the filter is on, the unfiltered values are then reported beside them — against the label for every foreground class; their nanmean and
     the number of undefined (empty-surface) entries are printed, the per-case values go to the dict surface_log.  The returned scores are not affected.
     closing (--val_closing N) / fill_holes (--val_fill_holes): evaluation.postprocess runs in the filter's place — per foreground class a binary closing of N
-    iterations (26-neighbourhood), then hole filling (6-connectivity), then the component filter if it is on; everything said of the filter above holds for it."""
+    iterations (26-neighbourhood), then hole filling (6-connectivity), then the component filter if it is on; everything said of the filter above holds for it.
+    lesion (--val_lesion): additionally, for the hard prediction after whatever clean-up is on, the lesion-wise detection record of every foreground class
+    (evaluation.lesion_metrics: 26-connected components, min_size = min_component) and the per-class scores of the confusion matrix
+    (evaluation.confusion) — on the device, brought to the host once after the last case; the per-case values go to the dict lesion_log
+    (LESION_LOG_FIELDS).  The returned scores are not affected, and with lesion False nothing of this is launched."""
     from .evaluation import postprocess
+    les = {}
     post = keep_largest > 0 or closing > 0 or fill_holes
     scores, raw = {}, {}
     surf, surf_raw = {}, {}
@@ -262,6 +267,11 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
                 surf_raw[i] = ops.surface_distances(hard[:, lo:], gt[:, lo:])
                 hard = filtered
             surf[i] = ops.surface_distances(hard[:, lo:], gt[:, lo:])
+        if lesion and method != "discriminator_train":
+            from .evaluation import confusion, lesion_metrics
+            hard = filtered if filtered is not None else ops.hard_onehot(pred)
+            les[i] = (lesion_metrics(hard[:, lo:], gt[:, lo:], connectivity=26, min_size=int(min_component)),
+                      confusion(hard.argmax(1, keepdim=True), gt.argmax(1, keepdim=True), nc))
         if save_dir is not None:
             from .evaluation import binarize
             stem = os.path.join(save_dir, "%d_%d_" % (epoch, i))
@@ -293,7 +303,27 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
                     entry = surface_log.setdefault(i, {})
                     entry["assd" + suffix] = [float(v) for v in a[row]]
                     entry["hd95" + suffix] = [float(v) for v in h[row]]
+    if les and lesion_log is not None:
+        from .evaluation import LESION_RECORD_FIELDS, lesion_record_to_host
+        for i in sorted(les):
+            rec, conf = les[i]
+            entry = {k: v[0] for k, v in lesion_record_to_host(rec).items()}                  # batch 1: lists over the foreground classes
+            assert tuple(entry) == LESION_RECORD_FIELDS
+            for name in CONFUSION_LOG_FIELDS:
+                entry[name] = conf[name.replace("class_", "")][0, 0].cpu().tolist()            # over all classes, background first
+            entry["confusion_overflow"] = int(conf["overflow"][0, 0])
+            lesion_log[i] = entry
+        tp, n_gt = (sum(sum(lesion_log[i][k]) for i in lesion_log) for k in ("tp", "n_gt"))
+        fp = sum(sum(lesion_log[i]["fp"]) for i in lesion_log)
+        print("validation lesions: %d of %d reference lesions detected, %d false detections (components of at least %d voxels)"
+              % (tp, n_gt, fp, max(int(min_component), 1)))
     return scores
+
+
+# lesion_<epoch>.json, per case: evaluation.LESION_RECORD_FIELDS as lists over the foreground classes, then the voxel-wise scores of evaluation.confusion as
+# lists over ALL classes (its sensitivity / precision under a class_ prefix: the record has lesion-wise ones of the same name) and its overflow count
+CONFUSION_LOG_FIELDS = ("dice", "iou", "class_sensitivity", "class_precision")
+LESION_LOG_FIELDS = ("n_gt", "n_pred", "tp", "fn", "fp", "sensitivity", "precision", "f1", "overflow") + CONFUSION_LOG_FIELDS + ("confusion_overflow",)
 
 
 def validate_finetune(runner, loader):
@@ -432,6 +462,18 @@ def check_fine_whole_flags(a, script="main_source.py"):
         need(getattr(a, "val_fine_whole", False), "--save_whole_pred writes the labels that --val_fine_whole pastes: it needs --val_fine_whole")
 
 
+def check_lesion_flags(a, script="main_source.py"):
+    """--val_lesion scores the objects of the prediction validation already makes: it needs a validation pass that makes one"""
+    def need(cond, what):
+        if not cond:
+            raise SystemExit("%s: inconsistent flags — %s" % (script, what))
+    if not getattr(a, "val_lesion", False):
+        return
+    need(a.method != "discriminator_train", "--val_lesion scores a segmentation, --method discriminator_train predicts none")
+    need(not getattr(a, "val_finetune", 0), "--val_lesion rides on the plain validation pass: it cannot be combined with --val_finetune")
+    need(getattr(a, "val_min_component", 0) >= 0, "--val_min_component is a number of voxels: it cannot be negative")
+
+
 def check_whole_volume_flags(a, script="main_source.py"):
     """--val_whole_volume reads whole cases from disk and needs a segmentation network; --val_tta augments its sliding-window passes;
     --val_closing counts iterations"""
@@ -460,6 +502,7 @@ def check_whole_volume_flags(a, script="main_source.py"):
 def run(args, side="source"):
     check_fine_whole_flags(args, "main_%s.py" % side)
     check_whole_volume_flags(args, "main_%s.py" % side)
+    check_lesion_flags(args, "main_%s.py" % side)
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if not torch.cuda.is_available():
         raise SystemExit("the native kernels need a GPU (there is no CPU path)")
@@ -774,6 +817,7 @@ def run(args, side="source"):
         if rank == 0:
             model.eval()
             surface_log = {}                                                       # --val_surface: per-case ASSD / HD95, filled by validate
+            lesion_log = {}                                                        # --val_lesion: per-case lesion records and confusion scores
             if runner is not None and (epoch != 0 or args.test_only):             # main_target.py:811
                 scores, scores_noft = validate_finetune(runner, val_loader)
                 print("epoch %d validation result without finetuning: %f" % (epoch + 1, float(np.mean(list(scores_noft.values())))))
@@ -782,7 +826,8 @@ def run(args, side="source"):
                 scores = validate(method, model, val_loader, nc, keep_largest=getattr(args, "val_keep_largest", 0),
                                   min_component=getattr(args, "val_min_component", 0), save_dir=save_dir, epoch=epoch,
                                   surface=bool(getattr(args, "val_surface", False)), surface_log=surface_log,
-                                  closing=getattr(args, "val_closing", 0), fill_holes=bool(getattr(args, "val_fill_holes", False)))
+                                  closing=getattr(args, "val_closing", 0), fill_holes=bool(getattr(args, "val_fill_holes", False)),
+                                  lesion=bool(getattr(args, "val_lesion", False)), lesion_log=lesion_log)
             mean = float(np.mean(list(scores.values()))) if scores else 0.0
             os.makedirs(os.path.join("tensorboard", args.prefix), exist_ok=True)
             with open(os.path.join("tensorboard", args.prefix, "score_%d.json" % epoch), "w") as f:
@@ -790,6 +835,9 @@ def run(args, side="source"):
             if surface_log:
                 with open(os.path.join("tensorboard", args.prefix, "surface_%d.json" % epoch), "w") as f:
                     json.dump(surface_log, f)
+            if lesion_log:
+                with open(os.path.join("tensorboard", args.prefix, "lesion_%d.json" % epoch), "w") as f:
+                    json.dump(lesion_log, f)
             if getattr(args, "val_whole_volume", False):                           # after validation, which it leaves as it is
                 whole_log = {}
                 validate_whole_volume(model, val_loader.whole_cases(), nc, args.size, overlap=args.sw_overlap, batch=args.sw_batch, blend=args.sw_blend,
@@ -873,6 +921,10 @@ def add_native_flags(parser):
                    "background voxels change class; recorded as \"fill_holes\"")
     g.add_argument("--val_surface", action="store_true", help="validation: also report ASSD and HD95 (medpy's convention, in voxels) of the hard prediction against "
                    "the label per foreground class, computed on the device; per-case values go to tensorboard/<prefix>/surface_<epoch>.json")
+    g.add_argument("--val_lesion", action="store_true", help="validation: also report lesion-wise detection — per foreground class the 26-connected components of "
+                   "the hard prediction (after --val_closing / --val_fill_holes / --val_keep_largest) against those of the label: lesions found and missed, false "
+                   "detections, sensitivity, precision, F1 — and per-class Dice, IoU, sensitivity and precision from the confusion matrix, computed on the "
+                   "device; --val_min_component drops smaller components from both sides; per-case values go to tensorboard/<prefix>/lesion_<epoch>.json")
     g.add_argument("--val_whole_volume", action="store_true", help="validation (with --real_data): additionally predict every WHOLE validation case by sliding window "
                    "with the segmentation network (windows of --size) and report dice_whole — hard Dice against the whole label — and dice_label_free — the fine "
                    "pass on a crop chosen by the prediction's box instead of the label's; per-case values go to tensorboard/<prefix>/whole_<epoch>.json")

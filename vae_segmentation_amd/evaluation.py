@@ -133,6 +133,132 @@ def hd95(A, B, spacing=None, connectivity=6):
 
 
 # ----------------------------------------------------------------------------------------------------
+# the objects of a label: per-component measurements, the class confusion matrix and lesion-wise detection scores on the device
+# (csrc/regions.hip).  The reference has no counterpart; tests/regions_util.py restates the definitions with scipy.ndimage and numpy.
+# ----------------------------------------------------------------------------------------------------
+LESION_RECORD_FIELDS = ("n_gt", "n_pred", "tp", "fn", "fp", "sensitivity", "precision", "f1", "overflow")
+LESION_TABLE_ROWS = 2047          # components per side the lesion table can hold: (rows + 1)^2 <= 2^22 (ops.contingency)
+
+
+def _spacing3(spacing, what):
+    if spacing is None:
+        return None
+    try:
+        vals = tuple(float(s) for s in spacing)
+    except (TypeError, ValueError):
+        vals = ()
+    if len(vals) != 3 or not all(v > 0 and v < float("inf") for v in vals):
+        raise ValueError("%s: spacing is (sz, sy, sx), positive and finite, got %r" % (what, spacing))
+    return vals
+
+
+def _components(X, connectivity, what):
+    """(labels int32, sizes int32 (N, C, maxk)) of the binarised mask's components"""
+    ops._check_connectivity(connectivity, what)
+    labels, _, sizes = ops.cc_label(X.detach(), connectivity=connectivity)
+    return labels, sizes
+
+
+def region_props(mask, spacing=None, connectivity=26, max_components=4096):
+    """The connected components of the binarised (>= 0.5) mask — (D, H, W), or per plane of a planar (N, C, D, H, W) tensor — and their measurements:
+    ops.cc_label -> ops.region_props, on the device, no host copy.  -> the dict of ops.region_props for the components 1..max_components in
+    scipy.ndimage.label's numbering ("count", "bbox", "centroid", "sums", "overflow": voxels of components beyond max_components) plus
+    "volume" fp64 = count x sz x sy x sx (voxels without a spacing), "n_components" int32 and "labels" int32, the label volume.  With
+    spacing = (sz, sy, sx) the centroid is in the spacing's unit (index x spacing), otherwise in voxels; NaN for a component that does not exist."""
+    sp = _spacing3(spacing, "region_props")
+    ops._rows(max_components, "region_props: max_components", 1)
+    x, single = _planar(mask)
+    ops._check_connectivity(connectivity, "region_props")
+    labels, counts, _ = ops.cc_label(x.detach(), connectivity=connectivity)
+    out = ops.region_props(labels, max_components=max_components)
+    unit = 1.0
+    if sp is not None:
+        out["centroid"] = out["centroid"] * torch.tensor(sp, dtype=torch.float64, device=labels.device)
+        unit = sp[0] * sp[1] * sp[2]
+    out["volume"] = out["count"].double() * unit
+    out["n_components"], out["labels"] = counts, labels
+    return {k: v[0, 0] for k, v in out.items()} if single else out
+
+
+def _ratio(num, den, other):
+    """num / den in fp64; where den is 0 (num is then 0 too): 1.0 if the other side is empty as well, else 0.0"""
+    safe = torch.where(den == 0, torch.ones_like(den), den)
+    return torch.where(den == 0, (other == 0).double(), num.double() / safe.double())
+
+
+def _label_map(X, what):
+    x, single = _planar(X)
+    if x.is_floating_point() or x.dtype == torch.bool:
+        if x.dtype == torch.bool:
+            raise TypeError("%s: label maps hold integers, got a bool tensor" % what)
+        x = x.round()
+    return x.detach().to(torch.int32).contiguous(), single
+
+
+def confusion(pred_label, gt_label, n_class):
+    """The confusion matrix of two label maps with classes 0..n_class-1 — (D, H, W), or per plane of (N, C, D, H, W); any integer dtype, or floats
+    holding integers — from ONE read of both (ops.contingency), and the per-class scores derived from it on the device.
+    -> {"table": int64 (..., n_class, n_class), table[i, j] = voxels predicted i with label j; "dice", "iou", "sensitivity", "precision": fp64
+        (..., n_class); "overflow": int32, voxels whose class is outside [0, n_class) on either side (in no cell)}.
+    With tp = table[k, k], p = the row sum (predicted k) and g = the column sum (labelled k): dice = 2 tp / (p + g), iou = tp / (p + g - tp),
+    sensitivity = tp / g, precision = tp / p.  A class that is empty on both sides scores 1.0 everywhere; sensitivity of a class nobody labelled but
+    somebody predicted — and precision the other way round — is 0.0."""
+    k = ops._rows(n_class, "confusion: n_class", 1)
+    a, single = _label_map(pred_label, "confusion")
+    b, _ = _label_map(gt_label, "confusion")
+    table, overflow = ops.contingency(a, b, k - 1, k - 1)
+    tp = torch.diagonal(table, dim1=-2, dim2=-1)
+    p, g = table.sum(-1), table.sum(-2)
+    out = {"table": table, "dice": _ratio(2 * tp, p + g, p + g), "iou": _ratio(tp, p + g - tp, p + g), "sensitivity": _ratio(tp, g, p),
+           "precision": _ratio(tp, p, g), "overflow": overflow}
+    return {k_: v[0, 0] for k_, v in out.items()} if single else out
+
+
+def lesion_metrics(pred, gt, connectivity=26, min_overlap=1, min_size=0, max_components=4096):
+    """Lesion-wise detection scores of the binarised (>= 0.5) masks pred against gt — (D, H, W), or per plane of (N, C, D, H, W) — on the device, without
+    a synchronisation.  P = ops.cc_label(pred), G = ops.cc_label(gt); components of fewer than min_size voxels are dropped from both sides;
+    T = ops.contingency(P, G).  Reference lesion j is DETECTED iff it shares at least min_overlap voxels with the predicted components together
+    (sum_i T[i, j] >= min_overlap, i >= 1); predicted component i is a FALSE POSITIVE iff it shares no voxel with any reference lesion.
+    -> a dict over LESION_RECORD_FIELDS of (N, C) device tensors (0-d for a single volume): n_gt, n_pred (components that remain), tp (detected lesions),
+    fn = n_gt - tp, fp — int64; sensitivity = tp / n_gt, precision = (n_pred - fp) / n_pred, f1 = 2 tp / (2 tp + fp + fn) — fp64, a ratio with
+    denominator 0 being 1.0 when the other side is empty too and 0.0 otherwise; overflow — int32, voxels of components numbered above
+    min(max_components, 2047), the most the table holds per side: the record is then not valid, and lesion_record_to_host raises."""
+    ops._check_connectivity(connectivity, "lesion_metrics")
+    ops._rows(max_components, "lesion_metrics: max_components", 1)
+    ops._rows(min_overlap, "lesion_metrics: min_overlap", 1)
+    ops._rows(min_size, "lesion_metrics: min_size", 0)
+    a, single = _planar(pred)
+    b, _ = _planar(gt)
+    if a.shape != b.shape:
+        raise ValueError("lesion_metrics: the two masks differ in shape: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+    P, sizes_p = _components(a, connectivity, "lesion_metrics")
+    G, sizes_g = _components(b, connectivity, "lesion_metrics")
+    rows = min(max_components, LESION_TABLE_ROWS, sizes_p.shape[-1])
+    table, overflow = ops.contingency(P, G, rows, rows)
+    least = max(min_size, 1)
+    keep_p, keep_g = sizes_p[..., :rows] >= least, sizes_g[..., :rows] >= least            # a dropped component: its row / column is not looked at
+    shared = table[..., 1:, 1:] * (keep_p.unsqueeze(-1) & keep_g.unsqueeze(-2))
+    n_pred, n_gt = keep_p.sum(-1), keep_g.sum(-1)
+    tp = (shared.sum(-2) >= min_overlap).sum(-1)
+    fp = (keep_p & (shared.sum(-1) == 0)).sum(-1)
+    fn = n_gt - tp
+    out = {"n_gt": n_gt, "n_pred": n_pred, "tp": tp, "fn": fn, "fp": fp, "sensitivity": _ratio(tp, n_gt, n_pred),
+           "precision": _ratio(n_pred - fp, n_pred, n_gt), "f1": _ratio(2 * tp, 2 * tp + fp + fn, n_gt + n_pred), "overflow": overflow}
+    assert tuple(out) == LESION_RECORD_FIELDS
+    return {k: v[0, 0] for k, v in out.items()} if single else out
+
+
+def lesion_record_to_host(record):
+    """a lesion_metrics record as nested Python lists (numbers for a single volume), one host copy per field; RuntimeError when a plane had more
+    components than the table holds (overflow != 0): its counts would be wrong"""
+    host = {k: record[k].cpu() for k in LESION_RECORD_FIELDS}
+    if bool((host["overflow"] != 0).any()):
+        raise RuntimeError("lesion_metrics: %d voxels belong to components beyond the table's rows: the record is not valid (max_components counts "
+                           "components before the min_size filter, at most %d per side)" % (int(host["overflow"].sum()), LESION_TABLE_ROWS))
+    return {k: v.tolist() for k, v in host.items()}
+
+
+# ----------------------------------------------------------------------------------------------------
 # binary morphology and hole filling on the device (csrc/morph.hip): scipy.ndimage's operators without the host detour
 # ----------------------------------------------------------------------------------------------------
 def _morph(name, X, **kw):

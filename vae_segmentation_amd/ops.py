@@ -10,6 +10,7 @@ For autograd, ``stats`` is a non-differentiable side output and the gradient att
 total derivative (the InstanceNorm+ReLU backward is applied by the consumer's backward).
 """
 import ctypes as _ctypes
+import numbers as _numbers
 import os
 import weakref as _weakref
 
@@ -2583,6 +2584,69 @@ def fill_holes(mask, connectivity=6):
     out = torch.empty_like(m)
     check(lib.vs_fill_holes(m.data_ptr(), out.data_ptr(), n, c, d, h, w, connectivity, ws.data_ptr(), _stream()), "fill_holes")
     return out
+
+
+# per-component measurements and contingency tables of label volumes (csrc/regions.hip).  No workspace: the outputs are the only buffers, and the
+# kernels write their initial state themselves.
+REGION_COLUMNS = ("count", "zmin", "ymin", "xmin", "zmax", "ymax", "xmax", "sum_z", "sum_y", "sum_x")      # vs_region_props
+CONTINGENCY_MAX_CELLS = 1 << 22                                                                            # (rows_a + 1) * (rows_b + 1) per plane
+
+
+def _rows(value, what, least):
+    if isinstance(value, bool) or not isinstance(value, _numbers.Integral) or value < least or value > 2 ** 31 - 2:
+        raise ValueError("%s is an integer >= %d, got %r" % (what, least, value))
+    return int(value)
+
+
+def _label_volume(t, what):
+    """every check that needs no device; the tensor is used as it is — a label volume is never converted or copied behind the caller's back"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+        raise TypeError("%s: label volumes are int32 tensors (ops.cc_label's labels), got %s" % (what, getattr(t, "dtype", type(t))))
+    if t.dim() != 5:
+        raise ValueError("%s: expected a planar (N, C, D, H, W) label volume, got shape %s" % (what, tuple(t.shape)))
+    if t.numel() == 0 or t.shape[2] * t.shape[3] * t.shape[4] >= 2 ** 31:
+        raise ValueError("%s: an empty volume or a plane of 2^31 voxels or more, shape %s" % (what, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: the label volume must be contiguous" % what)
+
+
+def region_props(labels, max_components=4096):
+    """Per-label measurements of every (n, c) plane of an int32 label volume (N, C, D, H, W) — 0 background, 1..K components, as ops.cc_label
+    numbers them — for the labels 1..R, R = max_components; what scipy.ndimage.find_objects, np.bincount and center_of_mass give on the host.
+    -> {"count": int64 (N, C, R) voxels; "bbox": int32 (N, C, R, 6) = (zmin, ymin, xmin, zmax, ymax, xmax), inclusive;
+        "centroid": fp64 (N, C, R, 3) = (z, y, x) in voxels, sum / count; "sums": int64 (N, C, R, 3) the coordinate sums behind it;
+        "overflow": int32 (N, C) voxels whose label is negative or above R — counted there and nowhere else}.
+    A label that does not occur has count 0, box mins (D, H, W) and maxes -1, centroid NaN.  Two launches, no synchronisation."""
+    r = _rows(max_components, "region_props: max_components", 1)
+    _label_volume(labels, "region_props")
+    _require_cuda(labels)
+    n, c, d, h, w = labels.shape
+    table = torch.empty((n, c, r, len(REGION_COLUMNS)), dtype=torch.int64, device=labels.device)
+    overflow = torch.empty((n, c), dtype=torch.int32, device=labels.device)
+    check(lib.vs_region_props(labels.data_ptr(), n, c, d, h, w, r, table.data_ptr(), overflow.data_ptr(), _stream()), "region_props")
+    count, sums = table[..., 0], table[..., 7:10]
+    return {"count": count, "bbox": table[..., 1:7].to(torch.int32), "centroid": sums.double() / count.double().unsqueeze(-1), "sums": sums,
+            "overflow": overflow}
+
+
+def contingency(a, b, rows_a, rows_b):
+    """The contingency table of two int32 label volumes of one shape (N, C, D, H, W), per (n, c) plane:
+    -> table int64 (N, C, rows_a + 1, rows_b + 1), table[..., i, j] = voxels with a == i and b == j (row / column 0: background), and
+    overflow int32 (N, C): voxels with a label outside [0, rows_a] / [0, rows_b] on either side — counted there and in no cell.
+    (rows_a + 1) * (rows_b + 1) <= 2^22.  Two launches, no synchronisation; np.bincount(a * (rows_b + 1) + b) without the host."""
+    ra, rb = _rows(rows_a, "contingency: rows_a", 0), _rows(rows_b, "contingency: rows_b", 0)
+    if (ra + 1) * (rb + 1) > CONTINGENCY_MAX_CELLS:
+        raise ValueError("contingency: (rows_a + 1) * (rows_b + 1) = %d cells per plane, at most 2^22" % ((ra + 1) * (rb + 1)))
+    _label_volume(a, "contingency")
+    _label_volume(b, "contingency")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("contingency: the two label volumes differ in shape or device: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+    _require_cuda(a, b)
+    n, c, d, h, w = a.shape
+    table = torch.empty((n, c, ra + 1, rb + 1), dtype=torch.int64, device=a.device)
+    overflow = torch.empty((n, c), dtype=torch.int32, device=a.device)
+    check(lib.vs_contingency(a.data_ptr(), b.data_ptr(), n, c, d, h, w, ra, rb, table.data_ptr(), overflow.data_ptr(), _stream()), "contingency")
+    return table, overflow
 
 
 # sliding-window prediction (csrc/window.hip).  evaluation.sliding_window_predict drives these; nothing here synchronises.
