@@ -199,6 +199,7 @@ typedef struct vs_config {
     int wgrad_xcd;             /* VS_WGRAD_XCD 2: a layer's workgroups re-ranked so that one XCD walks neighbouring tiles and holds all channel-block pairs of a tile (1: single-pair layers only; 0: plain order) */
     int k3_short_tiles;        /* VS_K3_SHORT_TILES 2: 4x2x16 tiles for the 32-channel 3x3x3 launches of at most 128 workgroups (the 12^3-class levels), 4x1x16 where that still leaves at most 128 (2); 1: 4x2x16 only; 0: off */
     int wgrad_bias_fold;       /* VS_WGRAD_BIAS_FOLD 1: a ConvTranspose3d's bias gradient is summed by its weight-gradient workgroups (the same tensor is their Q operand) */
+    int hist_form;             /* VS_HIST_FORM 0: the counting kernel of vs_histogram / vs_joint_histogram is chosen by table size; 1 / 2 / 3 force the 32-bit LDS, the packed 16-bit LDS or the global-atomic form where the table fits it (A/B measurements; the tables are the same) */
     long long wgrad_wgs;            /* VS_WGRAD_WGS 512: workgroups per ungrouped weight-gradient launch */
     long long wgrad_f32_tiles;      /* VS_WGRAD_F32_TILES 8 */
     long long wgrad_group_wgs;      /* VS_WGRAD_GROUP_WGS 0: workgroups per bucket of a grouped pass (0 = chosen per pass) */
@@ -573,6 +574,50 @@ int vs_fill_holes(const float* mask, float* out, int n, int c, int d, int h, int
 int vs_region_props(const int* labels, int n, int c, int d, int h, int w, int max_rows, long long* table, int* overflow, void* stream);
 int vs_contingency(const int* a, const int* b, int n, int c, int d, int h, int w, int rows_a, int rows_b, long long* table, int* overflow,
                    void* stream);
+
+/* ---- intensity histograms, joint histograms and mutual information (csrc/hist.hip) -------------------------------------------------------
+ * np.histogram / np.histogram2d of volumes and the tail of the reference's mutual_information_3d (utils/utils.py:804-845) without the host.  x, y:
+ * planar fp32 (n, c, d, h, w), contiguous; every (n, c) plane is its own problem; any d, h, w >= 1 with d*h*w < 2^31.  Counts are int64.
+ * The binning rule (it does not follow numpy's dtype rules):
+ *   edges     for bins = B >= 1 and bounds lo <= hi the B + 1 edges are the fp64 values with the bits of np.linspace(lo, hi, B + 1):
+ *             step = (hi - lo) / B, e_i = i * step + lo with the product and the sum rounded separately (no fused multiply-add), e_B = hi.
+ *             lo == hi becomes (lo - 0.5, hi + 0.5) first.  They are written to the caller's buffer, fp64 (n, c, B + 1).
+ *   bin       a voxel x, promoted to fp64, is in bin i iff e_i <= x < e_{i+1}; x == e_B is in bin B - 1.  The kernels estimate the bin as
+ *             (x - e_0) * B / (e_B - e_0) and then walk the edge table until that inequality holds.
+ *   outside   int64 (n, c): NaN, +-inf and values outside [e_0, e_B] are counted there and in no bin.
+ *   bounds    from_data == 0: the host doubles given, for all planes (not finite or lo > hi: VS_EINVAL).  from_data != 0: per plane, on the device
+ *             and without a synchronisation, lo / hi = the minimum / maximum over the plane's FINITE voxels (a zero bound is +0.0); a plane
+ *             without a finite voxel gets (0, 0), hence (-0.5, 0.5).  The running extrema live in the plane's own edge table until it is written.
+ *   vs_histogram        table: int64 (n, c, rows + 1, bins).  labels == NULL: rows is 0, one row.  Otherwise labels is an int32 volume of x's shape
+ *                       as vs_cc_label or an argmax writes it and row r is the histogram of the voxels labelled r; voxels whose label is negative or
+ *                       above rows are counted in overflow, int32 (n, c), and nowhere else (vs_contingency's rule).  bins <= 4096 and
+ *                       (rows + 1) * bins <= 2^22, VS_ESHAPE beyond.  lo, hi: the host bounds.
+ *   vs_joint_histogram  table: int64 (n, c, bins_x, bins_y); a voxel counts in cell (bin of x, bin of y) iff both values are in range, otherwise in
+ *                       outside.  range4: host doubles (lo_x, hi_x, lo_y, hi_y), not read with from_data.  bins_x * bins_y <= 2^22.
+ * Three counting kernels, chosen by the cells of one plane's table: up to 8192 cells 32-bit counters in LDS; up to 65536 cells (256 x 256) two 16-bit
+ * counters per LDS word, 128 KB, where a workgroup flushes to the int64 table after 16384 voxels — fewer than 2^16, so no half can carry; larger tables
+ * one 64-bit global atomic per run, with the cell a wave currently sees most carried in registers.  In all of them a run of equal cells along x is one
+ * update of the run's length.  vs_config.hist_form forces a form for measurements; the tables do not depend on it.
+ *   vs_mutual_information  table: int64 (n, c, bins_x, bins_y) as vs_joint_histogram writes it -> mi: fp64 (n, c), all in fp64:
+ *                       scipy.ndimage.gaussian_filter(jh, sigma, mode="constant") — the separable kernel of radius int(4 * sigma + 0.5), weights
+ *                       exp(-k^2 / (2 sigma^2)) over their sum, along x then y, zeros beyond the table; sigma == 0 skips it — then + eps
+ *                       (2^-52), division by the total, the two marginals s1, s2 and  normalized ? (sum s1 log s1 + sum s2 log s2) / sum jh log jh - 1
+ *                       : sum jh log jh - sum s1 log s1 - sum s2 log s2.  sigma < 0, NaN or a radius above 64: VS_EINVAL; n * c <= 65535.
+ *                       workspace: n * c * (2 * bins_x * bins_y + 2 * bins_x + bins_y) doubles, contents undefined on entry.  Every sum runs in a
+ *                       fixed order (strided partials, then a tree per workgroup), there are no floating-point atomics: the same bits on every
+ *                       run, in both builds and under graph replay.
+ * The caller owns every buffer and need not clear them: the first launch of a call writes the initial state.  Nothing is allocated, synchronised or
+ * read back, no kernel waits for another workgroup, every call can be captured in a HIP graph (3 launches with host bounds, 4 from the data; 4 or 5
+ * for the mutual information).  Every count is an integer added with vector-lane atomics, so the tables do not depend on the order of arrival:
+ * both builds of the library and every run give the same bits.  A null pointer, bins < 1, rows < 0 (or != 0 without labels), edges_x == edges_y:
+ * VS_EINVAL; an empty or too large shape or table: VS_ESHAPE; x, y, labels, overflow not 4-byte, the other buffers not 8-byte aligned: VS_EALIGN;
+ * all answered on the host before any launch. */
+int vs_histogram(const float* x, const int* labels, int n, int c, int d, int h, int w, int bins, int rows, double lo, double hi, int from_data,
+                 double* edges, long long* table, long long* outside, int* overflow, void* stream);
+int vs_joint_histogram(const float* x, const float* y, int n, int c, int d, int h, int w, int bins_x, int bins_y, const double* range4, int from_data,
+                       double* edges_x, double* edges_y, long long* table, long long* outside, void* stream);
+int vs_mutual_information(const long long* table, int n, int c, int bins_x, int bins_y, double sigma, int normalized, double* workspace, double* mi,
+                          void* stream);
 
 /* ---- sliding-window prediction of a whole volume (csrc/window.hip; no counterpart in the reference) -------------------------------
  * A volume (C, D, H, W) is tiled with overlapping cubic windows of side `patch`, a network maps batches (B, C, P, P, P) of them to planar

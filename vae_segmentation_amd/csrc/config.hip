@@ -39,6 +39,7 @@ extern "C" int vs_config_from_env(vs_config* c) {
     c->wgrad_xcd = env_int("VS_WGRAD_XCD", 2);
     c->k3_short_tiles = env_int("VS_K3_SHORT_TILES", 2);
     c->wgrad_bias_fold = env_int("VS_WGRAD_BIAS_FOLD", 1);
+    c->hist_form = env_int("VS_HIST_FORM", 0);
     c->wgrad_wgs = env_ll("VS_WGRAD_WGS", 512);
     c->wgrad_f32_tiles = env_ll("VS_WGRAD_F32_TILES", 8);
     c->wgrad_group_wgs = env_ll("VS_WGRAD_GROUP_WGS", 0);
@@ -65,7 +66,7 @@ extern "C" int vs_set_config(const vs_config* in) {
     if (!in) return VS_EINVAL;
     if (in->k3x_ck != 8 && in->k3x_ck != 16) return VS_EINVAL;
     if (in->k3_wgs_per_cu < 0 || in->k3t_wgs_per_cu < 1 || in->k2s8_wgs_per_cu < 1 || in->up_wgs_per_cu < 1 || in->wgrad_wgs < 1 || in->wgrad_f32_tiles < 1 ||
-        in->wgrad_group_wgs < 0 || in->wgrad_big_min_voxels < 0 || in->mt_min_wgs < 0 || in->k3f_min_wgs < 0) return VS_EINVAL;
+        in->wgrad_group_wgs < 0 || in->wgrad_big_min_voxels < 0 || in->mt_min_wgs < 0 || in->k3f_min_wgs < 0 || in->hist_form < 0 || in->hist_form > 3) return VS_EINVAL;
     vs_cfg();                                            // the environment is read first, never after a set
     std::lock_guard<std::mutex> lock(g_cfg_mutex);
     g_cfg = *in;

@@ -215,7 +215,7 @@ def save_checkpoint(prefix, epoch_label, model, optimizer, best):
 # ----------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_dir=None, epoch=0, surface=False, surface_log=None, closing=0,
-             fill_holes=False, lesion=False, lesion_log=None):
+             fill_holes=False, lesion=False, lesion_log=None, intensity=0, intensity_log=None):
     """main_source.py:688-822 / main_target.py:754-805: batch-1 forwards and hard Dice per case.  Forward only (no autograd graph is recorded: nothing is kept
     for a backward pass — the per-(n, c) statistics the conv epilogues accumulate are the FORWARD's own, the next layer normalises with them).
     keep_largest = k > 0: the hard prediction is cleaned up first as utils/utils.py:776-796 (predict_vol step 2) does — per foreground channel only the k largest
@@ -231,9 +231,15 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
     lesion (--val_lesion): additionally, for the hard prediction after whatever clean-up is on, the lesion-wise detection record of every foreground class
     (evaluation.lesion_metrics: 26-connected components, min_size = min_component) and the per-class scores of the confusion matrix
     (evaluation.confusion) — on the device, brought to the host once after the last case; the per-case values go to the dict lesion_log
-    (LESION_LOG_FIELDS).  The returned scores are not affected, and with lesion False nothing of this is launched."""
+    (LESION_LOG_FIELDS).  The returned scores are not affected, and with lesion False nothing of this is launched.
+    intensity (--val_intensity BINS) > 0: additionally, per case, the histogram (BINS bins over INTENSITY_RANGE, what Clip and CenterIntensities leave) of
+    the network's input image inside every foreground class of the hard prediction — after whatever clean-up is on — and inside every foreground class of
+    the label (ops.histogram with the class map as labels: one pass over the image per side), and the normalised mutual information of every foreground
+    probability with its label channel (evaluation.mutual_information_3d) — on the device, brought to the host once after the last case; the per-case
+    values go to the dict intensity_log (INTENSITY_LOG_FIELDS).  The returned scores are not affected, and with intensity 0 nothing of this is launched."""
     from .evaluation import postprocess
     les = {}
+    inten = {}
     post = keep_largest > 0 or closing > 0 or fill_holes
     scores, raw = {}, {}
     surf, surf_raw = {}, {}
@@ -272,6 +278,16 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
             hard = filtered if filtered is not None else ops.hard_onehot(pred)
             les[i] = (lesion_metrics(hard[:, lo:], gt[:, lo:], connectivity=26, min_size=int(min_component)),
                       confusion(hard.argmax(1, keepdim=True), gt.argmax(1, keepdim=True), nc))
+        if intensity > 0 and method != "discriminator_train":
+            from .evaluation import mutual_information_3d
+            hard = filtered if filtered is not None else ops.hard_onehot(pred)
+            image = batch[IMG_KEY].cuda(non_blocking=True).float()[:, :1].contiguous()
+            sides = {}
+            for name, hot in (("pred", hard), ("label", gt)):
+                rec = ops.histogram(image, int(intensity), range=INTENSITY_RANGE, labels=hot.argmax(1, keepdim=True).to(torch.int32), rows=nc - 1)
+                sides[name] = (rec["table"][:, 0, lo:], rec["outside"][:, 0], hot[:, lo:].sum((2, 3, 4)))
+            nmi = torch.stack([mutual_information_3d(pred[:, k], gt[:, k]) for k in range(lo, nc)])
+            inten[i] = (sides, nmi)
         if save_dir is not None:
             from .evaluation import binarize
             stem = os.path.join(save_dir, "%d_%d_" % (epoch, i))
@@ -317,7 +333,28 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
         fp = sum(sum(lesion_log[i]["fp"]) for i in lesion_log)
         print("validation lesions: %d of %d reference lesions detected, %d false detections (components of at least %d voxels)"
               % (tp, n_gt, fp, max(int(min_component), 1)))
+    if inten and intensity_log is not None:
+        for i in sorted(inten):
+            sides, nmi = inten[i]
+            entry = {"bins": int(intensity), "range": list(INTENSITY_RANGE)}
+            for name in ("pred", "label"):                                                     # batch 1: lists over the foreground classes
+                table, outside, voxels = sides[name]
+                entry[name + "_hist"] = table[0].cpu().tolist()
+                entry[name + "_voxels"] = [int(v) for v in voxels[0].cpu().tolist()]
+                entry[name + "_outside"] = int(outside[0])
+            entry["nmi"] = [float(v) for v in nmi.cpu().tolist()]
+            assert tuple(entry) == INTENSITY_LOG_FIELDS
+            intensity_log[i] = entry
+        print("validation intensities: %d-bin histograms of the image inside prediction and label, mean normalised mutual information of probability and "
+              "label %f" % (int(intensity), float(np.mean([np.mean(intensity_log[i]["nmi"]) for i in intensity_log]))))
     return scores
+
+
+# intensity_<epoch>.json, per case: the image's histogram inside every foreground class of the hard prediction and of the label (lists over the foreground
+# classes, then over the bins), the voxels of those classes (the histograms sum to them when nothing is outside the range), the image voxels of the whole
+# case outside the range, and the normalised mutual information of every foreground probability with its label channel
+INTENSITY_RANGE = (-1.0, 1.0)                       # Clip(-200, 400) then CenterIntensities(100, 300)
+INTENSITY_LOG_FIELDS = ("bins", "range", "pred_hist", "pred_voxels", "pred_outside", "label_hist", "label_voxels", "label_outside", "nmi")
 
 
 # lesion_<epoch>.json, per case: evaluation.LESION_RECORD_FIELDS as lists over the foreground classes, then the voxel-wise scores of evaluation.confusion as
@@ -474,6 +511,19 @@ def check_lesion_flags(a, script="main_source.py"):
     need(getattr(a, "val_min_component", 0) >= 0, "--val_min_component is a number of voxels: it cannot be negative")
 
 
+def check_intensity_flags(a, script="main_source.py"):
+    """--val_intensity reads the image inside the prediction validation already makes: it needs a validation pass that makes one"""
+    def need(cond, what):
+        if not cond:
+            raise SystemExit("%s: inconsistent flags — %s" % (script, what))
+    bins = getattr(a, "val_intensity", 0)
+    if not bins:
+        return
+    need(1 <= bins <= ops.HISTOGRAM_MAX_BINS, "--val_intensity is a number of bins between 1 and %d" % ops.HISTOGRAM_MAX_BINS)
+    need(a.method != "discriminator_train", "--val_intensity reads the image inside a segmentation, --method discriminator_train predicts none")
+    need(not getattr(a, "val_finetune", 0), "--val_intensity rides on the plain validation pass: it cannot be combined with --val_finetune")
+
+
 def check_whole_volume_flags(a, script="main_source.py"):
     """--val_whole_volume reads whole cases from disk and needs a segmentation network; --val_tta augments its sliding-window passes;
     --val_closing counts iterations"""
@@ -503,6 +553,7 @@ def run(args, side="source"):
     check_fine_whole_flags(args, "main_%s.py" % side)
     check_whole_volume_flags(args, "main_%s.py" % side)
     check_lesion_flags(args, "main_%s.py" % side)
+    check_intensity_flags(args, "main_%s.py" % side)
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if not torch.cuda.is_available():
         raise SystemExit("the native kernels need a GPU (there is no CPU path)")
@@ -818,6 +869,7 @@ def run(args, side="source"):
             model.eval()
             surface_log = {}                                                       # --val_surface: per-case ASSD / HD95, filled by validate
             lesion_log = {}                                                        # --val_lesion: per-case lesion records and confusion scores
+            intensity_log = {}                                                     # --val_intensity: per-case histograms and mutual information
             if runner is not None and (epoch != 0 or args.test_only):             # main_target.py:811
                 scores, scores_noft = validate_finetune(runner, val_loader)
                 print("epoch %d validation result without finetuning: %f" % (epoch + 1, float(np.mean(list(scores_noft.values())))))
@@ -827,7 +879,8 @@ def run(args, side="source"):
                                   min_component=getattr(args, "val_min_component", 0), save_dir=save_dir, epoch=epoch,
                                   surface=bool(getattr(args, "val_surface", False)), surface_log=surface_log,
                                   closing=getattr(args, "val_closing", 0), fill_holes=bool(getattr(args, "val_fill_holes", False)),
-                                  lesion=bool(getattr(args, "val_lesion", False)), lesion_log=lesion_log)
+                                  lesion=bool(getattr(args, "val_lesion", False)), lesion_log=lesion_log,
+                                  intensity=int(getattr(args, "val_intensity", 0) or 0), intensity_log=intensity_log)
             mean = float(np.mean(list(scores.values()))) if scores else 0.0
             os.makedirs(os.path.join("tensorboard", args.prefix), exist_ok=True)
             with open(os.path.join("tensorboard", args.prefix, "score_%d.json" % epoch), "w") as f:
@@ -838,6 +891,9 @@ def run(args, side="source"):
             if lesion_log:
                 with open(os.path.join("tensorboard", args.prefix, "lesion_%d.json" % epoch), "w") as f:
                     json.dump(lesion_log, f)
+            if intensity_log:
+                with open(os.path.join("tensorboard", args.prefix, "intensity_%d.json" % epoch), "w") as f:
+                    json.dump(intensity_log, f)
             if getattr(args, "val_whole_volume", False):                           # after validation, which it leaves as it is
                 whole_log = {}
                 validate_whole_volume(model, val_loader.whole_cases(), nc, args.size, overlap=args.sw_overlap, batch=args.sw_batch, blend=args.sw_blend,
@@ -925,6 +981,10 @@ def add_native_flags(parser):
                    "the hard prediction (after --val_closing / --val_fill_holes / --val_keep_largest) against those of the label: lesions found and missed, false "
                    "detections, sensitivity, precision, F1 — and per-class Dice, IoU, sensitivity and precision from the confusion matrix, computed on the "
                    "device; --val_min_component drops smaller components from both sides; per-case values go to tensorboard/<prefix>/lesion_<epoch>.json")
+    g.add_argument("--val_intensity", type=int, default=0, metavar="BINS", help="validation: also write, per case and foreground class, the BINS-bin histogram over "
+                   "[-1, 1] of the network's input image inside the hard prediction (after --val_closing / --val_fill_holes / --val_keep_largest) and inside the "
+                   "label, and the normalised mutual information of the foreground probability with the label, computed on the device, to "
+                   "tensorboard/<prefix>/intensity_<epoch>.json; 0 = off")
     g.add_argument("--val_whole_volume", action="store_true", help="validation (with --real_data): additionally predict every WHOLE validation case by sliding window "
                    "with the segmentation network (windows of --size) and report dice_whole — hard Dice against the whole label — and dice_label_free — the fine "
                    "pass on a crop chosen by the prediction's box instead of the label's; per-case values go to tensorboard/<prefix>/whole_<epoch>.json")

@@ -259,6 +259,66 @@ def lesion_record_to_host(record):
 
 
 # ----------------------------------------------------------------------------------------------------
+# the intensities of a volume: histograms, joint histograms and mutual information on the device (csrc/hist.hip).  mutual_information_3d is the
+# reference's utils/utils.py:804-845; tests/hist_util.py restates the binning rule and the formula with numpy and scipy.
+# ----------------------------------------------------------------------------------------------------
+def _intensities(X, what):
+    """(planar contiguous fp32 tensor, single): float32 is what the kernels read; other floating-point and integer dtypes are converted"""
+    if not isinstance(X, torch.Tensor) or X.dtype == torch.bool or X.is_complex():
+        raise TypeError("%s: expected a real-valued tensor, got %s" % (what, getattr(X, "dtype", type(X))))
+    x, single = _planar(X)
+    return x.detach().to(torch.float32).contiguous(), single
+
+
+def histogram(volume, bins, range=None, mask=None):
+    """The intensity histogram of a volume — (D, H, W), or per plane of (N, C, D, H, W) — on the device, optionally inside a mask (ops.histogram).
+    Edges are np.linspace(lo, hi, bins + 1) in fp64, a voxel promoted to fp64 is in bin i iff e_i <= x < e_{i+1} (the last edge belongs to the last bin);
+    range=None takes lo / hi from the finite voxels of each plane, on the device.  mask: a 0 / 1 volume of the same shape (foreground: value >= 0.5).
+    -> {"table": int64 (..., bins) — with a mask the voxels inside it, and then also "complement": the voxels where the mask is 0;
+        "edges": fp64 (..., bins + 1); "outside": int64, voxels that are NaN, +-inf or out of range (in no bin, whatever the mask says)}."""
+    x, single = _intensities(volume, "histogram")
+    lab = None
+    if mask is not None:
+        m, _ = _planar(mask)
+        if m.shape != x.shape:
+            raise ValueError("histogram: the mask's shape %s is not the volume's %s" % (tuple(mask.shape), tuple(volume.shape)))
+        lab = (m.detach() >= 0.5).to(torch.int32).contiguous()
+    rec = ops.histogram(x, bins, range=range, labels=lab, rows=0 if lab is None else 1)
+    out = {"table": rec["table"][:, :, -1], "edges": rec["edges"], "outside": rec["outside"]}
+    if lab is not None:
+        out["complement"] = rec["table"][:, :, 0]
+    return {k: v[0, 0] for k, v in out.items()} if single else out
+
+
+def joint_histogram(a, b, bins=256, range=None):
+    """The joint intensity histogram of two volumes of one shape — (D, H, W), or per plane of (N, C, D, H, W) — on the device (ops.joint_histogram):
+    np.histogram2d with histogram's binning rule per variable.  bins: an integer or (bins_a, bins_b); range: None (from the data) or
+    ((lo_a, hi_a), (lo_b, hi_b)).  -> {"table": int64 (..., bins_a, bins_b), "edges_x", "edges_y": fp64, "outside": int64}."""
+    x, single = _intensities(a, "joint_histogram")
+    y, _ = _intensities(b, "joint_histogram")
+    if x.shape != y.shape:
+        raise ValueError("joint_histogram: the two volumes differ in shape: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+    rec = ops.joint_histogram(x, y, bins=bins, range=range)
+    return {k: v[0, 0] for k, v in rec.items()} if single else rec
+
+
+def mutual_information_3d(x, y, sigma=1, normalized=True):
+    """utils/utils.py:804-845 on the device: the (normalised) mutual information of two variables from their 256 x 256 joint histogram, smoothed with a
+    Gaussian of `sigma` (scipy.ndimage.gaussian_filter, mode "constant"), Studholme's measure when normalized.
+    x, y: device tensors of any equal shape; they are flattened, as the reference takes 1-D arrays, and binned as ONE plane with bounds from the data.
+    The kernels read float32 (another dtype is converted to it first); every value is promoted to fp64 before binning, and the edges are the fp64 values
+    np.linspace(min, max, 257) — the bins numpy gives for float64 inputs.  -> a 0-d fp64 device tensor; nothing is copied to the host or synchronised."""
+    if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
+        raise TypeError("mutual_information_3d: x and y are device tensors, got %s and %s" % (type(x).__name__, type(y).__name__))
+    if x.shape != y.shape or x.numel() == 0:
+        raise ValueError("mutual_information_3d: x and y have one non-empty shape, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    a, _ = _intensities(x.reshape(1, 1, 1, 1, -1), "mutual_information_3d")
+    b, _ = _intensities(y.reshape(1, 1, 1, 1, -1), "mutual_information_3d")
+    rec = ops.joint_histogram(a, b, bins=(256, 256), range=None)
+    return ops.mutual_information(rec["table"], sigma=sigma, normalized=normalized)[0, 0]
+
+
+# ----------------------------------------------------------------------------------------------------
 # binary morphology and hole filling on the device (csrc/morph.hip): scipy.ndimage's operators without the host detour
 # ----------------------------------------------------------------------------------------------------
 def _morph(name, X, **kw):

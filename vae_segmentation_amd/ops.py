@@ -68,7 +68,7 @@ class VsConfig(_ctypes.Structure):
     """vs_config (include/vaeseg.h): the library's tuning switches"""
     _fields_ = [(n, _ctypes.c_int) for n in ("k3_small", "k3_tall", "k3_wgs_per_cu", "k3t_wgs_per_cu", "k3f_min_wgs", "mt_min_wgs", "f32_limbs", "g1_limbs", "k3x_ck",
                                             "k3x_toeplitz", "fuse_wgrad", "epilogue_apply", "chain", "k2s2_stream", "k2s8_wgs_per_cu", "up_wgs_per_cu", "up_rb",
-                                            "wgrad_uber", "wgrad_mpack", "wgrad_swap", "wgrad_big", "wgrad_xcd", "k3_short_tiles", "wgrad_bias_fold")] + \
+                                            "wgrad_uber", "wgrad_mpack", "wgrad_swap", "wgrad_big", "wgrad_xcd", "k3_short_tiles", "wgrad_bias_fold", "hist_form")] + \
                [(n, _ctypes.c_longlong) for n in ("wgrad_wgs", "wgrad_f32_tiles", "wgrad_group_wgs", "wgrad_big_min_voxels")]
 
 
@@ -2647,6 +2647,142 @@ def contingency(a, b, rows_a, rows_b):
     overflow = torch.empty((n, c), dtype=torch.int32, device=a.device)
     check(lib.vs_contingency(a.data_ptr(), b.data_ptr(), n, c, d, h, w, ra, rb, table.data_ptr(), overflow.data_ptr(), _stream()), "contingency")
     return table, overflow
+
+
+# intensity histograms, joint histograms and mutual information (csrc/hist.hip).  The outputs are the only buffers of the histogram calls; the kernels
+# write their initial state themselves.
+HISTOGRAM_MAX_BINS = 4096                      # vs_histogram
+HISTOGRAM_MAX_CELLS = 1 << 22                  # (rows + 1) * bins, bins_x * bins_y per plane
+MI_MAX_RADIUS = 64                             # int(4 * sigma + 0.5) of vs_mutual_information
+MI_MAX_PLANES = 65535
+_MI_WORKSPACES = {}
+
+
+def _bins(value, what):
+    if isinstance(value, bool) or not isinstance(value, _numbers.Integral) or value < 1:
+        raise ValueError("%s is an integer >= 1, got %r" % (what, value))
+    return int(value)
+
+
+def _intensity_volume(t, what):
+    """every check that needs no device; the tensor is used as it is — no conversion and no copy behind the caller's back"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError("%s: intensity volumes are float32 tensors, got %s" % (what, getattr(t, "dtype", type(t))))
+    if t.dim() != 5:
+        raise ValueError("%s: expected a planar (N, C, D, H, W) volume, got shape %s" % (what, tuple(t.shape)))
+    if t.numel() == 0 or t.shape[2] * t.shape[3] * t.shape[4] >= 2 ** 31:
+        raise ValueError("%s: an empty volume or a plane of 2^31 voxels or more, shape %s" % (what, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: the volume must be contiguous" % what)
+
+
+def _bounds(pair, what):
+    """(lo, hi) as two Python floats with lo <= hi, both finite"""
+    import math
+    try:
+        lo, hi = (float(v) for v in pair)
+    except (TypeError, ValueError):
+        raise ValueError("%s is a pair (lo, hi) of numbers, got %r" % (what, pair)) from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+        raise ValueError("%s needs finite bounds with lo <= hi, got %r" % (what, (lo, hi)))
+    return lo, hi
+
+
+def histogram(x, bins, range=None, labels=None, rows=0):
+    """np.histogram of every (n, c) plane of a planar fp32 volume (N, C, D, H, W) on the device, optionally one histogram per label.
+    Edges: the fp64 values np.linspace(lo, hi, bins + 1) (product and sum rounded separately; lo == hi becomes lo - 0.5, hi + 0.5).  range=(lo, hi): the
+    same host bounds for all planes; range=None: per plane the minimum and maximum over its finite voxels, found on the device ((0, 0) without any).
+    A voxel x, promoted to fp64, is in bin i iff e_i <= x < e_{i+1}; x == e_bins is in the last bin.
+    labels: an int32 volume of x's shape (ops.cc_label's labels, an argmax); row r of the table counts the voxels labelled r, 0 <= r <= rows.
+    -> {"table": int64 (N, C, rows + 1, bins); "edges": fp64 (N, C, bins + 1); "outside": int64 (N, C), NaN, +-inf and out-of-range voxels, in no bin;
+        "overflow": int32 (N, C), voxels whose label is negative or above rows — counted there and nowhere else}.
+    bins <= 4096 and (rows + 1) * bins <= 2^22.  Three or four launches, no synchronisation (vs_histogram)."""
+    b = _bins(bins, "histogram: bins")
+    r = _rows(rows, "histogram: rows", 0)
+    if b > HISTOGRAM_MAX_BINS or (r + 1) * b > HISTOGRAM_MAX_CELLS:
+        raise ValueError("histogram: bins = %d, (rows + 1) * bins = %d; at most 4096 bins and 2^22 cells per plane" % (b, (r + 1) * b))
+    lo, hi = (0.0, 0.0) if range is None else _bounds(range, "histogram: range")
+    _intensity_volume(x, "histogram")
+    if labels is None:
+        if r != 0:
+            raise ValueError("histogram: rows = %d without labels" % r)
+    else:
+        _label_volume(labels, "histogram")
+        if labels.shape != x.shape or labels.device != x.device:
+            raise ValueError("histogram: labels and x differ in shape or device: %s vs %s" % (tuple(labels.shape), tuple(x.shape)))
+    _require_cuda(x, labels)
+    n, c, d, h, w = x.shape
+    table = torch.empty((n, c, r + 1, b), dtype=torch.int64, device=x.device)
+    edges = torch.empty((n, c, b + 1), dtype=torch.float64, device=x.device)
+    outside = torch.empty((n, c), dtype=torch.int64, device=x.device)
+    overflow = torch.empty((n, c), dtype=torch.int32, device=x.device)
+    check(lib.vs_histogram(x.data_ptr(), _p(labels), n, c, d, h, w, b, r, lo, hi, int(range is None), edges.data_ptr(), table.data_ptr(),
+                           outside.data_ptr(), overflow.data_ptr(), _stream()), "histogram")
+    return {"table": table, "edges": edges, "outside": outside, "overflow": overflow}
+
+
+def joint_histogram(x, y, bins=(256, 256), range=None):
+    """np.histogram2d of every (n, c) plane of two planar fp32 volumes of one shape (N, C, D, H, W) on the device, with histogram's binning rule per
+    variable.  bins: an integer or (bins_x, bins_y); range: None (bounds from the data, per plane and variable) or ((lo_x, hi_x), (lo_y, hi_y)).
+    -> {"table": int64 (N, C, bins_x, bins_y), table[..., i, j] = voxels with x in bin i and y in bin j; "edges_x": fp64 (N, C, bins_x + 1); "edges_y";
+        "outside": int64 (N, C), voxels with either value NaN, +-inf or out of range — in no cell}.
+    bins_x * bins_y <= 2^22.  Three or four launches, no synchronisation (vs_joint_histogram)."""
+    if isinstance(bins, _numbers.Integral) and not isinstance(bins, bool):
+        bins = (bins, bins)
+    try:
+        bx, by = bins
+    except (TypeError, ValueError):
+        raise ValueError("joint_histogram: bins is an integer or a pair, got %r" % (bins,)) from None
+    bx, by = _bins(bx, "joint_histogram: bins_x"), _bins(by, "joint_histogram: bins_y")
+    if bx * by > HISTOGRAM_MAX_CELLS:
+        raise ValueError("joint_histogram: bins_x * bins_y = %d cells per plane, at most 2^22" % (bx * by))
+    r4 = None
+    if range is not None:
+        try:
+            rx, ry = range
+        except (TypeError, ValueError):
+            raise ValueError("joint_histogram: range is None or ((lo_x, hi_x), (lo_y, hi_y)), got %r" % (range,)) from None
+        r4 = (_ctypes.c_double * 4)(*(_bounds(rx, "joint_histogram: range of x") + _bounds(ry, "joint_histogram: range of y")))
+    _intensity_volume(x, "joint_histogram")
+    _intensity_volume(y, "joint_histogram")
+    if x.shape != y.shape or x.device != y.device:
+        raise ValueError("joint_histogram: the two volumes differ in shape or device: %s vs %s" % (tuple(x.shape), tuple(y.shape)))
+    _require_cuda(x, y)
+    n, c, d, h, w = x.shape
+    table = torch.empty((n, c, bx, by), dtype=torch.int64, device=x.device)
+    edges_x = torch.empty((n, c, bx + 1), dtype=torch.float64, device=x.device)
+    edges_y = torch.empty((n, c, by + 1), dtype=torch.float64, device=x.device)
+    outside = torch.empty((n, c), dtype=torch.int64, device=x.device)
+    check(lib.vs_joint_histogram(x.data_ptr(), y.data_ptr(), n, c, d, h, w, bx, by, None if r4 is None else _ctypes.addressof(r4), int(r4 is None),
+                                 edges_x.data_ptr(), edges_y.data_ptr(), table.data_ptr(), outside.data_ptr(), _stream()), "joint_histogram")
+    return {"table": table, "edges_x": edges_x, "edges_y": edges_y, "outside": outside}
+
+
+def mutual_information(table, sigma=1.0, normalized=True):
+    """The tail of the reference's mutual_information_3d (utils/utils.py:824-845) on an int64 joint histogram (N, C, bins_x, bins_y), in fp64 on the
+    device: scipy.ndimage.gaussian_filter(jh, sigma, mode="constant") (sigma == 0: none), + eps, division by the total, the marginals s1 and s2, then
+    (sum s1 log s1 + sum s2 log s2) / sum jh log jh - 1 when normalized, otherwise sum jh log jh - sum s1 log s1 - sum s2 log s2.
+    -> fp64 (N, C).  Every sum runs in a fixed order: the same bits on every run.  No synchronisation (vs_mutual_information).
+    sigma is a number >= 0 with int(4 * sigma + 0.5) <= 64; N * C <= 65535."""
+    import math
+    if isinstance(sigma, bool) or not isinstance(sigma, _numbers.Real) or not (sigma >= 0) or math.isinf(sigma) or int(4.0 * sigma + 0.5) > MI_MAX_RADIUS:
+        raise ValueError("mutual_information: sigma is a number >= 0 with a kernel radius int(4 sigma + 0.5) <= %d, got %r" % (MI_MAX_RADIUS, sigma))
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int64:
+        raise TypeError("mutual_information: the table is an int64 tensor (ops.joint_histogram's), got %s" % getattr(table, "dtype", type(table)))
+    if table.dim() != 4 or table.numel() == 0:
+        raise ValueError("mutual_information: expected a table (N, C, bins_x, bins_y), got shape %s" % (tuple(table.shape),))
+    n, c, bx, by = table.shape
+    if bx * by > HISTOGRAM_MAX_CELLS or n * c > MI_MAX_PLANES:
+        raise ValueError("mutual_information: at most 2^22 cells per plane and %d planes, got shape %s" % (MI_MAX_PLANES, tuple(table.shape)))
+    if not table.is_contiguous():
+        raise ValueError("mutual_information: the table must be contiguous")
+    _require_cuda(table)
+    ws = _workspace(_MI_WORKSPACES, (n, c, bx, by, table.device), lambda: 8 * n * c * (2 * bx * by + 2 * bx + by), "mutual_information workspace",
+                    table.device)
+    mi = torch.empty((n, c), dtype=torch.float64, device=table.device)
+    check(lib.vs_mutual_information(table.data_ptr(), n, c, bx, by, float(sigma), int(bool(normalized)), ws.data_ptr(), mi.data_ptr(), _stream()),
+          "mutual_information")
+    return mi
 
 
 # sliding-window prediction (csrc/window.hip).  evaluation.sliding_window_predict drives these; nothing here synchronises.
