@@ -434,6 +434,27 @@ int vs_data_affine_sample(const void* src, float* dst, int sd, int sh, int sw, i
 /* x = (clamp(x, lo, hi) - subtrahend) / divisor, in place */
 int vs_data_clip_center(float* x, long long total, float lo, float hi, float subtrahend, float divisor, void* stream);
 
+/* ---- elastic deformation of the spatial augmentation (csrc/elastic.hip) -------------------------------------------------------------------
+ * augment_spatial's first stage: per sample a displacement off[k] = scipy.ndimage.gaussian_filter(noise[k], sigma, mode="constant", cval=0) * alpha,
+ * k = 0, 1, 2 (z, y, x), noise uniform in [-1, 1), is added to the zero-centred output mesh BEFORE rotation and scale: the input coordinate of output
+ * voxel o is A (o - (P - 1) / 2 + off[:, o]) + ctr.  noise / field / tmp: (3, d, h, w) fp64, contiguous, 8-byte aligned, three different buffers.
+ *   vs_data_noise_philox   noise[k][v] = 2 u - 1 from Philox4x32-10 with key (seed low 32 bits, seed high 32 bits) and counter (v low 32, v high 32, k,
+ *                          sample low 32), v the linear voxel index of one field; u = ((w0 >> 5) 2^26 + (w1 >> 6)) / 2^53 of the first two output
+ *                          words, in [0, 1).  A pure function of (seed, sample, k, v): the same bits on every run and in every launch geometry.
+ *   vs_data_elastic_field  three separable passes (z, y, x) over all three fields, fp64 throughout; weights exp(-0.5 k^2 / sigma^2) over their sum,
+ *                          radius int(4 sigma + 0.5), made on the host and handed over in the kernel arguments; taps beyond the volume are zeros.
+ *                          tmp is scratch.  sigma <= 0 or not finite, a radius above 128 (sigma > 32.1), alpha not finite, a null pointer or two
+ *                          buffers being one: VS_EINVAL.  alpha == 0 gives zeros.
+ *   vs_data_warp_sample    vs_data_affine_sample with field[(k, oz, oy, ox)] added to the zero-centred output coordinate before the matrix; field has
+ *                          the patch's shape (3, pd, ph, pw).  The sampler is the same code: a zero field gives vs_data_affine_sample's bits.
+ * An empty shape, or fields of 2^31 elements or more: VS_ESHAPE; a misaligned fp64 buffer: VS_EALIGN; all answered on the host before any launch.  No
+ * atomics, no memset, nothing allocated, synchronised or read back; one thread writes each output in a fixed order of additions: the same bits on
+ * every run, in both builds and under graph replay (1, 3 and 1 launches). */
+int vs_data_noise_philox(double* noise, int d, int h, int w, unsigned long long seed, unsigned long long sample, void* stream);
+int vs_data_elastic_field(const double* noise, double* field, double* tmp, int d, int h, int w, double sigma, double alpha, void* stream);
+int vs_data_warp_sample(const void* src, float* dst, const double* field, int sd, int sh, int sw, int pd, int ph, int pw, const double* a9,
+                        const double* ctr3, int order, float cval, void* stream);
+
 /* ---- layout glue at the NCDHW boundary ----------------------------------------------------------- */
 /* planar fp32 [N][c_src][V] -> channels-last [N][V][c_pad] (zero-filled channels >= c_src) */
 int vs_pack_planar(const float* src, void* dst, int n, long long voxels, int c_src, int c_pad, int dtype, void* stream);

@@ -45,7 +45,7 @@ def parse(argv=None):
     p.add_argument("--adam", action="store_true")
     p.add_argument("--mode", type=int, default=0)
     driver.add_native_flags(p)
-    return p.parse_args(argv)
+    return driver.check_aug_flags(p, p.parse_args(argv))
 
 
 if __name__ == "__main__":

@@ -70,7 +70,7 @@ def parse(argv=None):
     p.add_argument("--generate_bounding_boxes", action="store_true", help="accepted (main_target.py:80,169: asserted, never used)")
     p.add_argument("--shift", type=int, default=0, help="CropResize(shift=...) of the training crops (main_target.py:81,204)")
     driver.add_native_flags(p)
-    a = p.parse_args(argv)
+    a = driver.check_aug_flags(p, p.parse_args(argv))
     driver.check_target_flags(a)
     return a
 

@@ -5,15 +5,8 @@
 // skimage.transform.resize and augment_spatial call): gaussian_filter / zoom(grid_mode=True) with mirror boundaries, order-3 spline
 // prefilter (mirror initialisation, fp64 like scipy) + map_coordinates with mode 'constant'.  Not tuned: one thread per output voxel / line.
 #include "common.h"
+#include "data_sample.h"          // dp_mirror, DpAffine, dp_sample: shared with elastic.hip
 #include <limits.h>
-
-__device__ __forceinline__ int dp_mirror(int i, int n) {       // scipy 'mirror': d c b | a b c d | c b a
-    if (n == 1) return 0;
-    const int p = 2 * n - 2;
-    i = i < 0 ? -i : i;
-    i %= p;
-    return i >= n ? p - i : i;
-}
 
 // ---- bounding box of label > 0: box = {min z, y, x, max z, y, x} ----------------------------------------------------------------------------
 __global__ void dp_bbox_init_kernel(int* box) {
@@ -175,47 +168,15 @@ __global__ __launch_bounds__(256) void dp_widen_kernel(const float* __restrict__
 
 // ---- affine resampling: input coordinate of output voxel o = A (o - (P - 1) / 2) + ctr (augment_spatial: A = scale * R^T); scipy
 // map_coordinates(mode='constant'): cval where any coordinate leaves [0, n - 1]; order 3 on the spline coefficients (taps mirrored), order 0 nearest
-struct DpAffine { double a[9]; double ctr[3]; int sd, sh, sw, pd, ph, pw; };
-__device__ __forceinline__ void dp_cubic_w(double t, double (&w)[4]) {
-    w[0] = (1 - t) * (1 - t) * (1 - t) / 6.0;
-    w[1] = (3 * t * t * t - 6 * t * t + 4) / 6.0;
-    w[2] = (-3 * t * t * t + 3 * t * t + 3 * t + 1) / 6.0;
-    w[3] = t * t * t / 6.0;
-}
 template <int ORDER>
 __global__ __launch_bounds__(256) void dp_affine_kernel(const void* __restrict__ src, float* __restrict__ dst, DpAffine p, float cval) {
     const long long total = (long long)p.pd * p.ph * p.pw;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int ox = (int)(i % p.pw), oy = (int)((i / p.pw) % p.ph), oz = (int)(i / ((long long)p.pw * p.ph));
         const double uz = oz - (p.pd - 1) / 2.0, uy = oy - (p.ph - 1) / 2.0, ux = ox - (p.pw - 1) / 2.0;
-        const double cz = p.a[0] * uz + p.a[1] * uy + p.a[2] * ux + p.ctr[0];
-        const double cy = p.a[3] * uz + p.a[4] * uy + p.a[5] * ux + p.ctr[1];
-        const double cx = p.a[6] * uz + p.a[7] * uy + p.a[8] * ux + p.ctr[2];
-        float v = cval;
-        if (cz >= 0.0 && cz <= p.sd - 1.0 && cy >= 0.0 && cy <= p.sh - 1.0 && cx >= 0.0 && cx <= p.sw - 1.0) {
-            if (ORDER == 0) {
-                const int z = (int)floor(cz + 0.5), y = (int)floor(cy + 0.5), x = (int)floor(cx + 0.5);
-                v = ((const float*)src)[((long long)z * p.sh + y) * p.sw + x];
-            } else {
-                const int z0 = (int)floor(cz), y0 = (int)floor(cy), x0 = (int)floor(cx);
-                double wz[4], wy[4], wx[4];
-                dp_cubic_w(cz - z0, wz); dp_cubic_w(cy - y0, wy); dp_cubic_w(cx - x0, wx);
-                const double* co = (const double*)src;
-                double acc = 0.0;
-                for (int a = 0; a < 4; ++a) {
-                    const long long zo = (long long)dp_mirror(z0 - 1 + a, p.sd) * p.sh;
-                    for (int b = 0; b < 4; ++b) {
-                        const long long yo = (zo + dp_mirror(y0 - 1 + b, p.sh)) * p.sw;
-                        double row = 0.0;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) row += wx[k] * co[yo + dp_mirror(x0 - 1 + k, p.sw)];
-                        acc += wz[a] * wy[b] * row;
-                    }
-                }
-                v = (float)acc;
-            }
-        }
-        dst[i] = v;
+        double cz, cy, cx;
+        dp_affine_map(p, uz, uy, ux, cz, cy, cx);
+        dst[i] = dp_sample<ORDER>(src, p, cz, cy, cx, cval);
     }
 }
 
@@ -223,9 +184,6 @@ __global__ __launch_bounds__(256) void dp_affine_kernel(const void* __restrict__
 __global__ __launch_bounds__(256) void dp_clip_center_kernel(float* __restrict__ x, long long total, float lo, float hi, float sub, float div) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) x[i] = (fminf(fmaxf(x[i], lo), hi) - sub) / div;
 }
-
-static inline int dp_blocks(long long total) { long long b = (total + 255) / 256; return (int)(b < 1 ? 1 : (b > 65535 ? 65535 : b)); }
-static inline bool dp_dims_ok(int d, int h, int w) { return d > 0 && h > 0 && w > 0 && (double)d * h * w < 2147483648.0; }
 
 extern "C" int vs_data_bbox(const float* label, int d, int h, int w, int* box6, void* stream) {
     if (!label || !box6 || !dp_dims_ok(d, h, w)) return VS_EINVAL;

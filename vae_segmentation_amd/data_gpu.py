@@ -3,8 +3,8 @@ same names, constructor arguments and dict-in / dict-out protocol, operating on 
 
     NumpyLoader_Multi_merge   utils/utils.py:220-276   (the relabelling; file I/O stays with the caller: hand it the merge array)
     CropResize                utils/utils.py:326-383   (bounding box of the label or of a coarse prediction, cube crop + zero pad, resize)
-    MySpatialTransform        utils/utils.py:927-968   (batchgenerators augment_spatial: rotation, scale, random crop; elastic deformation,
-                                                        which main_source.py:198 switches off, is not implemented)
+    MySpatialTransform        utils/utils.py:927-968   (batchgenerators augment_spatial: elastic deformation — which main_source.py:198 switches off;
+                                                        here it needs a noise source chosen, see the class — rotation, scale, random crop)
     Clip, CenterIntensities   utils/utils.py:508-533, 575-618
 
 The reference runs this chain on 16 CPU workers per loader (skimage resize + scipy map_coordinates of 128^3 volumes: seconds per
@@ -241,9 +241,7 @@ def rotation_matrix(ax, ay, az):
     return np.identity(3) @ rx @ ry @ rz
 
 
-def affine_resample(vol, patch_size, angles, scale, centre, order, cval):
-    """one channel through augment_spatial's coordinate map: coords = (mesh - (P-1)/2) . R * scale + centre, then
-    scipy.ndimage.map_coordinates(order, mode='constant', cval)"""
+def _resample(vol, field, patch_size, angles, scale, centre, order, cval):
     _vol(vol)
     a = (scale * rotation_matrix(*angles).T).astype(np.float64).reshape(-1)          # row vectors times R == R^T times column vectors
     a9, c3 = (ctypes.c_double * 9)(*a), (ctypes.c_double * 3)(*[float(v) for v in centre])
@@ -256,21 +254,86 @@ def affine_resample(vol, patch_size, angles, scale, centre, order, cval):
         src = vol
     else:
         raise NotImplementedError("native resampling: order 3 (image) or 0 (label), the reference's settings")
-    check(lib.vs_data_affine_sample(src.data_ptr(), out.data_ptr(), *vol.shape, *out.shape, a9, c3, order, float(cval), _stream()), "data_affine_sample")
+    if field is None:
+        check(lib.vs_data_affine_sample(src.data_ptr(), out.data_ptr(), *vol.shape, *out.shape, a9, c3, order, float(cval), _stream()), "data_affine_sample")
+    else:
+        if not (field.is_cuda and field.dtype == torch.float64 and tuple(field.shape) == (3,) + tuple(out.shape) and field.is_contiguous()):
+            raise TypeError("expected a contiguous CUDA float64 displacement field %s, got %s %s on %s"
+                            % ((3,) + tuple(out.shape), tuple(field.shape), field.dtype, field.device))
+        check(lib.vs_data_warp_sample(src.data_ptr(), out.data_ptr(), field.data_ptr(), *vol.shape, *out.shape, a9, c3, order, float(cval), _stream()),
+              "data_warp_sample")
     return out
+
+
+def affine_resample(vol, patch_size, angles, scale, centre, order, cval):
+    """one channel through augment_spatial's coordinate map: coords = (mesh - (P-1)/2) . R * scale + centre, then
+    scipy.ndimage.map_coordinates(order, mode='constant', cval)"""
+    return _resample(vol, None, patch_size, angles, scale, centre, order, cval)
+
+
+def warp_resample(vol, field, patch_size, angles, scale, centre, order, cval):
+    """affine_resample with the displacement `field` (3, *patch_size), fp64 on the device (elastic_field), added to the zero-centred mesh before
+    rotation and scale, as augment_spatial adds its elastic offsets: coords = (mesh - (P-1)/2 + field) . R * scale + centre"""
+    return _resample(vol, field, patch_size, angles, scale, centre, order, cval)
+
+
+ELASTIC_MAX_SIGMA = 32.0          # radius int(4 sigma + 0.5) <= 128: the longest weight table the filter kernels take
+
+
+def _is_counter(noise):
+    return isinstance(noise, tuple) and len(noise) == 2 and all(isinstance(v, (int, np.integer)) for v in noise)
+
+
+def elastic_field(patch, alpha, sigma, noise):
+    """augment_spatial's elastic offsets for one sample: scipy.ndimage.gaussian_filter(noise[k], sigma, mode="constant", cval=0) * alpha for the three
+    axes k -> (3, D, H, W) fp64 on the device, in voxels.  `noise`: the three fields uniform in [-1, 1) as a (3, D, H, W) float64 array or tensor (host
+    or device), or a tuple (seed, sample) of ints: the fields are then made on the device by Philox4x32-10 (vs_data_noise_philox), a pure function of
+    (seed, sample, axis, voxel)."""
+    patch = tuple(int(s) for s in patch)
+    if len(patch) != 3 or min(patch) < 1:
+        raise ValueError("elastic_field: patch is (D, H, W), got %r" % (patch,))
+    alpha, sigma = float(alpha), float(sigma)
+    if not (0.0 < sigma <= ELASTIC_MAX_SIGMA) or not np.isfinite(alpha):
+        raise ValueError("elastic_field: 0 < sigma <= %g and a finite alpha, got sigma %r, alpha %r" % (ELASTIC_MAX_SIGMA, sigma, alpha))
+    shape = (3,) + patch
+    if _is_counter(noise):
+        src = torch.empty(shape, dtype=torch.float64, device="cuda")
+        check(lib.vs_data_noise_philox(src.data_ptr(), *patch, int(noise[0]) & (2 ** 64 - 1), int(noise[1]) & (2 ** 64 - 1), _stream()), "data_noise_philox")
+    else:
+        src = torch.from_numpy(noise) if isinstance(noise, np.ndarray) else noise
+        if not isinstance(src, torch.Tensor) or src.dtype != torch.float64 or tuple(src.shape) != shape:
+            raise TypeError("elastic_field: noise is a float64 array or tensor of shape %s or a tuple (seed, sample) of ints" % (shape,))
+        src = src.cuda().contiguous()
+    field, tmp = torch.empty_like(src), torch.empty_like(src)
+    check(lib.vs_data_elastic_field(src.data_ptr(), field.data_ptr(), tmp.data_ptr(), *patch, sigma, alpha, _stream()), "data_elastic_field")
+    return field
 
 
 class MySpatialTransform:
     """utils/utils.py:927-968 with the arguments main_source.py:196-205 passes.  data_dict[data_key] / [label_key]: (B, C, D, H, W) CUDA
-    tensors (the reference reshapes to [-1, 1, D, H, W] first).  `rng`: a numpy RandomState (default: the global one, as batchgenerators)."""
+    tensors (the reference reshapes to [-1, 1, D, H, W] first).  `rng`: a numpy RandomState (default: the global one, as batchgenerators).
+    Elastic deformation (do_elastic_deform and p_el_per_sample > 0) needs `noise` chosen, because the two sources give different samples:
+      noise="numpy"   alpha, sigma and then the three rng.random_sample(patch) fields are drawn from `rng` in augment_spatial's order, before the
+                      rotation draws: a seeded RandomState yields the stream batchgenerators would consume; the fields cross to the device
+      noise="philox"  only alpha and sigma come from `rng`; the fields are made on the device from (seed, n), n counting this transform's deformed
+                      samples: nothing patch-sized leaves the device, and the stream of `rng` differs from batchgenerators' from the first sample on
+    One field per sample is shared by all of its channels and by its label."""
 
     def __init__(self, patch_size, patch_center_dist_from_border=30, do_elastic_deform=True, alpha=(0., 1000.), sigma=(10., 13.), do_rotation=True,
                  angle_x=(0, 2 * np.pi), angle_y=(0, 2 * np.pi), angle_z=(0, 2 * np.pi), do_scale=True, scale=(0.75, 1.25), border_mode_data="nearest",
                  border_cval_data=0, order_data=3, border_mode_seg="constant", border_cval_seg=0, order_seg=0, random_crop=True, data_key="data",
                  label_key="seg", p_el_per_sample=1, p_scale_per_sample=1, p_rot_per_sample=1, independent_scale_for_each_axis=False,
-                 p_rot_per_axis: float = 1, rng=None):
-        if do_elastic_deform and p_el_per_sample > 0:
-            raise NotImplementedError("elastic deformation has no native kernel (main_source.py:198 passes do_elastic_deform=False)")
+                 p_rot_per_axis: float = 1, rng=None, noise=None, seed=0):
+        if noise not in (None, "numpy", "philox"):
+            raise ValueError("MySpatialTransform: noise is None, 'numpy' or 'philox', got %r" % (noise,))
+        self.do_elastic = bool(do_elastic_deform and p_el_per_sample > 0)
+        if self.do_elastic and noise is None:
+            raise NotImplementedError("elastic deformation needs a noise source: choose noise='numpy' (the fields are drawn from rng, batchgenerators' "
+                                      "stream) or noise='philox' (made on the device from seed); main_source.py:198 passes do_elastic_deform=False")
+        if self.do_elastic and not (0 <= alpha[0] <= alpha[1] and 0 < sigma[0] <= sigma[1] <= ELASTIC_MAX_SIGMA):
+            raise ValueError("MySpatialTransform: elastic deformation takes 0 <= alpha[0] <= alpha[1] and 0 < sigma[0] <= sigma[1] <= %g, got %r, %r"
+                             % (ELASTIC_MAX_SIGMA, alpha, sigma))
+        self.alpha, self.sigma, self.p_el, self.noise, self.seed, self.n_elastic = alpha, sigma, p_el_per_sample, noise, int(seed), 0
         if border_mode_data != "constant" or border_mode_seg != "constant" or independent_scale_for_each_axis:
             raise NotImplementedError("native resampling: constant borders, isotropic scale (main_source.py:196-205)")
         self.patch_size = patch_size
@@ -283,9 +346,19 @@ class MySpatialTransform:
         self.rng = rng if rng is not None else np.random
 
     def draw(self, shape):
-        """the random draws of one sample in augment_spatial's order -> (angles, scale, centre, modified)"""
+        """the random draws of one sample in augment_spatial's order -> (angles, scale, centre, modified), and for a deformed sample a fifth element
+        (alpha, sigma, noise_spec): noise_spec is what elastic_field takes, the (3, D, H, W) fields (noise='numpy') or (seed, n) (noise='philox')"""
         r = self.rng
-        angles, sc, modified = [0.0, 0.0, 0.0], 1.0, False
+        angles, sc, modified, elastic = [0.0, 0.0, 0.0], 1.0, False, None
+        if self.do_elastic and r.uniform() < self.p_el:
+            a, s = r.uniform(self.alpha[0], self.alpha[1]), r.uniform(self.sigma[0], self.sigma[1])
+            if self.noise == "numpy":
+                patch = tuple(self.patch_size) if self.patch_size is not None else tuple(shape)
+                spec = np.stack([r.random_sample(patch) * 2 - 1 for _ in range(3)])
+            else:
+                spec = (self.seed, self.n_elastic)
+            self.n_elastic += 1
+            elastic, modified = (a, s, spec), True
         if self.do_rotation and r.uniform() < self.p_rot:
             for d in range(3):
                 angles[d] = r.uniform(self.angle[d][0], self.angle[d][1]) if r.uniform() <= self.p_rot_axis else 0.0
@@ -300,6 +373,8 @@ class MySpatialTransform:
             centre = [r.uniform(self.dist[d], shape[d] - self.dist[d]) for d in range(3)]
         else:
             centre = [shape[d] / 2.0 - 0.5 for d in range(3)]
+        if elastic is not None:
+            return tuple(angles), sc, tuple(centre), modified, elastic
         return tuple(angles), sc, tuple(centre), modified
 
     def __call__(self, data_dict, params=None):
@@ -308,17 +383,19 @@ class MySpatialTransform:
         out_d = torch.empty((data.shape[0], data.shape[1]) + patch, dtype=torch.float32, device=data.device)
         out_s = None if seg is None else torch.empty((seg.shape[0], seg.shape[1]) + patch, dtype=torch.float32, device=seg.device)
         for b in range(data.shape[0]):
-            angles, sc, centre, modified = params[b] if params is not None else self.draw(data.shape[2:])
+            prm = params[b] if params is not None else self.draw(data.shape[2:])
+            angles, sc, centre, modified = prm[:4]
+            field = elastic_field(patch, *prm[4]) if len(prm) > 4 and prm[4] is not None else None        # one field for the sample's channels and its label
             if not modified and not self.random_crop and tuple(data.shape[2:]) == patch:
                 out_d[b] = data[b]
                 if seg is not None:
                     out_s[b] = seg[b]
                 continue
             for c in range(data.shape[1]):
-                out_d[b, c] = affine_resample(data[b, c].contiguous(), patch, angles, sc, centre, self.order_data, self.cval_data)
+                out_d[b, c] = _resample(data[b, c].contiguous(), field, patch, angles, sc, centre, self.order_data, self.cval_data)
             if seg is not None:
                 for c in range(seg.shape[1]):
-                    out_s[b, c] = affine_resample(seg[b, c].contiguous(), patch, angles, sc, centre, self.order_seg, self.cval_seg)
+                    out_s[b, c] = _resample(seg[b, c].contiguous(), field, patch, angles, sc, centre, self.order_seg, self.cval_seg)
         data_dict[self.data_key] = out_d
         if seg is not None:
             data_dict[self.label_key] = out_s
@@ -362,7 +439,7 @@ class CenterIntensities(BaseTransform):
 def train_sample(merge, patch_size, mask_index=None, transform=None, params=None, field="venous", shift=0):
     """One training sample through main_source.py:191-211 on the device: merge (D, H, W, >= 2) CUDA float32 tensor (what
     NumpyLoader_Multi_merge loads) -> (image (1, 1, P, P, P), label (1, 1, P, P, P)).  `transform`: a MySpatialTransform (None: no
-    augmentation, --no_aug); `params`: its per-sample (angles, scale, centre, modified) instead of random draws."""
+    augmentation, --no_aug); `params`: its per-sample (angles, scale, centre, modified[, (alpha, sigma, noise_spec)]) instead of random draws."""
     img = merge[..., 0].contiguous()
     lab = merge[..., 1].contiguous()
     if mask_index is not None:

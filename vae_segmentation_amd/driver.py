@@ -101,11 +101,13 @@ class DeviceCaseLoader:
         self.shift = int(getattr(args, "shift", 0)) if train else 0           # main_target.py:204 (training crops only; validation: CropResize default)
         self.transform = None
         if train and not getattr(args, "no_aug", False):                       # main_source.py:195-205
+            p_el = float(getattr(args, "aug_elastic", 0.0) or 0.0)            # --aug_elastic: the stage main_source.py:198 leaves one flag away from on
+            elastic = {"noise": "philox", "seed": seed + 1000 * rank} if p_el > 0 else {}
             self.transform = data_gpu.MySpatialTransform(
-                self.patch, [d // 2 - 5 for d in self.patch], random_crop=True, scale=(0.85, 1.15), do_elastic_deform=False, alpha=(0, 500),
+                self.patch, [d // 2 - 5 for d in self.patch], random_crop=True, scale=(0.85, 1.15), do_elastic_deform=p_el > 0, alpha=(0, 500),
                 do_rotation=True, sigma=(10, 30.), angle_x=(-0.2, 0.2), angle_y=(-0.2, 0.2), angle_z=(-0.2, 0.2), border_mode_data="constant",
-                border_cval_data=-1024, data_key=IMG_KEY, p_el_per_sample=0, label_key=LABEL_KEY, p_scale_per_sample=1, p_rot_per_sample=1,
-                rng=np.random.RandomState(seed + 1000 * rank))
+                border_cval_data=-1024, data_key=IMG_KEY, p_el_per_sample=p_el, label_key=LABEL_KEY, p_scale_per_sample=1, p_rot_per_sample=1,
+                rng=np.random.RandomState(seed + 1000 * rank), **elastic)
         self._dg = data_gpu
 
     def set_epoch(self, epoch):
@@ -952,11 +954,32 @@ def check_target_flags(a):
               % ", ".join("--" + n for n in ignored), file=sys.stderr)
 
 
+def _probability(text):
+    import argparse
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError("a probability in [0, 1], got %r" % text)
+    return v
+
+
+def check_aug_flags(parser, a):
+    """--aug_elastic deforms the augmented training samples: with --no_aug there are none"""
+    if getattr(a, "aug_elastic", 0.0) > 0 and getattr(a, "no_aug", False):
+        parser.error("--aug_elastic deforms the augmented training samples: it cannot be combined with --no_aug")
+    return a
+
+
 def add_native_flags(parser):
     g = parser.add_argument_group("native (MI355X) additions")
     g.add_argument("--synthetic", action="store_true", default=True, help="synthetic volumes (default: no dataset ships with this repository)")
     g.add_argument("--real_data", action="store_true", help="train / validate on the merge.npy cases of lists/<data_path>[train_list | val_list] under "
                    "data_root / val_data_root, transformed on the device (data_gpu.py) — the reference's loader stack (main_source.py:186-243)")
+    g.add_argument("--aug_elastic", type=_probability, default=0.0, metavar="P", help="with --real_data: elastic deformation of a training sample with "
+                   "probability P before rotation and scale (augment_spatial's first stage with the alpha=(0, 500), sigma=(10, 30) the reference's entry "
+                   "points pass, noise from Philox on the device: data_gpu.MySpatialTransform(noise='philox')); 0 = off, the reference's setting")
     g.add_argument("--size", type=int, default=128, help="cubic patch side (reference: patch_size 128, main_source.py:117)")
     g.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "fp16"], help="kernel storage dtype")
     g.add_argument("--synthetic_train", type=int, default=16)
