@@ -754,7 +754,9 @@ int vs_kl_bwd(const float* mean, const float* std_, const float* gout, float* gm
 /* ---- losses ---------------------------------------------------------------------------------------- */
 /* soft Dice (utils/evaluation.py:48-80; main_source.py:150-182):  s,t planar fp32 [B][C][V].
  *   sums[b][c] = (sum s*t, sum s, sum t) for bot <= c < top (double[B][C][3], fully overwritten)
- *   per_sample[b] = mean_{c in [bot,top)} 2*I/(S+T+eps) ;  mean_out[0] = mean_b per_sample[b]            */
+ *   per_sample[b] = mean_{c in [bot,top)} 2*I/(S+T+eps) ;  mean_out[0] = mean_b per_sample[b]
+ *   V is a multiple of 4 (the kernels read 16-byte quads; VS_EALIGN otherwise, here and in vs_dice_loss_multi_*): a caller with another
+ *   plane size pads the planes with zeros — labels with -1 — as ops.Dice / ops.DiceLossSum do.            */
 int vs_dice_fwd(const float* s, const float* t, double* sums, float* per_sample, float* mean_out,
                 int batch, int channels, long long voxels, int bot, int top, float eps, void* stream);
 /* gs/gt (either may be NULL) = d(sum_b w[b]*per_sample[b])/d(s|t); channels outside [bot,top) get 0.

@@ -674,8 +674,6 @@ __global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict_
         a1 += (double)(x[0] + x[1]) + (double)(x[2] + x[3]);
         a2 += (double)(y[0] + y[1]) + (double)(y[2] + y[3]);
     }
-    if (blockIdx.x == 0)
-        for (long long i = v4 * 4 + threadIdx.x; i < voxels; i += 256) { a0 += (double)sp[i] * tp[i]; a1 += sp[i]; a2 += tp[i]; }
     __shared__ double red[4][3];
     a0 = wave_sum_d(a0); a1 = wave_sum_d(a1); a2 = wave_sum_d(a2);
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = a0; red[threadIdx.x >> 6][1] = a1; red[threadIdx.x >> 6][2] = a2; }

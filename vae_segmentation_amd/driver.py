@@ -376,12 +376,9 @@ def validate_finetune(runner, loader):
 
 
 def _hard_dice(pred_hot, gt_hot, lo, nc):
-    """hard Dice of two planar one-hot tensors (K, ...) over the classes [lo, nc), avg_dsc(binary=True)'s arithmetic; the Dice kernel reads whole
-    16-byte quads, so a volume of any size is padded with voxels that belong to no class on either side"""
+    """hard Dice of two planar one-hot tensors (K, ...) over the classes [lo, nc), avg_dsc(binary=True)'s arithmetic; a volume of any size
+    (ops.Dice pads a plane that is no whole number of 16-byte quads with voxels that belong to no class on either side)"""
     a, b = pred_hot.reshape(1, pred_hot.shape[0], -1), gt_hot.reshape(1, gt_hot.shape[0], -1)
-    pad = (-a.shape[-1]) % 4
-    if pad:
-        a, b = torch.nn.functional.pad(a, (0, pad)), torch.nn.functional.pad(b, (0, pad))
     return ops.Dice.apply(a, b, lo, nc, EPS_EVALUATION, True)
 
 

@@ -12,13 +12,7 @@ EPS_MAIN_SOURCE = 1e-4
 
 def dice(A, B):
     """utils/evaluation.py:6-7 — whole-tensor soft dice (eps 1e-6)."""
-    a = A.reshape(1, 1, -1)
-    b = B.reshape(1, 1, -1)
-    pad = (-a.shape[-1]) % 4
-    if pad:
-        a = torch.nn.functional.pad(a, (0, pad))
-        b = torch.nn.functional.pad(b, (0, pad))
-    return ops.Dice.apply(a, b, 0, 1, EPS_EVALUATION, True)
+    return ops.Dice.apply(A.reshape(1, 1, -1), B.reshape(1, 1, -1), 0, 1, EPS_EVALUATION, True)
 
 
 def binarize(A):

@@ -2196,8 +2196,28 @@ class KL(torch.autograd.Function):
         return gm, gs
 
 
+def _pad_quads(x, b, c, value):
+    """The Dice kernels read whole 16-byte quads of a plane.  A contiguous (b, c, ...) tensor whose planes hold a multiple of 4 voxels is returned as it
+    is; any other is flattened to (b, c, V) and padded to the next multiple of 4 with `value` — 0 for a source or a tensor target (it adds nothing to
+    I, S or T), -1 for a label volume (it matches no class)."""
+    voxels = x.numel() // (b * c)
+    if voxels % 4 == 0:
+        return x
+    return torch.nn.functional.pad(x.reshape(b, c, voxels), (0, (-voxels) % 4), value=value)
+
+
+def _unpad_quads(g, shape):
+    """the gradient of a tensor that _pad_quads padded, in the caller's shape (the padding's gradient is dropped)"""
+    if g is None or tuple(g.shape) == tuple(shape):
+        return g
+    voxels = 1
+    for d in shape[2:]:
+        voxels *= d
+    return g[:, :, :voxels].reshape(shape)
+
+
 class Dice(torch.autograd.Function):
-    """Soft Dice over channels [bot, top) of two planar fp32 (B, C, D, H, W) tensors.
+    """Soft Dice over channels [bot, top) of two planar fp32 (B, C, D, H, W) tensors; any voxel count (_pad_quads).
     return_mean=True -> scalar mean over (b, c); False -> per-sample (B,) means (utils/evaluation.py:68-79)."""
 
     @staticmethod
@@ -2205,6 +2225,8 @@ class Dice(torch.autograd.Function):
         _require_cuda(s, t)
         s, t = _contig(s.float()), _contig(t.float())
         b, c = s.shape[0], s.shape[1]
+        ctx.shape = tuple(s.shape)
+        s, t = _pad_quads(s, b, c, 0.0), _pad_quads(t, b, c, 0.0)
         voxels = s.numel() // (b * c)
         sums = torch.empty((b, c, 3), dtype=torch.float64, device=s.device)
         per = torch.empty(b, dtype=torch.float32, device=s.device)
@@ -2227,7 +2249,7 @@ class Dice(torch.autograd.Function):
         if gs is not None or gt is not None:
             check(lib.vs_dice_bwd(s.data_ptr(), t.data_ptr(), sums.data_ptr(), g.data_ptr(), 1 if return_mean else 0,
                                   _p(gs), _p(gt), b, c, voxels, bot, top, eps, _stream()), "dice_bwd")
-        return gs, gt, None, None, None, None
+        return _unpad_quads(gs, ctx.shape), _unpad_quads(gt, ctx.shape), None, None, None, None
 
 
 class LabelTarget:
@@ -2258,6 +2280,10 @@ class DiceLossSum(torch.autograd.Function):
         for t, lab in zip(ts, is_lab):
             if lab and t.numel() != b * voxels:
                 raise ValueError("label target: expected %d x %d labels, got %s" % (b, voxels, tuple(t.shape)))
+        ctx.shapes = [tuple(s.shape)] + [tuple(t.shape) for t in ts]
+        s = _pad_quads(s, b, c, 0.0)
+        ts = [_pad_quads(t, b, 1, -1.0) if lab else _pad_quads(t, b, c, 0.0) for t, lab in zip(ts, is_lab)]
+        voxels = s.numel() // (b * c)
         scratch = torch.empty(lib.vs_dice_loss_multi_scratch_doubles(k, b, c), dtype=torch.float64, device=s.device)
         terms = torch.empty(k, dtype=torch.float32, device=s.device)
         final = torch.empty((), dtype=torch.float32, device=s.device)
@@ -2292,7 +2318,7 @@ class DiceLossSum(torch.autograd.Function):
             wp = (_ct.c_float * k)(*weights)
             check(lib.vs_dice_loss_multi_labels_bwd(s.data_ptr(), _ct.addressof(tp), _ct.addressof(lp), _ct.addressof(wp), k, scratch.data_ptr(),
                                                     g.data_ptr(), _p(gs), _ct.addressof(gp), b, c, voxels, bot, top, eps, _stream()), "dice_loss_multi_bwd")
-        return (gs, None, None, None, None) + tuple(gts)
+        return (_unpad_quads(gs, ctx.shapes[0]), None, None, None, None) + tuple(_unpad_quads(x, sh) for x, sh in zip(gts, ctx.shapes[1:]))
 
 
 FUSED_LOSS = [os.environ.get("VS_FUSED_LOSS", "1") != "0"]
