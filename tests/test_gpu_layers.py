@@ -386,9 +386,12 @@ def test_k3b_bwd_data_with_fused_apply(case, dtype):
     assert lib.vs_conv_k3_fused_apply_supported(2, 24, 24, 24, 32, 32, 1, dt) == 0
 
 
+FUSED_WGRAD_CASES = [(2, 96, 96, 96), (2, 12, 16, 40), (1, 9, 11, 33), (3, 5, 9, 33), (1, 4, 8, 32), (1, 128, 128, 128), (16, 4, 8, 32), (25, 4, 8, 32)]      # (N, D, H, W)
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("fused_apply", [False, True])
-@pytest.mark.parametrize("case", [(2, 96, 96, 96), (2, 12, 16, 40), (1, 9, 11, 33), (3, 5, 9, 33), (1, 4, 8, 32), (1, 128, 128, 128), (16, 4, 8, 32), (25, 4, 8, 32)])
+@pytest.mark.parametrize("case", FUSED_WGRAD_CASES)
 def test_k3_bwd_data_with_fused_weight_gradient(case, fused_apply, dtype):
     """vs_conv_k3_bwd_data_wgrad (igemm_k3tw.h): the backward-data launch of an 8 -> 8 layer that also forms the layer's weight gradient — against the two
     launches it replaces: backward-data output and fused sums identical to vs_conv_gather_bwd_data / vs_conv_k3_bwd_data_fused_apply (same instruction

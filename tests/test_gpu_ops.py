@@ -121,8 +121,12 @@ def test_conv_k3_fwd_bwd(case, lazy, dtype, stat_tol=1.0):
     assert relerr(w_gpu.grad.cpu(), wq.grad) < gtol
 
 
+ODD_CHUNK_CASES = [(3, 96, 32, 5, 6, 6), (2, 160, 96, 2, 3, 4)]
+EXTREME_ASPECT_CASES = [(1, 32, 32, 1, 1, 54), (2, 32, 64, 30, 2, 2), (1, 64, 32, 1, 7, 16), (2, 32, 32, 2, 30, 2)]
+
+
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("case", [(3, 96, 32, 5, 6, 6), (2, 160, 96, 2, 3, 4)])
+@pytest.mark.parametrize("case", ODD_CHUNK_CASES)
 def test_conv_k3_small_volume_odd_chunk_counts(case, dtype):
     """3 and 5 chunks of 32 channels: the small-volume kernel keeps two stages in flight, the last stage of an odd count runs alone.
     (Materialised input: the statistics kernels only take the model's channel counts.)"""
@@ -131,7 +135,7 @@ def test_conv_k3_small_volume_odd_chunk_counts(case, dtype):
 
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("lazy", [False, True])
-@pytest.mark.parametrize("case", [(1, 32, 32, 1, 1, 54), (2, 32, 64, 30, 2, 2), (1, 64, 32, 1, 7, 16), (2, 32, 32, 2, 30, 2)])
+@pytest.mark.parametrize("case", EXTREME_ASPECT_CASES)
 def test_conv_k3_small_volume_extreme_aspects(case, lazy, dtype):
     """The small-volume kernel stages the REAL voxels of the padded sample (igemm_k3s.h, end of round 6): a thread's fragment is voxel rv -> (z, y, x) by
     reciprocal multiplication.  Volumes far from cubic — one long axis up to the 512-voxel padded limit — put the largest divisors and the most padding there."""
@@ -169,9 +173,12 @@ def test_conv_k2s2_fwd_bwd(case, lazy, dtype):
     assert relerr(b_gpu.grad.cpu(), bq.grad) < gtol
 
 
+T2_CASES = [(2, 16, 4, 4, 8), (1, 32, 3, 5, 7), (1, 64, 2, 2, 3), (1, 128, 3, 3, 3), (2, 256, 2, 2, 2)]
+
+
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("lazy", [False, True])
-@pytest.mark.parametrize("case", [(2, 16, 4, 4, 8), (1, 32, 3, 5, 7), (1, 64, 2, 2, 3), (1, 128, 3, 3, 3), (2, 256, 2, 2, 2)])
+@pytest.mark.parametrize("case", T2_CASES)
 def test_conv_transpose_fwd_bwd(case, lazy, dtype):
     ops = _ops()
     n, c, d, h, w = case
@@ -532,9 +539,18 @@ def _group_layers_backward(ops, dtype):
     return [(wg.grad.clone(), None if bg is None else bg.grad.clone()) for wg, bg in outs], refs
 
 
+GROUP_SETTINGS = [("1", "1", "1", "0", "1"), ("0", "1", "1", "0", "1"), ("1", "0", "1", "0", "1"), ("1", "1", "0", "0", "1"),      # (mpack, uber, swap, big, fold)
+                  ("1", "1", "1", "1", "1"), ("1", "1", "0", "1", "1"), ("0", "1", "1", "1", "1"), ("1", "1", "1", "0", "0")]
+
+
+def group_config(mpack, uber, swap, big, fold):
+    """the vs_config switches of one GROUP_SETTINGS entry"""
+    return dict(wgrad_mpack=int(mpack), wgrad_uber=int(uber), wgrad_swap=int(swap), wgrad_big_min_voxels=1 if big == "1" else 1000000000,
+                wgrad_bias_fold=int(fold), wgrad_xcd=2 if fold == "1" else 1)
+
+
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("mpack,uber,swap,big,fold", [("1", "1", "1", "0", "1"), ("0", "1", "1", "0", "1"), ("1", "0", "1", "0", "1"), ("1", "1", "0", "0", "1"),
-                                                      ("1", "1", "1", "1", "1"), ("1", "1", "0", "1", "1"), ("0", "1", "1", "1", "1"), ("1", "1", "1", "0", "0")])
+@pytest.mark.parametrize("mpack,uber,swap,big,fold", GROUP_SETTINGS)
 def test_grouped_weight_gradients_many_layers(dtype, mpack, uber, swap, big, fold, monkeypatch):
     """vs_conv_wgrad_multi (main_source.py:660: the gradients the optimiser step reads): 34 layers of all conv kinds deferred to the end of ONE
     backward pass and issued as grouped launches — each against F.conv3d / F.conv_transpose3d autograd on the CPU, against the
@@ -545,8 +561,7 @@ def test_grouped_weight_gradients_many_layers(dtype, mpack, uber, swap, big, fol
     # (csrc/wgrad.hip multi_plan); 0: as submitted.  big: the 8 x 8 x 16-tile kernel (g3c_body) takes every layer it supports — by default only tensors of
     # >= 400 k voxels (none of this list) get it.  Switched through the library's one configuration entry point (vs_set_config), restored afterwards.
     # fold 1 (default): a transposed conv's bias gradient is summed by its own weight-gradient workgroups (their Q operand is that tensor); 0: a pass of its own.
-    with ops.config(wgrad_mpack=int(mpack), wgrad_uber=int(uber), wgrad_swap=int(swap), wgrad_big_min_voxels=1 if big == "1" else 1000000000,
-                    wgrad_bias_fold=int(fold), wgrad_xcd=2 if fold == "1" else 1):
+    with ops.config(**group_config(mpack, uber, swap, big, fold)):
         assert ops._GROUP["enabled"]
         got, refs = _group_layers_backward(ops, dtype)
         tol = TOL[dtype] * 4
