@@ -455,6 +455,44 @@ int vs_data_elastic_field(const double* noise, double* field, double* tmp, int d
 int vs_data_warp_sample(const void* src, float* dst, const double* field, int sd, int sh, int sw, int pd, int ph, int pw, const double* a9,
                         const double* ctr3, int order, float cval, void* stream);
 
+/* ---- intensity augmentation (csrc/augment.hip) ---------------------------------------------------------------------------------------------
+ * The batchgenerators / nnU-Net intensity set on fp32 planes (d, h, w): an op is computed in fp64 from the fp32 input and from fp64 plane statistics
+ * and rounded to fp32 once (DESIGN "Intensity augmentation" states every rule).  A statistics RECORD is four doubles {min, max, mean, population std};
+ * the sums are shifted by the plane's first voxel and added over a fixed chunking (8192 voxels) of the linear index in chunk order: a function of the
+ * plane's bits alone, whichever entry point makes it.  workspace: vs_aug_stats_workspace_bytes(planes, d, h, w) bytes of scratch, 8-byte aligned.
+ *   vs_aug_stats          rec[planes][4] of x[planes][d][h][w]
+ *   vs_aug_normal_philox  n[v], v < d h w: pair j = v / 2 from Philox4x32-10 under key (seed low, seed high) and counter (j low, j high, 0x100 + channel,
+ *                         sample low); u1 = ((w0 >> 5) 2^26 + (w1 >> 6) + 0.5) 2^-53, u2 = ((w2 >> 5) 2^26 + (w3 >> 6)) 2^-53, r = sqrt(-2 ln u1),
+ *                         n[2j] = r cos(2 pi u2), n[2j + 1] = r sin(2 pi u2), fp64
+ *   vs_aug_stage          one pass over one plane, in this order, with an fp32 rounding after each step that is present:
+ *                           read x at the voxel mirrored by `flip` (z / y / x = 4 / 2 / 1)
+ *                           + s n     noise_mode 1: n = noise[] (fp64), 2: n as vs_aug_normal_philox makes it; n is indexed by the OUTPUT voxel when
+ *                                     flip_first != 0 (the mirror is the stage's first op) and by the voxel READ otherwise (the mirror is its last op)
+ *                           * m       has_mult
+ *                           op 1 contrast: (v - mean) p + mean, clamped to [min, max] when flag; op 2 power: v' = -v when flag, then
+ *                                     ((v' - min) / (max - min + 1e-7))^p (max - min) + min, negated back; op 3 restat: (v' - mean) / (std + 1e-8) std0
+ *                                     + mean0, same negation.  min / max / mean / std: the record `rec` of the plane the op applies to — which the
+ *                                     caller has, so an op may share a stage only with steps that FOLLOW it or with the mirror — negated and swapped
+ *                                     for v'.  (mean0, std0): the host values, or, when rec0 is given, the mean (negated when flag) and std of rec0.
+ *                           store y; when rec_out is given, the record of y (one more small launch; workspace for one plane)
+ *   vs_aug_blur           scipy.ndimage.gaussian_filter(x, sigma, mode="reflect", truncate=4) of a float32 array: radius int(4 sigma + 0.5), passes along
+ *                         z, y, x with fp64 accumulation, each rounded to fp32; weights: a HOST array, the half kernel w[0 .. radius] (w[k]: taps -k
+ *                         and +k) as scipy's _gaussian_kernel1d makes it, copied into the kernel arguments.  0 < sigma <= 2, VS_EINVAL beyond.  One
+ *                         launch; vs_aug_blur_tile writes the (z, y, x) output tile of a workgroup at that sigma to tile3 (host ints).
+ *   vs_aug_flip           y = x mirrored by mask, per plane: a copy
+ * x and y are different buffers.  A null pointer, flip / mask outside [0, 7], an unknown mode or op, a parameter that is not finite: VS_EINVAL; an empty
+ * plane or one of 2^31 voxels or more: VS_ESHAPE; fp32 buffers not 4-byte, fp64 buffers not 8-byte aligned: VS_EALIGN; all answered on the host before
+ * any launch.  No atomics, no memset, nothing allocated, synchronised or read back: the same bits on every run, in both builds and under graph replay. */
+long long vs_aug_stats_workspace_bytes(int planes, int d, int h, int w);
+int vs_aug_stats(const float* x, double* rec, double* workspace, int planes, int d, int h, int w, void* stream);
+int vs_aug_normal_philox(double* n, int d, int h, int w, unsigned long long seed, unsigned long long sample, int channel, void* stream);
+int vs_aug_stage(const float* x, float* y, int d, int h, int w, int flip, int flip_first, int noise_mode, const double* noise, double s,
+                 unsigned long long seed, unsigned long long sample, int channel, int has_mult, double m, int op, double p, int flag,
+                 const double* rec, const double* rec0, double mean0, double std0, double* rec_out, double* workspace, void* stream);
+int vs_aug_blur_tile(double sigma, int* tile3);
+int vs_aug_blur(const float* x, float* y, int d, int h, int w, double sigma, const double* weights, void* stream);
+int vs_aug_flip(const float* x, float* y, int planes, int d, int h, int w, int mask, void* stream);
+
 /* ---- layout glue at the NCDHW boundary ----------------------------------------------------------- */
 /* planar fp32 [N][c_src][V] -> channels-last [N][V][c_pad] (zero-filled channels >= c_src) */
 int vs_pack_planar(const float* src, void* dst, int n, long long voxels, int c_src, int c_pad, int dtype, void* stream);

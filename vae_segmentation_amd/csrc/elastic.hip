@@ -20,6 +20,7 @@
 // fixed order of additions: the same bits on every run, in both builds of the library and under graph replay.
 #include "common.h"
 #include "data_sample.h"
+#include "philox.h"
 #include <math.h>
 
 constexpr int EL_MAX_RADIUS = 128;
@@ -107,26 +108,15 @@ __global__ __launch_bounds__(256) void el_gauss_x_kernel(const double* __restric
     }
 }
 
-// ---- Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) ------------------------------------------------------------
-__device__ __forceinline__ void el_philox4x32_10(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int c3, unsigned int k0, unsigned int k1,
-                                                 unsigned int& w0, unsigned int& w1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned int)p1; c3 = (unsigned int)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    w0 = c0; w1 = c1;
-}
+// ---- the noise: Philox4x32-10 (philox.h) ---------------------------------------------------------------------------------------------------------
 // noise[axis][v] = 2 u - 1, u = ((w0 >> 5) 2^26 + (w1 >> 6)) / 2^53 of block (v lo, v hi, axis, sample lo) under key (seed lo, seed hi): every step exact in fp64
 __global__ __launch_bounds__(256) void el_noise_kernel(double* __restrict__ noise, long long voxels, unsigned long long seed, unsigned int sample) {
     const long long total = 3 * voxels;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const unsigned int axis = (unsigned int)(i / voxels);
         const unsigned long long v = (unsigned long long)(i - (long long)axis * voxels);
-        unsigned int w0, w1;
-        el_philox4x32_10((unsigned int)v, (unsigned int)(v >> 32), axis, sample, (unsigned int)seed, (unsigned int)(seed >> 32), w0, w1);
+        unsigned int w0, w1, w2, w3;
+        vs_philox4x32_10((unsigned int)v, (unsigned int)(v >> 32), axis, sample, (unsigned int)seed, (unsigned int)(seed >> 32), w0, w1, w2, w3);
         const double u = ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6)) * 0x1p-53;
         noise[i] = 2.0 * u - 1.0;
     }

@@ -1,0 +1,16 @@
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw, "Parallel random numbers: as easy as 1, 2, 3", SC'11): four 32-bit counter words and two key words ->
+// four output words, ten rounds of two 32 x 32 -> 64 bit products.  A pure function of its arguments: no state, the same bits in every launch geometry.
+// Users: elastic.hip (counter word 2 = the field's axis, 0..2; words w0, w1) and augment.hip (counter word 2 = 0x100 + channel; all four words).
+#pragma once
+
+__device__ __forceinline__ void vs_philox4x32_10(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int c3, unsigned int k0, unsigned int k1,
+                                                 unsigned int& w0, unsigned int& w1, unsigned int& w2, unsigned int& w3) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned int)p1; c3 = (unsigned int)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    w0 = c0; w1 = c1; w2 = c2; w3 = c3;
+}

@@ -6,6 +6,8 @@ same names, constructor arguments and dict-in / dict-out protocol, operating on 
     MySpatialTransform        utils/utils.py:927-968   (batchgenerators augment_spatial: elastic deformation — which main_source.py:198 switches off;
                                                         here it needs a noise source chosen, see the class — rotation, scale, random crop)
     Clip, CenterIntensities   utils/utils.py:508-533, 575-618
+    IntensityAugment          no counterpart in the reference's loaders: the batchgenerators / nnU-Net intensity transforms it inherits and leaves off
+                              (noise, blur, brightness, contrast, gamma, mirror), applied after CenterIntensities; intensity_augment is its functional form
 
 The reference runs this chain on 16 CPU workers per loader (skimage resize + scipy map_coordinates of 128^3 volumes: seconds per
 sample); here a sample costs a handful of kernel launches.  One host synchronisation per sample remains: the crop cube's side depends
@@ -436,10 +438,228 @@ class CenterIntensities(BaseTransform):
         return data_dict
 
 
-def train_sample(merge, patch_size, mask_index=None, transform=None, params=None, field="venous", shift=0):
+# ---- intensity augmentation (csrc/augment.hip; DESIGN "Intensity augmentation" holds the rules) --------------------------------------------------------
+_STAT_OPS = ("contrast", "power", "restat", "restat_rec")
+
+
+def _per_channel(v, channels, what):
+    if isinstance(v, (list, tuple, np.ndarray)):
+        if len(v) != channels:
+            raise ValueError("intensity_augment: %s has %d per-channel values for %d channels" % (what, len(v), channels))
+        return list(v)
+    return [v] * channels
+
+
+def _plane_ops(ops_list, channels, c, shape):
+    """the ops of channel c with scalar parameters; gamma becomes power (+ restat from the record of power's input); ops that leave the plane as it is
+    (a channel's parameter None, flip 0) are dropped"""
+    out = []
+    for op in ops_list:
+        name, args = op[0], op[1:]
+        if name == "noise":
+            s, spec = _per_channel(args[0], channels, "noise s")[c], args[1]
+            if s is None:
+                continue
+            if _is_counter(spec):
+                n = (int(spec[0]), int(spec[1]))
+            else:
+                n = torch.from_numpy(spec) if isinstance(spec, np.ndarray) else spec
+                if not isinstance(n, torch.Tensor) or n.dtype != torch.float64 or tuple(n.shape) != (channels,) + shape:
+                    raise TypeError("intensity_augment: noise is a float64 array or tensor of shape %s or a tuple (seed, sample) of ints"
+                                    % ((channels,) + shape,))
+                n = n[c].cuda().contiguous()
+            out.append(("noise", float(s), n))
+        elif name == "blur":
+            sigma = _per_channel(args[0], channels, "blur sigma")[c]
+            if sigma is not None:
+                from . import ops
+                ops.gaussian_weights(sigma)                                   # the range check, before anything is launched
+                out.append(("blur", float(sigma)))
+        elif name == "brightness":
+            m = _per_channel(args[0], channels, "brightness m")[c]
+            if m is not None:
+                out.append(("brightness", float(m)))
+        elif name == "contrast":
+            f = _per_channel(args[0], channels, "contrast f")[c]
+            if f is not None:
+                out.append(("contrast", float(f), bool(args[1]) if len(args) > 1 else True))
+        elif name in ("gamma", "power"):
+            g = _per_channel(args[0], channels, "gamma")[c]
+            if g is not None:
+                invert = bool(args[1]) if len(args) > 1 else False
+                out.append(("power", float(g), invert))
+                if name == "gamma" and (bool(args[2]) if len(args) > 2 else False):
+                    out.append(("restat_rec", invert))
+        elif name == "restat":
+            m0 = _per_channel(args[0], channels, "restat mean0")[c]
+            if m0 is not None:
+                out.append(("restat", float(m0), float(_per_channel(args[1], channels, "restat std0")[c]), bool(args[2]) if len(args) > 2 else False))
+        elif name == "flip":
+            if not 0 <= int(args[0]) <= 7:
+                raise ValueError("intensity_augment: flip mask is 0..7 (z, y, x = 4, 2, 1), got %r" % (args[0],))
+            if int(args[0]):
+                out.append(("flip", int(args[0])))
+        else:
+            raise ValueError("intensity_augment: unknown op %r (noise, blur, brightness, contrast, gamma, power, restat, flip)" % (name,))
+    return out
+
+
+def _augment_plane(x, plane_ops, channel):
+    """One plane through its ops.  Neighbouring ops share a launch (ops.aug_stage) only where the result keeps the bits of the op-by-op chain:
+        [flip] [noise] [brightness] [flip]     point ops, each rounded to fp32 inside the kernel; at most one mirror, on the read
+        contrast | power | restat  [flip]      the op is driven by the record of the stage's input, so nothing may precede it in its stage
+    A stage whose successor needs statistics writes the record of what it stores; after a blur, or at the start, ops.aug_stats makes the same record."""
+    from . import ops
+    cur, rec, rec_power_in, k, n = x, None, None, 0, len(plane_ops)
+    while k < n:
+        name = plane_ops[k][0]
+        if name == "blur":
+            cur, rec, k = ops.gaussian_blur3d(cur, plane_ops[k][1]), None, k + 1
+            continue
+        st = {}
+        if name in _STAT_OPS:
+            if rec is None:
+                rec = ops.aug_stats(cur)
+            op = plane_ops[k]
+            if name == "contrast":
+                st.update(op="contrast", p=op[1], flag=op[2], rec=rec)
+            elif name == "power":
+                st.update(op="power", p=op[1], flag=op[2], rec=rec)
+                rec_power_in = rec
+            elif name == "restat":
+                st.update(op="restat", mean0=op[1], std0=op[2], flag=op[3], rec=rec)
+            else:
+                st.update(op="restat", flag=op[1], rec=rec, rec0=rec_power_in)
+            k += 1
+        else:
+            if name == "flip":
+                st.update(flip=plane_ops[k][1], flip_first=True)
+                k += 1
+            if k < n and plane_ops[k][0] == "noise":
+                st.update(s=plane_ops[k][1], noise=plane_ops[k][2], channel=channel)
+                k += 1
+            if k < n and plane_ops[k][0] == "brightness":
+                st.update(mult=plane_ops[k][1])
+                k += 1
+        if "flip" not in st and k < n and plane_ops[k][0] == "flip":
+            st.update(flip=plane_ops[k][1], flip_first=False)
+            k += 1
+        cur, rec = ops.aug_stage(cur, want_rec=k < n and plane_ops[k][0] in _STAT_OPS, **st)
+    return cur
+
+
+def intensity_augment(x, ops_list):
+    """x: (C, D, H, W) CUDA float32; ops_list: tuples applied in order, a parameter being one value for all channels or a per-channel sequence in which
+    None leaves that channel as it is:
+        ("noise", s, n)                         x + s n; n: the normals, float64 (C, D, H, W) (numpy or tensor), or (seed, sample): Philox on the device
+        ("blur", sigma)                         scipy.ndimage.gaussian_filter(mode="reflect"), 0 < sigma <= 2
+        ("brightness", m)                       x m
+        ("contrast", f, preserve_range=True)    (x - mean) f + mean, clipped to the plane's range
+        ("gamma", g, invert=False, retain_stats=False)      power, then restat to the mean and std of power's input
+        ("power", g, invert=False)              ((x' - min) / (max - min + 1e-7))^g (max - min) + min on x' = -x when invert, negated back
+        ("restat", mean0, std0, invert=False)   (x' - mean) / (std + 1e-8) std0 + mean0
+        ("flip", mask)                          mirror along z / y / x for the bits 4 / 2 / 1
+    Every op is computed in fp64 from the fp32 plane and the fp64 statistics of that plane and rounded to fp32 once; the result has the bits of the
+    single-op calls applied one after another, eagerly and under graph replay.  No call synchronises or reads back.  Without ops: x itself."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+        raise TypeError("intensity_augment: expected a contiguous CUDA float32 tensor (C, D, H, W), got %s %s" % (tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x))))
+    channels, shape = int(x.shape[0]), tuple(int(v) for v in x.shape[1:])
+    plans = [_plane_ops(ops_list, channels, c, shape) for c in range(channels)]
+    if not any(plans):
+        return x
+    planes = [_augment_plane(x[c], plans[c], c) if plans[c] else x[c] for c in range(channels)]
+    return planes[0][None] if channels == 1 else torch.stack(planes)
+
+
+class IntensityAugment:
+    """The batchgenerators / nnU-Net intensity stage on the device: per sample, each behind its own gate, Gaussian noise (p_noise, s in U(noise_s)),
+    Gaussian blur (p_blur; every channel with p_blur_per_channel, sigma in U(blur_sigma)), brightness (p_brightness, m in U(brightness) per channel),
+    contrast (p_contrast, preserve_range), gamma on the inverted image and gamma (p_gamma_inverted, p_gamma; retain_stats), and a mirror per axis
+    (p_mirror).  data_dict[data_key]: (B, C, D, H, W) CUDA float32; data_dict[label_key] receives the mirror and nothing else.
+    `rng`: a numpy RandomState (default: the global one).  The noise source has to be chosen when p_noise > 0:
+      noise="numpy"   the normals are drawn from `rng` (rng.normal(0, 1, plane) per channel) and cross to the device
+      noise="philox"  they are made on the device from (seed, n), n counting this transform's noised samples
+    draw(channels, shape) -> the sample's ops for intensity_augment, drawn from `rng` in the fixed order noise gate, s, [fields]; blur gate, per channel
+    (uniform <= p, sigma); brightness gate, m per channel; contrast gate, f per channel; inverted gamma gate, g per channel; gamma gate, g per channel;
+    one uniform per axis z, y, x.  Every gate is drawn whatever its probability."""
+
+    def __init__(self, data_key="data", label_key="seg", rng=None, noise=None, seed=0, p_noise=0.1, noise_s=(0.0, 0.1), p_blur=0.2, blur_sigma=(0.5, 1.0),
+                 p_blur_per_channel=0.5, p_brightness=0.15, brightness=(0.75, 1.25), p_contrast=0.15, contrast=(0.75, 1.25), preserve_range=True,
+                 p_gamma_inverted=0.1, p_gamma=0.3, gamma=(0.7, 1.5), retain_stats=True, p_mirror=0.5):
+        from .ops import AUG_MAX_SIGMA
+        if noise not in (None, "numpy", "philox"):
+            raise ValueError("IntensityAugment: noise is None, 'numpy' or 'philox', got %r" % (noise,))
+        if p_noise > 0 and noise is None:
+            raise NotImplementedError("IntensityAugment: Gaussian noise needs a noise source: choose noise='numpy' (the normals are drawn from rng) or "
+                                      "noise='philox' (made on the device from seed), or pass p_noise=0")
+        if not 0 < blur_sigma[0] <= blur_sigma[1] <= AUG_MAX_SIGMA:
+            raise ValueError("IntensityAugment: blur takes 0 < sigma[0] <= sigma[1] <= %g, got %r" % (AUG_MAX_SIGMA, blur_sigma))
+        for name, (lo, hi) in (("noise_s", noise_s), ("brightness", brightness), ("contrast", contrast), ("gamma", gamma)):
+            if not (np.isfinite(lo) and np.isfinite(hi) and 0 <= lo <= hi):
+                raise ValueError("IntensityAugment: %s is a range 0 <= lo <= hi, got %r" % (name, (lo, hi)))
+        self.data_key, self.label_key, self.noise, self.seed, self.n_noised = data_key, label_key, noise, int(seed), 0
+        self.p_noise, self.noise_s, self.p_blur, self.blur_sigma, self.p_blur_ch = p_noise, noise_s, p_blur, blur_sigma, p_blur_per_channel
+        self.p_brightness, self.brightness, self.p_contrast, self.contrast, self.preserve_range = p_brightness, brightness, p_contrast, contrast, preserve_range
+        self.p_gamma_inv, self.p_gamma, self.gamma, self.retain_stats, self.p_mirror = p_gamma_inverted, p_gamma, gamma, retain_stats, p_mirror
+        self.rng = rng if rng is not None else np.random
+
+    def _range_val(self, lo, hi):
+        """batchgenerators' contrast / gamma rule: below 1 and above 1 with equal probability"""
+        r = self.rng
+        if r.random_sample() < 0.5 and lo < 1:
+            return r.uniform(lo, 1)
+        return r.uniform(max(lo, 1), hi)
+
+    def draw(self, channels, shape):
+        r, ops_list = self.rng, []
+        if r.uniform() < self.p_noise:
+            s = r.uniform(self.noise_s[0], self.noise_s[1])
+            if self.noise == "numpy":
+                spec = np.stack([r.normal(0.0, 1.0, tuple(shape)) for _ in range(channels)])
+            else:
+                spec = (self.seed, self.n_noised)
+            self.n_noised += 1
+            ops_list.append(("noise", s, spec))
+        if r.uniform() < self.p_blur:
+            ops_list.append(("blur", [r.uniform(self.blur_sigma[0], self.blur_sigma[1]) if r.uniform() <= self.p_blur_ch else None for _ in range(channels)]))
+        if r.uniform() < self.p_brightness:
+            ops_list.append(("brightness", [r.uniform(self.brightness[0], self.brightness[1]) for _ in range(channels)]))
+        if r.uniform() < self.p_contrast:
+            ops_list.append(("contrast", [self._range_val(*self.contrast) for _ in range(channels)], self.preserve_range))
+        if r.uniform() < self.p_gamma_inv:
+            ops_list.append(("gamma", [self._range_val(*self.gamma) for _ in range(channels)], True, self.retain_stats))
+        if r.uniform() < self.p_gamma:
+            ops_list.append(("gamma", [self._range_val(*self.gamma) for _ in range(channels)], False, self.retain_stats))
+        mask = sum(bit for bit in (4, 2, 1) if r.uniform() < self.p_mirror)
+        if mask:
+            ops_list.append(("flip", mask))
+        return ops_list
+
+    def __call__(self, data_dict, params=None):
+        from . import ops
+        data, seg = data_dict.get(self.data_key), data_dict.get(self.label_key)
+        out_d, out_s = [], []
+        for b in range(data.shape[0]):
+            ops_list = params[b] if params is not None else self.draw(int(data.shape[1]), tuple(data.shape[2:]))
+            out_d.append(intensity_augment(data[b].contiguous(), ops_list))
+            if seg is not None:
+                mask = 0
+                for op in ops_list:
+                    if op[0] == "flip":
+                        mask ^= int(op[1])                   # mirrors compose by exclusive or
+                out_s.append(ops.aug_flip(seg[b].contiguous(), mask) if mask else seg[b])
+        data_dict[self.data_key] = out_d[0][None] if len(out_d) == 1 else torch.stack(out_d)
+        if seg is not None:
+            data_dict[self.label_key] = out_s[0][None] if len(out_s) == 1 else torch.stack(out_s)
+        return data_dict
+
+
+def train_sample(merge, patch_size, mask_index=None, transform=None, params=None, field="venous", shift=0, intensity=None, intensity_params=None):
     """One training sample through main_source.py:191-211 on the device: merge (D, H, W, >= 2) CUDA float32 tensor (what
     NumpyLoader_Multi_merge loads) -> (image (1, 1, P, P, P), label (1, 1, P, P, P)).  `transform`: a MySpatialTransform (None: no
-    augmentation, --no_aug); `params`: its per-sample (angles, scale, centre, modified[, (alpha, sigma, noise_spec)]) instead of random draws."""
+    augmentation, --no_aug); `params`: its per-sample (angles, scale, centre, modified[, (alpha, sigma, noise_spec)]) instead of random draws.
+    `intensity`: an IntensityAugment over (field, field + "_pancreas") applied after CenterIntensities (None: nothing more is launched);
+    `intensity_params`: its ops for this sample (IntensityAugment.draw) instead of random draws."""
     img = merge[..., 0].contiguous()
     lab = merge[..., 1].contiguous()
     if mask_index is not None:
@@ -451,4 +671,9 @@ def train_sample(merge, patch_size, mask_index=None, transform=None, params=None
         d = transform(d, params=None if params is None else [params])
     d = Clip([field], new_min=-200, new_max=400)(d)
     d = CenterIntensities([field], subtrahend=100, divisor=300)(d)
+    if intensity is not None:
+        if (intensity.data_key, intensity.label_key) != (field, field + "_pancreas"):
+            raise ValueError("train_sample: the intensity transform reads %r / %r, the sample is under %r / %r"
+                             % (intensity.data_key, intensity.label_key, field, field + "_pancreas"))
+        d = intensity(d, params=None if intensity_params is None else [intensity_params])
     return d[field], d[field + "_pancreas"]

@@ -108,6 +108,11 @@ class DeviceCaseLoader:
                 do_rotation=True, sigma=(10, 30.), angle_x=(-0.2, 0.2), angle_y=(-0.2, 0.2), angle_z=(-0.2, 0.2), border_mode_data="constant",
                 border_cval_data=-1024, data_key=IMG_KEY, p_el_per_sample=p_el, label_key=LABEL_KEY, p_scale_per_sample=1, p_rot_per_sample=1,
                 rng=np.random.RandomState(seed + 1000 * rank), **elastic)
+        self.intensity = None
+        if train and getattr(args, "aug_intensity", False) and not getattr(args, "no_aug", False):
+            # --aug_intensity: nnU-Net's intensity stage after CenterIntensities; its own generator, so the spatial draws keep their stream
+            self.intensity = data_gpu.IntensityAugment(IMG_KEY, LABEL_KEY, rng=np.random.RandomState(seed + 1000 * rank + 500), noise="philox",
+                                                       seed=seed + 1000 * rank)
         self._dg = data_gpu
 
     def set_epoch(self, epoch):
@@ -130,7 +135,8 @@ class DeviceCaseLoader:
             imgs, labs = [], []
             for i in order[b * self.bs:(b + 1) * self.bs]:
                 merge = torch.from_numpy(np.load(os.path.join(self.root, self.names[i])).astype(np.float32)).cuda(non_blocking=True)
-                img, lab = self._dg.train_sample(merge, self.patch, self.mask_index, self.transform, field=IMG_KEY, shift=self.shift)
+                extra = {} if self.intensity is None else {"intensity": self.intensity}
+                img, lab = self._dg.train_sample(merge, self.patch, self.mask_index, self.transform, field=IMG_KEY, shift=self.shift, **extra)
                 imgs.append(img); labs.append(lab)
             yield {IMG_KEY: torch.cat(imgs), LABEL_KEY: torch.cat(labs)}
 
@@ -963,9 +969,11 @@ def _probability(text):
 
 
 def check_aug_flags(parser, a):
-    """--aug_elastic deforms the augmented training samples: with --no_aug there are none"""
+    """--aug_elastic and --aug_intensity act on the augmented training samples: with --no_aug there are none"""
     if getattr(a, "aug_elastic", 0.0) > 0 and getattr(a, "no_aug", False):
         parser.error("--aug_elastic deforms the augmented training samples: it cannot be combined with --no_aug")
+    if getattr(a, "aug_intensity", False) and getattr(a, "no_aug", False):
+        parser.error("--aug_intensity changes the grey values of the augmented training samples: it cannot be combined with --no_aug")
     return a
 
 
@@ -977,6 +985,9 @@ def add_native_flags(parser):
     g.add_argument("--aug_elastic", type=_probability, default=0.0, metavar="P", help="with --real_data: elastic deformation of a training sample with "
                    "probability P before rotation and scale (augment_spatial's first stage with the alpha=(0, 500), sigma=(10, 30) the reference's entry "
                    "points pass, noise from Philox on the device: data_gpu.MySpatialTransform(noise='philox')); 0 = off, the reference's setting")
+    g.add_argument("--aug_intensity", action="store_true", help="with --real_data: the nnU-Net intensity stage on every training sample after "
+                   "CenterIntensities — Gaussian noise, Gaussian blur, brightness, contrast, gamma (inverted and plain, statistics retained) and a "
+                   "mirror per axis, each behind its gate, on the device (data_gpu.IntensityAugment(noise='philox')); off: the reference's setting")
     g.add_argument("--size", type=int, default=128, help="cubic patch side (reference: patch_size 128, main_source.py:117)")
     g.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "fp16"], help="kernel storage dtype")
     g.add_argument("--synthetic_train", type=int, default=16)

@@ -3053,6 +3053,118 @@ def to_native(src, geometry, interp="linear", want_prob=False):
     return res
 
 
+# ---- intensity augmentation (csrc/augment.hip; the transform lives in data_gpu.py) ---------------------------------------------------------------------
+AUG_MAX_SIGMA = 2.0                 # radius int(4 sigma + 0.5) <= 8: what the blur kernel's LDS tile is sized for
+AUG_OPS = {"none": 0, "contrast": 1, "power": 2, "restat": 3}
+
+
+def _aug_planes(x, what):
+    """a contiguous CUDA float32 tensor (..., D, H, W) -> (planes, d, h, w)"""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() < 3:
+        raise TypeError("%s: a float32 tensor (..., D, H, W), got %s %s" % (what, getattr(x, "dtype", type(x)), tuple(getattr(x, "shape", ()))))
+    d, h, w = (int(v) for v in x.shape[-3:])
+    if x.numel() == 0 or d * h * w >= 2 ** 31:
+        raise ValueError("%s: an empty tensor or a plane of 2^31 voxels or more, shape %s" % (what, tuple(x.shape)))
+    if not x.is_contiguous():
+        raise ValueError("%s: the tensor must be contiguous" % what)
+    _require_cuda(x)
+    return x.numel() // (d * h * w), d, h, w
+
+
+def _aug_workspace(planes, d, h, w, device):
+    return torch.empty(int(lib.vs_aug_stats_workspace_bytes(planes, d, h, w)) // 8, dtype=torch.float64, device=device)
+
+
+def aug_stats(x):
+    """{min, max, mean, population std} of every (D, H, W) plane of a float32 tensor (..., D, H, W) -> fp64 (..., 4) on the device.  fp64 sums shifted by
+    the plane's first voxel, over a fixed chunking of the linear voxel index in chunk order: a function of the plane's bits alone (two launches, no
+    atomics, no synchronisation) — the record vs_aug_stage's epilogue writes for the plane it stores."""
+    planes, d, h, w = _aug_planes(x, "aug_stats")
+    rec = torch.empty(tuple(x.shape[:-3]) + (4,), dtype=torch.float64, device=x.device)
+    ws = _aug_workspace(planes, d, h, w, x.device)
+    check(lib.vs_aug_stats(x.data_ptr(), rec.data_ptr(), ws.data_ptr(), planes, d, h, w, _stream()), "aug_stats")
+    return rec
+
+
+def philox_normal(shape, seed, sample, channel=0):
+    """the standard normals of one plane `shape` = (D, H, W), fp64 on the device: Philox4x32-10 under key `seed` and counter (pair, 0x100 + channel,
+    sample), Box-Muller in fp64 (vs_aug_normal_philox) — what a noise stage with the source (seed, sample) adds, times s"""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError("philox_normal: shape is (D, H, W), got %r" % (shape,))
+    out = torch.empty(shape, dtype=torch.float64, device="cuda")
+    check(lib.vs_aug_normal_philox(out.data_ptr(), *shape, int(seed) & (2 ** 64 - 1), int(sample) & (2 ** 64 - 1), int(channel), _stream()),
+          "aug_normal_philox")
+    return out
+
+
+def gaussian_weights(sigma):
+    """scipy.ndimage's _gaussian_kernel1d(sigma, 0, int(4 sigma + 0.5)) from the centre outwards: w[k] is the weight of taps -k and +k (host, numpy)"""
+    import numpy as np
+    sigma = float(sigma)
+    if not 0.0 < sigma <= AUG_MAX_SIGMA:
+        raise ValueError("gaussian blur: 0 < sigma <= %g (radius <= 8), got %r" % (AUG_MAX_SIGMA, sigma))
+    radius = int(4.0 * sigma + 0.5)
+    k = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[radius:], dtype=np.float64)
+
+
+def blur_tile(sigma):
+    """the (z, y, x) tile of outputs one workgroup of the blur kernel computes at this sigma"""
+    t = (_ctypes.c_int * 3)()
+    check(lib.vs_aug_blur_tile(float(sigma), t), "aug_blur_tile")
+    return tuple(t)
+
+
+def gaussian_blur3d(x, sigma):
+    """scipy.ndimage.gaussian_filter(x, sigma, mode="reflect", truncate=4) of one float32 volume (D, H, W): passes along z, y, x, fp64 accumulation,
+    rounded to fp32 after each; one launch, the three passes over an LDS tile (vs_aug_blur).  0 < sigma <= 2."""
+    planes, d, h, w = _aug_planes(x, "gaussian_blur3d")
+    if x.dim() != 3:
+        raise ValueError("gaussian_blur3d: one volume (D, H, W), got shape %s" % (tuple(x.shape),))
+    wts = gaussian_weights(sigma)
+    out = torch.empty_like(x)
+    check(lib.vs_aug_blur(x.data_ptr(), out.data_ptr(), d, h, w, float(sigma), wts.ctypes.data, _stream()), "aug_blur")
+    return out
+
+
+def aug_flip(x, mask):
+    """every (D, H, W) plane of a float32 tensor (..., D, H, W) mirrored along z / y / x for the bits 4 / 2 / 1 of mask: a copy (vs_aug_flip)"""
+    planes, d, h, w = _aug_planes(x, "aug_flip")
+    mask = int(mask)
+    if not 0 <= mask <= 7:
+        raise ValueError("aug_flip: mask is 0..7 (z, y, x = 4, 2, 1), got %r" % (mask,))
+    out = torch.empty_like(x)
+    check(lib.vs_aug_flip(x.data_ptr(), out.data_ptr(), planes, d, h, w, mask, _stream()), "aug_flip")
+    return out
+
+
+def aug_stage(x, flip=0, flip_first=False, noise=None, s=0.0, channel=0, mult=None, op="none", p=0.0, flag=False, rec=None, rec0=None, mean0=0.0,
+              std0=1.0, want_rec=False):
+    """One pass of vs_aug_stage over one float32 volume (D, H, W) -> (y, record of y or None).  noise: None, an fp64 device tensor of x's shape, or a
+    tuple (seed, sample) for the Philox normals of `channel`; rec / rec0: fp64 records (4,) on the device (aug_stats); see include/vaeseg.h for the
+    order of the steps.  One launch, two with want_rec; nothing is synchronised or read back."""
+    planes, d, h, w = _aug_planes(x, "aug_stage")
+    if x.dim() != 3:
+        raise ValueError("aug_stage: one volume (D, H, W), got shape %s" % (tuple(x.shape),))
+    mode, narr, seed, sample = 0, None, 0, 0
+    if isinstance(noise, tuple):
+        mode, seed, sample = 2, int(noise[0]) & (2 ** 64 - 1), int(noise[1]) & (2 ** 64 - 1)
+    elif noise is not None:
+        if not (isinstance(noise, torch.Tensor) and noise.dtype == torch.float64 and noise.shape == x.shape and noise.is_cuda and noise.is_contiguous()):
+            raise TypeError("aug_stage: noise is a contiguous CUDA float64 tensor of shape %s or a tuple (seed, sample)" % (tuple(x.shape),))
+        mode, narr = 1, noise
+    y = torch.empty_like(x)
+    rec_out = torch.empty(4, dtype=torch.float64, device=x.device) if want_rec else None
+    ws = _aug_workspace(1, d, h, w, x.device) if want_rec else None
+    check(lib.vs_aug_stage(x.data_ptr(), y.data_ptr(), d, h, w, int(flip), int(bool(flip_first)), mode, _p(narr), float(s), seed, sample, int(channel),
+                           int(mult is not None), 1.0 if mult is None else float(mult), AUG_OPS[op], float(p), int(bool(flag)), _p(rec), _p(rec0),
+                           float(mean0), float(std0), _p(rec_out), _p(ws), _stream()), "aug_stage")
+    return y, rec_out
+
+
 def instnorm_stats(x):
     n, c = x.shape[0], x.shape[-1]
     st = _new_stats(n, c, x.device)
