@@ -493,6 +493,22 @@ int vs_aug_blur_tile(double sigma, int* tile3);
 int vs_aug_blur(const float* x, float* y, int d, int h, int w, double sigma, const double* weights, void* stream);
 int vs_aug_flip(const float* x, float* y, int planes, int d, int h, int w, int mask, void* stream);
 
+/* ---- zoom with edge boundaries: simulated low resolution (csrc/lowres.hip) ------------------------------------------------------------------
+ * y (dd, dh, dw) = scipy.ndimage.zoom(x.astype(float64), out / in, order, mode="nearest", grid_mode=True) of one fp32 volume x (sd, sh, sw), clipped to
+ * [min x, max x] when clip != 0 and order > 0, rounded to fp32 once (DESIGN 3.17 states every rule).  Output index o of an axis of input length m and
+ * output length n reads c = (o + 0.5) zoom - 0.5 with zoom = m / n one fp64 division.  order 0: floor(c + 0.5); order 1: two taps per axis, clamped to
+ * the axis; order 3: per axis (z, y, x) the line padded by 12 edge values in LDS, scipy's mirror-started order-3 recursion, four taps at c + 12, fp64
+ * between the passes.  nnU-Net's simulated low resolution is two calls: down with order 0, up with order 3 and clip.
+ * workspace: vs_zoom_edge_workspace_bytes(...) bytes, 8-byte aligned (0 for arguments vs_zoom_edge refuses); needed for order 3 and for a clip.
+ * vs_zoom_edge_bundle(m, n): the lines one workgroup of an order-3 pass holds at input length m and output length n (64, 32, 16 or 8; 0 outside 1..512).
+ * Launches: order 0 and 1: 1, order 3: 3; a clip adds vs_aug_stats' 2, whose record of x (in the workspace) supplies the bounds on the device.  x and y
+ * are different buffers.  A null pointer, an order other than 0, 1, 3: VS_EINVAL; an empty volume, one of 2^31 voxels or more, or for order 3 an axis
+ * longer than 512 on either side: VS_ESHAPE; buffers not 4-byte (fp32) / 8-byte (workspace) aligned: VS_EALIGN; all answered on the host before any
+ * launch.  No atomics, no memset, nothing allocated, synchronised or read back: the same bits on every run, in both builds and under graph replay. */
+long long vs_zoom_edge_workspace_bytes(int sd, int sh, int sw, int dd, int dh, int dw, int order);
+int vs_zoom_edge_bundle(int m, int n);
+int vs_zoom_edge(const float* x, float* y, int sd, int sh, int sw, int dd, int dh, int dw, int order, int clip, void* workspace, void* stream);
+
 /* ---- layout glue at the NCDHW boundary ----------------------------------------------------------- */
 /* planar fp32 [N][c_src][V] -> channels-last [N][V][c_pad] (zero-filled channels >= c_src) */
 int vs_pack_planar(const float* src, void* dst, int n, long long voxels, int c_src, int c_pad, int dtype, void* stream);

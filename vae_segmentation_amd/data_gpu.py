@@ -7,7 +7,7 @@ same names, constructor arguments and dict-in / dict-out protocol, operating on 
                                                         here it needs a noise source chosen, see the class — rotation, scale, random crop)
     Clip, CenterIntensities   utils/utils.py:508-533, 575-618
     IntensityAugment          no counterpart in the reference's loaders: the batchgenerators / nnU-Net intensity transforms it inherits and leaves off
-                              (noise, blur, brightness, contrast, gamma, mirror), applied after CenterIntensities; intensity_augment is its functional form
+                              (noise, blur, brightness, contrast, simulated low resolution, gamma, mirror), applied after CenterIntensities; intensity_augment is its functional form
 
 The reference runs this chain on 16 CPU workers per loader (skimage resize + scipy map_coordinates of 128^3 volumes: seconds per
 sample); here a sample costs a handful of kernel launches.  One host synchronisation per sample remains: the crop cube's side depends
@@ -450,6 +450,21 @@ def _per_channel(v, channels, what):
     return [v] * channels
 
 
+def lowres_target_shape(shape, zoom, ignore_axes=()):
+    """the shape nnU-Net's simulated low resolution down-samples `shape` to: np.round(shape * zoom).astype(int) per axis (round-half-even), the axes in
+    ignore_axes keeping their length.  ValueError when an axis would vanish — before anything is launched.  Host arithmetic only."""
+    shape, ignore = tuple(int(v) for v in shape), tuple(int(a) for a in ignore_axes)
+    zoom = float(zoom)
+    if not (np.isfinite(zoom) and zoom > 0):
+        raise ValueError("lowres_target_shape: zoom is a positive number, got %r" % (zoom,))
+    if any(not 0 <= a < len(shape) for a in ignore):
+        raise ValueError("lowres_target_shape: ignore_axes index the %d axes of the shape, got %r" % (len(shape), ignore_axes))
+    out = tuple(s if a in ignore else int(np.round(np.float64(s) * np.float64(zoom))) for a, s in enumerate(shape))
+    if min(out) < 1:
+        raise ValueError("lowres_target_shape: an axis of %s vanishes at zoom %r (target %s)" % (shape, zoom, out))
+    return out
+
+
 def _plane_ops(ops_list, channels, c, shape):
     """the ops of channel c with scalar parameters; gamma becomes power (+ restat from the record of power's input); ops that leave the plane as it is
     (a channel's parameter None, flip 0) are dropped"""
@@ -475,6 +490,17 @@ def _plane_ops(ops_list, channels, c, shape):
                 from . import ops
                 ops.gaussian_weights(sigma)                                   # the range check, before anything is launched
                 out.append(("blur", float(sigma)))
+        elif name == "lowres":
+            zoom = _per_channel(args[0], channels, "lowres zoom")[c]
+            order_down, order_up = (int(args[1]) if len(args) > 1 else 0), (int(args[2]) if len(args) > 2 else 3)
+            from . import ops
+            if order_down not in ops.ZOOM_EDGE_ORDERS or order_up not in ops.ZOOM_EDGE_ORDERS:
+                raise ValueError("intensity_augment: lowres orders are 0, 1 or 3, got %r" % ((order_down, order_up),))
+            if zoom is not None:
+                target = lowres_target_shape(shape, zoom, args[3] if len(args) > 3 else ())      # the range check, before anything is launched
+                if 3 in (order_down, order_up) and max(shape + target) > ops.ZOOM_EDGE_MAX_LEN:
+                    raise ValueError("intensity_augment: lowres with order 3 takes axes of at most %d voxels, got %s" % (ops.ZOOM_EDGE_MAX_LEN, shape))
+                out.append(("lowres", target, order_down, order_up))
         elif name == "brightness":
             m = _per_channel(args[0], channels, "brightness m")[c]
             if m is not None:
@@ -500,7 +526,7 @@ def _plane_ops(ops_list, channels, c, shape):
             if int(args[0]):
                 out.append(("flip", int(args[0])))
         else:
-            raise ValueError("intensity_augment: unknown op %r (noise, blur, brightness, contrast, gamma, power, restat, flip)" % (name,))
+            raise ValueError("intensity_augment: unknown op %r (noise, blur, lowres, brightness, contrast, gamma, power, restat, flip)" % (name,))
     return out
 
 
@@ -508,13 +534,17 @@ def _augment_plane(x, plane_ops, channel):
     """One plane through its ops.  Neighbouring ops share a launch (ops.aug_stage) only where the result keeps the bits of the op-by-op chain:
         [flip] [noise] [brightness] [flip]     point ops, each rounded to fp32 inside the kernel; at most one mirror, on the read
         contrast | power | restat  [flip]      the op is driven by the record of the stage's input, so nothing may precede it in its stage
-    A stage whose successor needs statistics writes the record of what it stores; after a blur, or at the start, ops.aug_stats makes the same record."""
+    A stage whose successor needs statistics writes the record of what it stores; after a blur or a lowres (stages of their own), or at the start,
+    ops.aug_stats makes the same record."""
     from . import ops
     cur, rec, rec_power_in, k, n = x, None, None, 0, len(plane_ops)
     while k < n:
         name = plane_ops[k][0]
         if name == "blur":
             cur, rec, k = ops.gaussian_blur3d(cur, plane_ops[k][1]), None, k + 1
+            continue
+        if name == "lowres":
+            cur, rec, k = ops.simulate_lowres(cur, *plane_ops[k][1:]), None, k + 1
             continue
         st = {}
         if name in _STAT_OPS:
@@ -553,6 +583,7 @@ def intensity_augment(x, ops_list):
     None leaves that channel as it is:
         ("noise", s, n)                         x + s n; n: the normals, float64 (C, D, H, W) (numpy or tensor), or (seed, sample): Philox on the device
         ("blur", sigma)                         scipy.ndimage.gaussian_filter(mode="reflect"), 0 < sigma <= 2
+        ("lowres", zoom, order_down=0, order_up=3, ignore_axes=())      ops.simulate_lowres to lowres_target_shape(plane, zoom, ignore_axes) and back
         ("brightness", m)                       x m
         ("contrast", f, preserve_range=True)    (x - mean) f + mean, clipped to the plane's range
         ("gamma", g, invert=False, retain_stats=False)      power, then restat to the mean and std of power's input
@@ -581,12 +612,17 @@ class IntensityAugment:
       noise="philox"  they are made on the device from (seed, n), n counting this transform's noised samples
     draw(channels, shape) -> the sample's ops for intensity_augment, drawn from `rng` in the fixed order noise gate, s, [fields]; blur gate, per channel
     (uniform <= p, sigma); brightness gate, m per channel; contrast gate, f per channel; inverted gamma gate, g per channel; gamma gate, g per channel;
-    one uniform per axis z, y, x.  Every gate is drawn whatever its probability."""
+    one uniform per axis z, y, x.  Every gate is drawn whatever its probability — with one exception:
+    nnU-Net's simulated low resolution (p_lowres; every channel with p_lowres_per_channel, zoom in U(lowres_zoom), down with lowres_orders[0] and back up with
+    lowres_orders[1], the axes in lowres_ignore_axes keeping their resolution) sits between contrast and the inverted gamma, and its draws — the gate, then
+    per channel (uniform < p_lowres_per_channel, for a channel taken its zoom) — are made only when p_lowres > 0, so that a transform built without the
+    argument keeps the random stream it had before the stage existed."""
 
     def __init__(self, data_key="data", label_key="seg", rng=None, noise=None, seed=0, p_noise=0.1, noise_s=(0.0, 0.1), p_blur=0.2, blur_sigma=(0.5, 1.0),
                  p_blur_per_channel=0.5, p_brightness=0.15, brightness=(0.75, 1.25), p_contrast=0.15, contrast=(0.75, 1.25), preserve_range=True,
-                 p_gamma_inverted=0.1, p_gamma=0.3, gamma=(0.7, 1.5), retain_stats=True, p_mirror=0.5):
-        from .ops import AUG_MAX_SIGMA
+                 p_gamma_inverted=0.1, p_gamma=0.3, gamma=(0.7, 1.5), retain_stats=True, p_mirror=0.5, p_lowres=0.0, lowres_zoom=(0.5, 1.0),
+                 p_lowres_per_channel=0.5, lowres_orders=(0, 3), lowres_ignore_axes=()):
+        from .ops import AUG_MAX_SIGMA, ZOOM_EDGE_ORDERS
         if noise not in (None, "numpy", "philox"):
             raise ValueError("IntensityAugment: noise is None, 'numpy' or 'philox', got %r" % (noise,))
         if p_noise > 0 and noise is None:
@@ -597,6 +633,14 @@ class IntensityAugment:
         for name, (lo, hi) in (("noise_s", noise_s), ("brightness", brightness), ("contrast", contrast), ("gamma", gamma)):
             if not (np.isfinite(lo) and np.isfinite(hi) and 0 <= lo <= hi):
                 raise ValueError("IntensityAugment: %s is a range 0 <= lo <= hi, got %r" % (name, (lo, hi)))
+        if not (len(lowres_zoom) == 2 and 0 < lowres_zoom[0] <= lowres_zoom[1] <= 1):
+            raise ValueError("IntensityAugment: lowres_zoom is a range 0 < lo <= hi <= 1, got %r" % (lowres_zoom,))
+        if len(lowres_orders) != 2 or any(o not in ZOOM_EDGE_ORDERS for o in lowres_orders):
+            raise ValueError("IntensityAugment: lowres_orders are (down, up), each 0, 1 or 3, got %r" % (lowres_orders,))
+        if any(a not in (0, 1, 2) for a in lowres_ignore_axes):
+            raise ValueError("IntensityAugment: lowres_ignore_axes index the axes (0, 1, 2) of a plane, got %r" % (lowres_ignore_axes,))
+        self.p_lowres, self.lowres_zoom, self.p_lowres_ch = p_lowres, tuple(lowres_zoom), p_lowres_per_channel
+        self.lowres_orders, self.lowres_ignore_axes = tuple(int(o) for o in lowres_orders), tuple(int(a) for a in lowres_ignore_axes)
         self.data_key, self.label_key, self.noise, self.seed, self.n_noised = data_key, label_key, noise, int(seed), 0
         self.p_noise, self.noise_s, self.p_blur, self.blur_sigma, self.p_blur_ch = p_noise, noise_s, p_blur, blur_sigma, p_blur_per_channel
         self.p_brightness, self.brightness, self.p_contrast, self.contrast, self.preserve_range = p_brightness, brightness, p_contrast, contrast, preserve_range
@@ -626,6 +670,9 @@ class IntensityAugment:
             ops_list.append(("brightness", [r.uniform(self.brightness[0], self.brightness[1]) for _ in range(channels)]))
         if r.uniform() < self.p_contrast:
             ops_list.append(("contrast", [self._range_val(*self.contrast) for _ in range(channels)], self.preserve_range))
+        if self.p_lowres > 0 and r.uniform() < self.p_lowres:           # the one gate that is not drawn when its probability is 0 (class docstring)
+            ops_list.append(("lowres", [r.uniform(self.lowres_zoom[0], self.lowres_zoom[1]) if r.uniform() < self.p_lowres_ch else None
+                                        for _ in range(channels)], self.lowres_orders[0], self.lowres_orders[1], self.lowres_ignore_axes))
         if r.uniform() < self.p_gamma_inv:
             ops_list.append(("gamma", [self._range_val(*self.gamma) for _ in range(channels)], True, self.retain_stats))
         if r.uniform() < self.p_gamma:

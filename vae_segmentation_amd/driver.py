@@ -111,8 +111,10 @@ class DeviceCaseLoader:
         self.intensity = None
         if train and getattr(args, "aug_intensity", False) and not getattr(args, "no_aug", False):
             # --aug_intensity: nnU-Net's intensity stage after CenterIntensities; its own generator, so the spatial draws keep their stream
+            p_lr = float(getattr(args, "aug_lowres", 0.0) or 0.0)            # --aug_lowres: the stage's simulated low resolution, off unless asked for
+            lowres = {"p_lowres": p_lr} if p_lr > 0 else {}
             self.intensity = data_gpu.IntensityAugment(IMG_KEY, LABEL_KEY, rng=np.random.RandomState(seed + 1000 * rank + 500), noise="philox",
-                                                       seed=seed + 1000 * rank)
+                                                       seed=seed + 1000 * rank, **lowres)
         self._dg = data_gpu
 
     def set_epoch(self, epoch):
@@ -974,6 +976,8 @@ def check_aug_flags(parser, a):
         parser.error("--aug_elastic deforms the augmented training samples: it cannot be combined with --no_aug")
     if getattr(a, "aug_intensity", False) and getattr(a, "no_aug", False):
         parser.error("--aug_intensity changes the grey values of the augmented training samples: it cannot be combined with --no_aug")
+    if getattr(a, "aug_lowres", 0.0) > 0 and not getattr(a, "aug_intensity", False):
+        parser.error("--aug_lowres is a stage of the intensity augmentation: it needs --aug_intensity")
     return a
 
 
@@ -988,6 +992,9 @@ def add_native_flags(parser):
     g.add_argument("--aug_intensity", action="store_true", help="with --real_data: the nnU-Net intensity stage on every training sample after "
                    "CenterIntensities — Gaussian noise, Gaussian blur, brightness, contrast, gamma (inverted and plain, statistics retained) and a "
                    "mirror per axis, each behind its gate, on the device (data_gpu.IntensityAugment(noise='philox')); off: the reference's setting")
+    g.add_argument("--aug_lowres", type=_probability, default=0.0, metavar="P", help="with --aug_intensity: nnU-Net's simulated low resolution of a training "
+                   "sample with probability P (nnU-Net: 0.25), between contrast and the gammas — per channel with probability 0.5 a zoom from U(0.5, 1), "
+                   "down by nearest neighbour, back up by a cubic spline with edge boundaries, clipped, on the device (ops.simulate_lowres); 0 = off")
     g.add_argument("--size", type=int, default=128, help="cubic patch side (reference: patch_size 128, main_source.py:117)")
     g.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "fp16"], help="kernel storage dtype")
     g.add_argument("--synthetic_train", type=int, default=16)

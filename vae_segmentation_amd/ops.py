@@ -3165,6 +3165,61 @@ def aug_stage(x, flip=0, flip_first=False, noise=None, s=0.0, channel=0, mult=No
     return y, rec_out
 
 
+# ---- zoom with edge boundaries, simulated low resolution (csrc/lowres.hip) ---------------------------------------------------------------
+ZOOM_EDGE_ORDERS = (0, 1, 3)
+ZOOM_EDGE_MAX_LEN = 512             # order 3: the longest line a workgroup's LDS bundle holds
+
+
+def zoom_edge_bundle(m, n):
+    """the lines one workgroup of an order-3 pass holds at input length m and output length n"""
+    return int(lib.vs_zoom_edge_bundle(int(m), int(n)))
+
+
+def _zoom_edge_shape(shape, what):
+    try:
+        out = tuple(int(v) for v in shape)
+    except TypeError:
+        raise TypeError("%s: a shape (D, H, W), got %r" % (what, shape))
+    if len(out) != 3 or min(out) < 1:
+        raise ValueError("%s: a shape (D, H, W) of positive lengths, got %r" % (what, shape))
+    return out
+
+
+def zoom_edge(x, out_shape, order=3, clip=True):
+    """scipy.ndimage.zoom(x.astype(float64), out / in, order=order, mode="nearest", grid_mode=True) of one float32 volume (D, H, W), clipped to
+    [x.min(), x.max()] when clip (and order > 0), rounded to float32 once.  order 0, 1 or 3; order 3: every axis of x and of out_shape at most 512.
+    One launch for orders 0 and 1, three for order 3, two more for the clip's bounds, which stay on the device; nothing is synchronised or read back."""
+    planes, d, h, w = _aug_planes(x, "zoom_edge")
+    if x.dim() != 3:
+        raise ValueError("zoom_edge: one volume (D, H, W), got shape %s" % (tuple(x.shape),))
+    out_shape = _zoom_edge_shape(out_shape, "zoom_edge")
+    if order not in ZOOM_EDGE_ORDERS:
+        raise ValueError("zoom_edge: order is 0, 1 or 3, got %r" % (order,))
+    order = int(order)
+    if order == 3 and max((d, h, w) + out_shape) > ZOOM_EDGE_MAX_LEN:
+        raise ValueError("zoom_edge: order 3 takes axes of at most %d voxels, got %s -> %s" % (ZOOM_EDGE_MAX_LEN, (d, h, w), out_shape))
+    if out_shape[0] * out_shape[1] * out_shape[2] >= 2 ** 31:
+        raise ValueError("zoom_edge: an output of 2^31 voxels or more, shape %s" % (out_shape,))
+    y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    ws = torch.empty(int(lib.vs_zoom_edge_workspace_bytes(d, h, w, *out_shape, order)) // 8, dtype=torch.float64, device=x.device)
+    check(lib.vs_zoom_edge(x.data_ptr(), y.data_ptr(), d, h, w, *out_shape, order, int(bool(clip)), ws.data_ptr(), _stream()), "zoom_edge")
+    return y
+
+
+def simulate_lowres(x, target_shape, order_down=0, order_up=3):
+    """nnU-Net's simulated low resolution of one float32 volume (D, H, W): zoom_edge down to target_shape (order_down, clipped when order_down > 0), then
+    zoom_edge back to x's shape (order_up, clipped to the down-sampled volume's range when order_up > 0).  The bits of the two calls."""
+    planes, d, h, w = _aug_planes(x, "simulate_lowres")
+    if x.dim() != 3:
+        raise ValueError("simulate_lowres: one volume (D, H, W), got shape %s" % (tuple(x.shape),))
+    target_shape = _zoom_edge_shape(target_shape, "simulate_lowres")
+    for order in (order_down, order_up):
+        if order not in ZOOM_EDGE_ORDERS:
+            raise ValueError("simulate_lowres: an order is 0, 1 or 3, got %r" % (order,))
+    t = zoom_edge(x, target_shape, order_down, clip=order_down > 0)
+    return zoom_edge(t, (d, h, w), order_up, clip=order_up > 0)
+
+
 def instnorm_stats(x):
     n, c = x.shape[0], x.shape[-1]
     st = _new_stats(n, c, x.device)
