@@ -801,6 +801,21 @@ int vs_linear_perm_out_bwd(const float* z, const float* wgt, const void* gy, int
 /* z = mean + noise*std*scale  (joint_model.py:248) ; bwd: gmean = gz, gstd = gz*noise*scale */
 int vs_reparam_fwd(const float* mean, const float* std_, const float* noise, float scale, float* z, long long count, void* stream);
 int vs_reparam_bwd(const float* gz, const float* noise, float scale, float* gmean, float* gstd, long long count, void* stream);
+/* The latent's noise drawn on the device.  A latent STREAM is (seed, draw), two unsigned 64-bit words.  Element i < count of draw t, pair q = i >> 1:
+ * Philox4x32-10 (csrc/philox.h) under key (seed low 32, seed high 32) and counter (q, t low 32, 0x200, t high 32); u1, u2 and r = sqrt(-2 ln u1) as
+ * vs_aug_normal_philox forms them, in fp64; even i takes r cos(2 pi u2), odd i takes r sin(2 pi u2), rounded to fp32 once; an odd count uses only the
+ * cosine of its last pair.  Counter word 2 = 0x200 keeps the stream apart from the elastic one (0 .. 2) and the augmentation's (0x100 + channel).
+ *   vs_latent_normal_philox  noise[count] of the stream (seed, draw), both host arguments
+ *   vs_reparam_philox_fwd    reads state[0] = seed and state[1] = draw from DEVICE memory, writes the normals to noise_out and z = mean + noise*std*scale
+ *                            with vs_reparam_fwd's arithmetic (the same bits for that noise_out); backward is vs_reparam_bwd on noise_out
+ *   vs_latent_advance        state[1] += 1, one thread, a launch of its own: on the stream of the forward it runs after every read of state[1]
+ * A captured vs_reparam_philox_fwd + vs_latent_advance pair therefore draws a fresh sample on every replay.  Null pointer: VS_EINVAL; count <= 0 or
+ * count >= 2^31: VS_ESHAPE; state not 8-byte, an fp32 buffer not 4-byte aligned: VS_EALIGN; all answered on the host before any launch.  No atomics, no
+ * memset, nothing allocated, synchronised or read back. */
+int vs_latent_normal_philox(float* noise, long long count, unsigned long long seed, unsigned long long draw, void* stream);
+int vs_reparam_philox_fwd(const float* mean, const float* std_, const unsigned long long* state, float scale, float* z, float* noise_out,
+                          long long count, void* stream);
+int vs_latent_advance(unsigned long long* state, void* stream);
 /* out = mean_b 0.5*(sum std^2 + sum mean^2 - 2 sum log(std+1e-5))     (utils/evaluation.py:42-45) */
 int vs_kl_fwd(const float* mean, const float* std_, float* out, int batch, int dim, void* stream);
 int vs_kl_bwd(const float* mean, const float* std_, const float* gout, float* gmean, float* gstd, int batch, int dim, void* stream);

@@ -1,6 +1,8 @@
 // Small / streaming kernels of the training step: softmax backward, label prep, VAE bottleneck (fc, reparam, KL),
 // Dice / BCE losses, multi-tensor SGD / Adam / EMA.
 #include "common.h"
+#include "philox.h"
+#include <math.h>
 
 // ---- deterministic build (common.h): a property of the library, queried by the package ----------------------------------------------
 extern "C" int vs_get_deterministic(void) { return VS_DET_BUILD; }
@@ -602,9 +604,11 @@ extern "C" int vs_linear_perm_out_bwd(const float* z, const float* wgt, const vo
 }
 
 // ---- reparameterisation / KL -----------------------------------------------------------------------
+// one definition of the latent's arithmetic: vs_reparam_fwd and vs_reparam_philox_fwd give the same bits for the same noise
+__device__ __forceinline__ float reparam_z(float mean, float sd, float noise, float scale) { return mean + noise * sd * scale; }
 __global__ void reparam_fwd_kernel(const float* mean, const float* sd, const float* noise, float scale, float* z, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) z[i] = mean[i] + noise[i] * sd[i] * scale;
+    if (i < n) z[i] = reparam_z(mean[i], sd[i], noise[i], scale);
 }
 __global__ void reparam_bwd_kernel(const float* gz, const float* noise, float scale, float* gmean, float* gstd, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -622,6 +626,77 @@ extern "C" int vs_reparam_fwd(const float* mean, const float* std_, const float*
 extern "C" int vs_reparam_bwd(const float* gz, const float* noise, float scale, float* gmean, float* gstd, long long count, void* stream) {
     if (!gz || !noise || count <= 0) return VS_EINVAL;
     hipLaunchKernelGGL(reparam_bwd_kernel, GRID1D(count), dim3(256), 0, (hipStream_t)stream, gz, noise, scale, gmean, gstd, count);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
+// ---- the latent's noise, drawn on the device ------------------------------------------------------------
+// A latent stream is (seed, draw), two unsigned 64-bit words.  Pair q of draw t: Philox4x32-10 under key (seed low, seed high) and counter
+// (q, t low, 0x200, t high); u1, u2 and r = sqrt(-2 ln u1) as vs_aug_normal_philox forms them, in fp64; element 2q = r cos(2 pi u2), element
+// 2q + 1 = r sin(2 pi u2), rounded to fp32 once.  An odd count uses the cosine of its last pair only.  One thread per pair.
+__device__ __forceinline__ void latent_pair(unsigned int q, unsigned long long seed, unsigned long long draw, float& even, float& odd) {
+#pragma clang fp contract(off)
+    unsigned int w0, w1, w2, w3;
+    vs_philox4x32_10(q, (unsigned int)draw, 0x200u, (unsigned int)(draw >> 32), (unsigned int)seed, (unsigned int)(seed >> 32), w0, w1, w2, w3);
+    const double u1 = ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6) + 0.5) * 0x1p-53;
+    const double u2 = ((double)(w2 >> 5) * 67108864.0 + (double)(w3 >> 6)) * 0x1p-53;
+    const double r = sqrt(-2.0 * log(u1)), a = 2.0 * M_PI * u2;
+    even = (float)(r * cos(a));
+    odd = (float)(r * sin(a));
+}
+__global__ __launch_bounds__(256) void latent_normal_kernel(float* __restrict__ noise, long long n, unsigned long long seed, unsigned long long draw) {
+    const long long pairs = (n + 1) >> 1;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < pairs; q += (long long)gridDim.x * 256) {
+        float even, odd;
+        latent_pair((unsigned int)q, seed, draw, even, odd);
+        noise[2 * q] = even;
+        if (2 * q + 1 < n) noise[2 * q + 1] = odd;
+    }
+}
+// state[0] = seed, state[1] = draw, read from device memory by every thread: a replayed graph draws what the counter says at that launch
+__global__ __launch_bounds__(256) void reparam_philox_fwd_kernel(const float* __restrict__ mean, const float* __restrict__ sd,
+                                                                const unsigned long long* __restrict__ state, float scale, float* __restrict__ z,
+                                                                float* __restrict__ noise_out, long long n) {
+    const unsigned long long seed = state[0], draw = state[1];
+    const long long pairs = (n + 1) >> 1;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < pairs; q += (long long)gridDim.x * 256) {
+        float even, odd;
+        latent_pair((unsigned int)q, seed, draw, even, odd);
+        const long long i = 2 * q;
+        noise_out[i] = even;
+        z[i] = reparam_z(mean[i], sd[i], even, scale);
+        if (i + 1 < n) {
+            noise_out[i + 1] = odd;
+            z[i + 1] = reparam_z(mean[i + 1], sd[i + 1], odd, scale);
+        }
+    }
+}
+// the launch behind the forward on the same stream: every read of state[1] above has completed when this one thread writes it
+__global__ void latent_advance_kernel(unsigned long long* state) { state[1] = state[1] + 1ull; }
+
+static inline int latent_count_ok(long long count) { return count > 0 && count < (1LL << 31); }
+extern "C" int vs_latent_normal_philox(float* noise, long long count, unsigned long long seed, unsigned long long draw, void* stream) {
+    if (!noise) return VS_EINVAL;
+    if (!latent_count_ok(count)) return VS_ESHAPE;
+    if ((uintptr_t)noise & 3) return VS_EALIGN;
+    hipLaunchKernelGGL(latent_normal_kernel, GRID1D((count + 1) / 2), dim3(256), 0, (hipStream_t)stream, noise, count, seed, draw);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+extern "C" int vs_reparam_philox_fwd(const float* mean, const float* std_, const unsigned long long* state, float scale, float* z, float* noise_out,
+                                     long long count, void* stream) {
+    if (!mean || !std_ || !state || !z || !noise_out) return VS_EINVAL;
+    if (!latent_count_ok(count)) return VS_ESHAPE;
+    if (((uintptr_t)state & 7) || (((uintptr_t)mean | (uintptr_t)std_ | (uintptr_t)z | (uintptr_t)noise_out) & 3)) return VS_EALIGN;
+    hipLaunchKernelGGL(reparam_philox_fwd_kernel, GRID1D((count + 1) / 2), dim3(256), 0, (hipStream_t)stream, mean, std_, state, scale, z, noise_out,
+                       count);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+extern "C" int vs_latent_advance(unsigned long long* state, void* stream) {
+    if (!state) return VS_EINVAL;
+    if ((uintptr_t)state & 7) return VS_EALIGN;
+    hipLaunchKernelGGL(latent_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state);
     VS_CHECK_LAUNCH();
     return VS_OK;
 }

@@ -1,6 +1,7 @@
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw, "Parallel random numbers: as easy as 1, 2, 3", SC'11): four 32-bit counter words and two key words ->
 // four output words, ten rounds of two 32 x 32 -> 64 bit products.  A pure function of its arguments: no state, the same bits in every launch geometry.
-// Users: elastic.hip (counter word 2 = the field's axis, 0..2; words w0, w1) and augment.hip (counter word 2 = 0x100 + channel; all four words).
+// Users: elastic.hip (counter word 2 = the field's axis, 0..2; words w0, w1), augment.hip (counter word 2 = 0x100 + channel; all four words) and
+// misc.hip's latent stream (counter (pair, draw low, 0x200, draw high); all four words).
 #pragma once
 
 __device__ __forceinline__ void vs_philox4x32_10(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int c3, unsigned int k0, unsigned int k1,

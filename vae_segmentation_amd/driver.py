@@ -706,13 +706,21 @@ def run(args, side="source"):
     lab_buf = torch.zeros(bs, 1, side_, side_, side_, device="cuda")
     score_buf = torch.zeros(bs, 1, device="cuda")                           # discriminator_train's regression target (venous_score)
     cur = {"epoch": 0}
-    # the Embed methods draw VAE noise per call on the device and embed_train toggles requires_grad by epoch: launched eagerly
+    # the sampling methods draw VAE noise per call.  --latent_noise torch (the default): torch.randn, launched eagerly.  --latent_noise philox: one
+    # ops.LatentStream per rank, drawn inside the forward launch from a device-resident counter, so the step is captured like every other method's;
+    # embed_train's requires_grad toggle by epoch parity rebuilds the captured step (loss_key below)
+    latent = None
     if method in ("embed_train", "refine_vae", "vae_train"):
-        use_graph = False
+        if getattr(args, "latent_noise", "torch") == "philox":
+            # 1000 rank + 700: the loaders' per-rank Philox streams are seeded base + 1000 rank (+ 500) with their own fixed bases; this one's base is 0
+            # (the entry points have no --seed flag)
+            latent = ops.LatentStream(1000 * rank + 700)
+        else:
+            use_graph = False
 
     def loss_fn():
         if method == "vae_train":
-            return T.vae_train_losses(model, lab_buf, scale=0.35, eps=eps, n_class=nc)
+            return T.vae_train_losses(model, lab_buf, scale=0.35, noise=latent, eps=eps, n_class=nc)
         if method == "seg_train":
             return T.seg_train_losses(model, img_buf, lab_buf, eps=eps, n_class=nc)
         if method == "joint_train":
@@ -720,9 +728,9 @@ def run(args, side="source"):
         if method == "sep_joint_train":
             return T.sep_joint_train_losses(model, teacher, img_buf, lab_buf, eps=eps, n_class=nc)
         if method == "embed_train":
-            return T.embed_train_losses(model, img_buf, lab_buf, eps=eps, n_class=nc)
+            return T.embed_train_losses(model, img_buf, lab_buf, eps=eps, n_class=nc, noise=latent)
         if method == "refine_vae":
-            return T.refine_vae_losses(model, img_buf, lab_buf, eps=eps, n_class=nc)
+            return T.refine_vae_losses(model, img_buf, lab_buf, eps=eps, n_class=nc, noise=latent)
         if method == "discriminator_train":
             return T.discriminator_train_loss(model, lab_buf, score_buf)
         if method == "domain_adaptation_dis":
@@ -761,6 +769,8 @@ def run(args, side="source"):
         """what of the loss expression depends on the epoch (main_target.py:583-592): a captured step is rebuilt when it changes"""
         if method == "domain_adaptation_dis":                               # main_target.py:720-723: lambda ramps with the epoch during the warm-up
             return min(epoch, warmup_epochs)
+        if method == "embed_train":                                         # the Encoder's requires_grad follows the epoch's parity: another live parameter set
+            return epoch % 2
         if method != "domain_adaptation" or getattr(args, "domain_loss_type", 0) != 0 or getattr(args, "only_pseudo", False):
             return 0
         if turn_epoch != -1:
@@ -784,6 +794,11 @@ def run(args, side="source"):
                 model.Vae.eval()
             if use_graph and (stepper is None or stepper_key != loss_key(epoch)):
                 stepper = None                                        # release the old capture's memory pool first
+                # a GraphedStep drops the gradients of ITS parameters only, and an eager optimiser tail steps every parameter that holds one: a parameter
+                # frozen for this epoch (embed_train's Encoder on even epochs) must not keep the gradient the previous capture's last replay left it
+                for grp in optimizer.param_groups:
+                    for p in grp["params"]:
+                        p.grad = None
                 stepper = T.GraphedStep(loss_fn, params, optimizer, grad_sync=sync, warmup=1, scaler=scaler)
                 stepper_key = loss_key(epoch)
                 if rank == 0:
@@ -995,6 +1010,10 @@ def add_native_flags(parser):
     g.add_argument("--aug_lowres", type=_probability, default=0.0, metavar="P", help="with --aug_intensity: nnU-Net's simulated low resolution of a training "
                    "sample with probability P (nnU-Net: 0.25), between contrast and the gammas — per channel with probability 0.5 a zoom from U(0.5, 1), "
                    "down by nearest neighbour, back up by a cubic spline with edge boundaries, clipped, on the device (ops.simulate_lowres); 0 = off")
+    g.add_argument("--latent_noise", default="torch", choices=["torch", "philox"], help="vae_train / embed_train / refine_vae: where the VAE's latent noise "
+                   "comes from — torch: torch.randn per call, the step launched eagerly (the reference's draw); philox: a stated Philox4x32-10 stream per "
+                   "rank (ops.LatentStream, seed 1000 rank + 700) drawn inside the forward launch from a counter in device memory, so the step is captured "
+                   "as a HIP graph and every replay draws a fresh sample")
     g.add_argument("--size", type=int, default=128, help="cubic patch side (reference: patch_size 128, main_source.py:117)")
     g.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "fp16"], help="kernel storage dtype")
     g.add_argument("--synthetic_train", type=int, default=16)

@@ -285,7 +285,8 @@ def _dropout(a, p):
 class VAE(nn.Module):
     """joint_model.py:204-272.  ``spatial`` generalises the reference's hard-wired 128^3 input
     (Linear(16384, dim), view(B,256,4,4,4)); the default reproduces the reference state_dict exactly.
-    ``noise`` (optional, (B, dim)) replaces the reference's CPU torch.randn draw (joint_model.py:246)."""
+    ``noise`` (optional) replaces the reference's CPU torch.randn draw (joint_model.py:246): a (B, dim) tensor is used as it is; an ops.LatentStream
+    makes one draw of its Philox stream per ``if_random=True`` call, on the device, so the call can be captured and a replay draws afresh."""
 
     def __init__(self, n_channels, n_class, norm_type=2, n_fmaps=[8, 16, 32, 64, 128, 256], dim=1024, soft=False,
                  spatial=128):
@@ -334,7 +335,9 @@ class VAE(nn.Module):
             feat = ops.Materialize.apply(a.raw, a.stats, None, None)
             x_mean, x_std = ops.LinearCLPair.apply(feat, self.fc_mean.weight, self.fc_mean.bias, False,
                                                    self.fc_std.weight, self.fc_std.bias, True)
-            if if_random:
+            if if_random and isinstance(noise, ops.LatentStream):
+                z, _ = ops.ReparamPhilox.apply(x_mean, x_std, noise, scale)         # one draw of the stream, made in the launch: capturable
+            elif if_random:
                 if noise is None:
                     noise = torch.randn(x_mean.shape, device=x_mean.device, dtype=torch.float32)
                 z = ops.Reparam.apply(x_mean, x_std, noise.to(x_mean.device, torch.float32).contiguous(), scale)
@@ -536,7 +539,7 @@ class Joint2(nn.Module):
 
 class Embed(nn.Module):
     """joint_model.py:469-500 — image encoder -> latent code -> VAE decoder (initial segmentation) -> Fusion refinement.
-    ``noise`` (optional) replaces the VAE's own draw for the `gt_recon` pass, as in VAE.forward."""
+    ``noise`` (optional, a tensor or an ops.LatentStream) replaces the VAE's own draw for the `gt_recon` pass, as in VAE.forward."""
 
     def __init__(self, models):
         super().__init__()

@@ -2173,6 +2173,69 @@ class Reparam(torch.autograd.Function):
         return gm, gs, None, None
 
 
+_U64 = 2 ** 64 - 1
+
+
+def latent_normal(shape, seed, draw):
+    """draw `draw` of the latent stream `seed`, fp32 on the device, shape (B, dim) (or any shape: element i is the i-th of the flattened tensor):
+    pair q = i >> 1 from Philox4x32-10 under key `seed` and counter (q, draw low, 0x200, draw high), Box-Muller in fp64 as ops.philox_normal forms it,
+    even i the cosine, odd i the sine, rounded to fp32 once (vs_latent_normal_philox) — the noise ReparamPhilox draws when its stream says (seed, draw)"""
+    shape = tuple(int(v) for v in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
+    if not shape or min(shape) < 1:
+        raise ValueError("latent_normal: a shape of positive sizes, got %r" % (shape,))
+    out = torch.empty(shape, dtype=torch.float32, device="cuda")
+    check(lib.vs_latent_normal_philox(out.data_ptr(), out.numel(), int(seed) & _U64, int(draw) & _U64, _stream()), "latent_normal_philox")
+    return out
+
+
+class LatentStream:
+    """The (seed, draw) of a latent noise stream, two unsigned 64-bit words in DEVICE memory: ReparamPhilox reads them in its forward launch and advances
+    `draw` by one behind it, so a captured step draws a fresh, stated sample on every replay — the same bits an eager step draws at that state."""
+
+    def __init__(self, seed, draw=0, device="cuda"):
+        self.words = torch.zeros(2, dtype=torch.int64, device=device)       # the two words' bits (torch has no arithmetic on uint64; none is needed)
+        self.set(seed, draw)
+
+    def set(self, seed, draw=0):
+        signed = [v - 2 ** 64 if v >= 2 ** 63 else v for v in (int(seed) & _U64, int(draw) & _U64)]
+        self.words.copy_(torch.tensor(signed, dtype=torch.int64))
+
+    def state(self):
+        """(seed, draw) on the host: a read-back that synchronises — for tests and for a caller that wants to store the stream, never in a step
+        (driver.save_checkpoint keeps the reference's three-key layout and does not store it: a resumed run starts its stream at draw 0 again)"""
+        seed, draw = (int(v) & _U64 for v in self.words.tolist())
+        return seed, draw
+
+
+class ReparamPhilox(torch.autograd.Function):
+    """z = mean + noise * std * scale with the noise drawn in the launch from the LatentStream's device-resident (seed, draw); the stream advances by one
+    draw behind the forward.  -> (z, noise): the noise is saved for the backward (ops.Reparam's) and returned for whoever wants to see it."""
+
+    @staticmethod
+    def forward(ctx, mean, std, stream, scale):
+        _require_cuda(mean, std, stream.words)
+        if mean.dtype != torch.float32 or std.dtype != torch.float32 or not (mean.is_contiguous() and std.is_contiguous()) or mean.shape != std.shape:
+            raise TypeError("ReparamPhilox: mean and std are contiguous float32 tensors of one shape")
+        z, noise = torch.empty_like(mean), torch.empty_like(mean)
+        check(lib.vs_reparam_philox_fwd(mean.data_ptr(), std.data_ptr(), stream.words.data_ptr(), float(scale), z.data_ptr(), noise.data_ptr(),
+                                        mean.numel(), _stream()), "reparam_philox_fwd")
+        check(lib.vs_latent_advance(stream.words.data_ptr(), _stream()), "latent_advance")
+        ctx.save_for_backward(noise)
+        ctx.mark_non_differentiable(noise)
+        ctx.scale = float(scale)
+        return z, noise
+
+    @staticmethod
+    def backward(ctx, gz, _gnoise):
+        (noise,) = ctx.saved_tensors
+        gz = _contig(gz)
+        gm = torch.empty_like(gz) if ctx.needs_input_grad[0] else None
+        gs = torch.empty_like(gz) if ctx.needs_input_grad[1] else None
+        check(lib.vs_reparam_bwd(gz.data_ptr(), noise.data_ptr(), ctx.scale, _p(gm), _p(gs), gz.numel(), _stream()),
+              "reparam_bwd")
+        return gm, gs, None, None
+
+
 class KL(torch.autograd.Function):
     """utils/evaluation.py:42-45."""
 

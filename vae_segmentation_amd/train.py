@@ -284,7 +284,11 @@ class GraphedStep:
     floats when a scheduler moved them: main_source.py:674-677 — no re-capture); what IS baked in — the set of live parameters and the
     addresses of parameters and momentum buffers — is compared on every step() and a change (requires_grad toggled, load_state_dict) re-captures
     (`self.recaptures`).  A LossScaler's scale, overflow flag and growth tracker are device scalars, so the scaled step captures as it is.
-    Models with dropout > 0 cannot be captured (ops.next_dropout_seed raises during capture): run them eagerly."""
+    Models with dropout > 0 cannot be captured (ops.next_dropout_seed raises during capture): run them eagerly.
+    A SAMPLING VAE (vae_train / embed_train / refine_vae losses) is captured by passing an ops.LatentStream as the loss function's ``noise``: the
+    forward launch reads the stream's (seed, draw) from device memory and a one-thread launch behind it advances the draw, so every replay draws a
+    fresh sample — the one an eager step draws at that state.  A fixed noise tensor captures too and replays the same sample; ``noise=None``
+    (torch.randn) ties the sample to torch's generator and is not meant for a capture.  The warm-up passes consume draws like any other step."""
 
     def __init__(self, loss_fn, params, optimizer, grad_sync=None, warmup=2, scaler=None, capture_tail=None):
         from . import ddp as _ddp
