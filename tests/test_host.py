@@ -388,6 +388,31 @@ def test_isa_phase_counts_finds_the_tile_loop_of_k3t():
     assert mfma == 72 and 300 <= valu + packed <= 800, out.stdout
 
 
+def test_isa_diff_verdicts_on_inline_assembly():
+    """tools/isa_diff.py's comparison (no compile): equal text is `identical`, scalar moves that traded places are `equivalent` (the same count of every
+    mnemonic, the same descriptor), one extra instruction is DIFFERENT, and a symbol that only one side has is reported as such."""
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    try:
+        import isa_diff
+    finally:
+        sys.path.pop(0)
+
+    def asm(body, ident="a", extra=""):
+        return ("\t.file\t\"%s.hip\"\n\t.type\tkern,@function\nkern:\n%s\ts_endpgm\n.Lfunc_end0:\n\t.size\tkern, .Lfunc_end0-kern\n"
+                "\t.amdhsa_kernel kern\n\t\t.amdhsa_next_free_vgpr 4\n\t\t.amdhsa_group_segment_fixed_size 0\n\t.end_amdhsa_kernel\n%s\t.ident\t\"%s\"\n"
+                % (ident, body, extra, ident))
+
+    base = "\ts_mov_b32 s0, s2\n\ts_mov_b32 s1, s3\n\tv_add_f32_e32 v0, v1, v2\n"
+    swapped = "\ts_mov_b32 s1, s3\n\ts_mov_b32 s4, s2\n\tv_add_f32_e32 v0, v1, v2\n"
+    longer = base + "\tv_add_f32_e32 v0, v0, v0\n"
+    assert isa_diff.compare(asm(base), asm(base, ident="b")) == {"kern": "identical"}
+    assert isa_diff.compare(asm(base), asm(swapped)) == {"kern": "equivalent"}
+    assert isa_diff.compare(asm(base), asm(longer)) == {"kern": "DIFFERENT"}
+    assert isa_diff.compare(asm(base), asm(base).replace("next_free_vgpr 4", "next_free_vgpr 5")) == {"kern": "DIFFERENT"}
+    other = "\t.type\tlone,@function\nlone:\n\ts_endpgm\n\t.size\tlone, 4\n"
+    assert isa_diff.compare(asm(base), asm(base, extra=other)) == {"kern": "identical", "lone": "only in new"}
+
+
 def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path):
     """bench.py --dump-outputs (no GPU: the writer alone): float32 .npy files, 64 MB in all; outputs that fit are written whole, the larger ones as a
     sample of positions that are the same in every run (two builds compare output for output), in ascending order."""

@@ -83,29 +83,6 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(int* __restrict__ paren
     }
 }
 
-template <int NT>
-__device__ __forceinline__ int cc_block_excl_scan(int val, int* total, int* lds) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = val;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) lds[wv] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int j = 0; j < NT / 64; ++j) {
-        const int s = lds[j];
-        if (j < wv) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - val;
-}
-
 // flags[j] = voxel e + j of the plane is a root
 template <bool VEC>
 __device__ __forceinline__ int cc_root_flags(const int* L, int e, int V, bool flags[4]) {
@@ -144,7 +121,7 @@ __global__ __launch_bounds__(256) void cc_chunk_kernel(const int* __restrict__ p
         bool flags[4];
         const int cnt = cc_root_flags<VEC>(L, e, g.V, flags);
         int tot;
-        int r = carry + cc_block_excl_scan<256>(cnt, &tot, lds);
+        int r = carry + block_excl_scan<256>(cnt, &tot, lds);
         if (RANK) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -168,7 +145,7 @@ __global__ __launch_bounds__(CC_SEL_NT) void cc_scan_kernel(int* __restrict__ ch
         const int i = base + threadIdx.x;
         const int val = i < g.nb ? c[i] : 0;
         int tot;
-        const int ex = cc_block_excl_scan<CC_SEL_NT>(val, &tot, lds);
+        const int ex = block_excl_scan<CC_SEL_NT>(val, &tot, lds);
         if (i < g.nb) c[i] = carry + ex;
         carry += tot;
     }
@@ -230,7 +207,7 @@ __global__ __launch_bounds__(256) void cc_relabel_kernel(const int* __restrict__
 
 __device__ __forceinline__ int cc_block_sum(int v, int* lds) {
     int tot;
-    cc_block_excl_scan<CC_SEL_NT>(v, &tot, lds);
+    block_excl_scan<CC_SEL_NT>(v, &tot, lds);
     return tot;
 }
 
@@ -266,7 +243,7 @@ __global__ __launch_bounds__(CC_SEL_NT) void cc_select_kernel(const int* __restr
         const int i = base + threadIdx.x;
         const int s = i < K ? sz[i] : 0;
         int tot;
-        const int ex = cc_block_excl_scan<CC_SEL_NT>(s == t, &tot, lds);
+        const int ex = block_excl_scan<CC_SEL_NT>(s == t, &tot, lds);
         if (i < K) kp[i] = s > t || (s == t && carry + ex < room);
         carry += tot;
     }

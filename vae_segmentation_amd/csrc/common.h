@@ -145,6 +145,30 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// exclusive prefix sum of `val` over the NT threads of a workgroup (thread order), *total = the sum; lds: NT / 64 ints.  Ends with a barrier: lds may be reused at once
+template <int NT>
+__device__ __forceinline__ int block_excl_scan(int val, int* total, int* lds) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int inc = val;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) lds[wv] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int j = 0; j < NT / 64; ++j) {
+        const int s = lds[j];
+        if (j < wv) base += s;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + inc - val;
+}
+
 // ---- per-(n,c) statistics: double[VS_STAT_SLOTS][pairs][2] --------------------------------------------------------------------------
 // A statistics buffer holds VS_STAT_SLOTS partial copies of its (sum, sumsq) [or IN-backward (sum g*mask, sum g*mask*xhat)] pairs.  A
 // producing workgroup accumulates into copy (blockIdx.x mod VS_STAT_SLOTS); consumers add the copies (fixed order) when they build their

@@ -25,7 +25,7 @@
 // is a per-thread strided sum followed by a fixed tree over the workgroup's 256 partials — no floating-point atomics, the same bits on every run.
 #include <limits.h>
 #include <math.h>
-#include "common.h"
+#include "volume.h"
 
 namespace {
 
@@ -42,17 +42,7 @@ static_assert(HS_WG_VOXELS % (256 * HS_UNROLL) == 0, "every thread of a workgrou
 
 enum { HS_AUTO = 0, HS_LDS32 = 1, HS_PACKED = 2, HS_GLOBAL = 3 };
 
-typedef long long i64;
-typedef unsigned long long u64;
 
-__device__ __forceinline__ void hs_add(i64* p, i64 v) { atomicAdd(reinterpret_cast<u64*>(p), (u64)v); }
-__device__ __forceinline__ int hs_ctz(u64 m) { return __ffsll((long long)m) - 1; }      // m != 0
-
-// length of the run that starts at `lane`, from the ballot of the lanes whose key differs from the lane below (bit 0 always set)
-__device__ __forceinline__ int hs_run_length(u64 heads, int lane) {
-    const u64 above = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1ull);
-    return (above ? hs_ctz(above) : 64) - lane;
-}
 
 // fp32 bits <-> an unsigned integer with the same order as the values (finite values never map to 0 or 0xffffffff)
 __device__ __forceinline__ unsigned int hs_enc(float f) {
@@ -250,7 +240,7 @@ __global__ __launch_bounds__(256) void hs_count_lds_kernel(hs_job j, int blocks_
             const bool head = lane == 0 || key != below;
             const u64 heads = __ballot(head);
             if (head && key >= 0) {
-                const unsigned int len = (unsigned int)hs_run_length(heads, lane);
+                const unsigned int len = (unsigned int)run_length(heads, lane);
                 if (PACKED) atomicAdd(&cells[key >> 1], len << ((key & 1) * 16));
                 else atomicAdd(&cells[key], len);
             }
@@ -266,14 +256,14 @@ __global__ __launch_bounds__(256) void hs_count_lds_kernel(hs_job j, int blocks_
         const unsigned int c = cells[i];
         if (!c) continue;
         if (PACKED) {
-            if (c & 0xffffu) hs_add(T + 2 * i, (i64)(c & 0xffffu));
-            if (c >> 16) hs_add(T + 2 * i + 1, (i64)(c >> 16));        // a key 2 i + 1 was counted, so the cell exists
+            if (c & 0xffffu) run_add(T + 2 * i, (i64)(c & 0xffffu));
+            if (c >> 16) run_add(T + 2 * i + 1, (i64)(c >> 16));        // a key 2 i + 1 was counted, so the cell exists
         } else {
-            hs_add(T + i, (i64)c);
+            run_add(T + i, (i64)c);
         }
     }
     if (threadIdx.x == 0) {
-        if (out_total) hs_add(j.outside + plane, (i64)out_total);
+        if (out_total) run_add(j.outside + plane, (i64)out_total);
         if (bad_total) atomicAdd(j.overflow + plane, bad_total);       // labels were given, so overflow is a buffer
     }
 }
@@ -306,8 +296,8 @@ __global__ __launch_bounds__(256) void hs_count_global_kernel(hs_job j, long lon
             if (!counted) continue;
             u64 m = pend_key >= 0 ? __ballot(key == pend_key) : 0ull;
             if (!m) {
-                if (pend_key >= 0 && lane == 0) hs_add(T + pend_key, pend_cnt);
-                pend_key = __shfl(key, hs_ctz(counted));
+                if (pend_key >= 0 && lane == 0) run_add(T + pend_key, pend_cnt);
+                pend_key = __shfl(key, run_ctz(counted));
                 pend_cnt = 0;
                 m = __ballot(key == pend_key);
             }
@@ -315,11 +305,11 @@ __global__ __launch_bounds__(256) void hs_count_global_kernel(hs_job j, long lon
             const int below = __shfl_up(key, 1);
             const bool head = lane == 0 || key != below;
             const u64 heads = __ballot(head);
-            if (head && key >= 0 && key != pend_key) hs_add(T + key, (i64)hs_run_length(heads, lane));
+            if (head && key >= 0 && key != pend_key) run_add(T + key, (i64)run_length(heads, lane));
         }
         if (lane == 0) {
-            if (pend_key >= 0) hs_add(T + pend_key, pend_cnt);
-            if (out) hs_add(j.outside + plane, (i64)out);
+            if (pend_key >= 0) run_add(T + pend_key, pend_cnt);
+            if (out) run_add(j.outside + plane, (i64)out);
             if (bad) atomicAdd(j.overflow + plane, bad);
         }
     }

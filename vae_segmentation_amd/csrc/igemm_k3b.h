@@ -16,7 +16,7 @@
 // k3_kernel.
 #pragma once
 #include <stdlib.h>
-#include "igemm.h"
+#include "igemm_tile.h"
 #include "chain.h"
 
 #ifdef VS_STAMPS   // diagnostic build only (tools/build_stamps.sh, tools/stamps_k3.py): per-phase cycle sums of wave 0
@@ -154,22 +154,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
 
     u32x4 xv[NIT], wv[NWI], fv[FA ? NIT : 1];
     unsigned int okbits = 0;
-    struct Coord { int n, z0, y0, x0; };
-    auto tile_coord = [&](int t) {                        // scalar: t is workgroup-uniform
-        Coord c;
-        c.n = fdiv(t, p.fd_m[0], p.fd_s[0]);
-        const int tl = t - c.n * p.tiles_per_sample;
-        const int tz = fdiv(tl, p.fd_m[1], p.fd_s[1]);
-        const int r = tl - tz * (p.txn * p.tyn);
-        const int ty = fdiv(r, p.fd_m[2], p.fd_s[2]);
-        c.z0 = tz * 4; c.y0 = ty * YT; c.x0 = (r - ty * p.txn) * 16;
-        return c;
-    };
     auto load_w = [&](int ch) {
 #pragma unroll
         for (int i = 0; i < NWI; ++i) wv[i] = wp[w_off[i] + ch * (NKGC * 64)];
     };
-    auto load_x = [&](const Coord& c, int ch) {
+    auto load_x = [&](const TileCoord& c, int ch) {
         const int n = c.n, z0 = c.z0, y0 = c.y0, x0 = c.x0;
         const int base = ((((n * p.D + z0 - 1) * p.H + y0 - 1) * p.W + x0 - 1) * p.C + ch * CK) * 2;
         okbits = 0;
@@ -182,7 +171,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
             if constexpr (FA) fv[b] = __builtin_bit_cast(u32x4, vs_raw_buffer_load_b128(frsrc, ok ? base + rel_off[b] : -1, 0, 0));
         }
     };
-    auto write_x_fa = [&](const Coord& c, int ch) {     // FA: apply pass on the staged fragments [+ the applied gradient of the centre voxels to fa_dx]
+    auto write_x_fa = [&](const TileCoord& c, int ch) {     // FA: apply pass on the staged fragments [+ the applied gradient of the centre voxels to fa_dx]
         f32x2 r2[4], s2[4], a2[4], b2[4];
         const int c0 = c.n * p.C + ch * CK + part * 8;
 #pragma unroll
@@ -249,19 +238,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
     };
 
     // ---- first stage in flight before anything else; the statistics tables meanwhile ----------------------------------
-    // XCD-aware walk: consecutive workgroup ids land on different XCDs (8, each with its own L2); the workgroups of one XCD work
-    // on one contiguous run of tiles and find their neighbours' halos in that XCD's L2 (identity walk when the grid is not a
-    // multiple of 8).
-    // XCD x owns the contiguous run [x*T/8, (x+1)*T/8) of the tile list and deals it round-robin to its workgroups: every XCD gets
-    // the same number of tiles (striding the whole list by the grid left the remainder T mod G to XCD 0 and 1).
     int t, t_end, G;
-    if (((int)gridDim.x & 7) == 0) {
-        const int xcd = (int)blockIdx.x & 7;
-        G = (int)gridDim.x >> 3;
-        t = (int)(((long long)total_tiles * xcd) >> 3) + ((int)blockIdx.x >> 3);
-        t_end = (int)(((long long)total_tiles * (xcd + 1)) >> 3);
-    } else { G = (int)gridDim.x; t = (int)blockIdx.x; t_end = total_tiles; }
-    Coord cur = tile_coord(t), nxt = cur;
+    tile_walk(total_tiles, t, t_end, G);
+    TileCoord cur = tile_coord<YT, 16>(p, t), nxt = cur;
     load_w(0);
     load_x(cur, 0);
     // bias of this workgroup's rows (registers: a load inside the tile loop would queue behind the prefetch)
@@ -372,7 +351,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
             }
             {
                 const int tn = last_ch ? t + G : t;
-                if (last_ch) nxt = tile_coord(tn);
+                if (last_ch) nxt = tile_coord<YT, 16>(p, tn);
                 if (tn < t_end) {
                     if constexpr (restage_w) load_w(last_ch ? 0 : ch + 1);
                     load_x(last_ch ? nxt : cur, last_ch ? 0 : ch + 1);
@@ -565,13 +544,6 @@ static inline int k3b_ea_max_wgs(int n, int c, int m) {
     return 2 * (lds + 1024) <= 160 * 1024 ? 512 : 256;
 }
 
-// (m, s) with n / d == (mulhi(n, m) + n) >> s for every 0 <= n < 2^31
-static inline void k3b_fastdiv(int d, unsigned int& m, unsigned int& s) {
-    s = 0;
-    while ((1ll << s) < d) ++s;
-    m = (unsigned int)((((1ull << (32 + s)) + (unsigned long long)d - 1) / (unsigned long long)d) - (1ull << 32));
-}
-
 template <typename T, int CK, int MT, int EPI, bool SUMS, int YT, bool HS, bool FA = false, bool EA = false>
 static int k3b_launch_t(const G1Params& p_in, int tiles_total, int row_tiles, hipStream_t stream) {
     using GEO = K3BGeom<CK, MT, YT>;
@@ -587,9 +559,7 @@ static int k3b_launch_t(const G1Params& p_in, int tiles_total, int row_tiles, hi
     }
     // buffer offsets are 32-bit bytes, signed on the device
     if ((long long)p.N * p.D * p.H * p.W * p.C * 2 >= 2147483648ll || (long long)p.N * p.D * p.H * p.W * p.M * 2 >= 2147483648ll) return VS_ESHAPE;
-    k3b_fastdiv(p.tiles_per_sample, p.fd_m[0], p.fd_s[0]);
-    k3b_fastdiv(p.txn * p.tyn, p.fd_m[1], p.fd_s[1]);
-    k3b_fastdiv(p.txn, p.fd_m[2], p.fd_s[2]);
+    tile_fastdiv_fill(p);
     if (SUMS != (p.sums != nullptr) || (SUMS && !FA && p.x_stats != nullptr)) return VS_EINVAL;
     auto kern = k3b_kernel<CK, MT, EPI, SUMS, YT, HS, T, FA, EA>;
     // idempotent one-time opt-in to the full 160 KiB of dynamic LDS (not a stream operation)

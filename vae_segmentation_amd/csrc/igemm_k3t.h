@@ -16,7 +16,7 @@
 // Staging, statistics, fused IN-backward sums and the softmax epilogue follow k3b_kernel.
 #pragma once
 #include <stdlib.h>
-#include "igemm.h"
+#include "igemm_tile.h"
 
 #define K3T_LDS_RED 0          // float[4][8][2]
 #define K3T_LDS_TILE 512       // halo tile [6][YT+2][34] x 16 B, then the per-(n,c) tables
@@ -83,18 +83,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     u32x4 xv[NIT], fv[FA ? NIT : 1];
     unsigned int okbits = 0;
-    struct Coord { int n, z0, y0, x0; };
-    auto tile_coord = [&](int t) {
-        Coord c;
-        c.n = fdiv(t, p.fd_m[0], p.fd_s[0]);
-        const int tl = t - c.n * p.tiles_per_sample;
-        const int tz = fdiv(tl, p.fd_m[1], p.fd_s[1]);
-        const int r = tl - tz * (p.txn * p.tyn);
-        const int ty = fdiv(r, p.fd_m[2], p.fd_s[2]);
-        c.z0 = tz * 4; c.y0 = ty * YT; c.x0 = (r - ty * p.txn) * 32;
-        return c;
-    };
-    auto load_x = [&](const Coord& c) {
+    auto load_x = [&](const TileCoord& c) {
         const int base = (((c.n * p.D + c.z0 - 1) * p.H + c.y0 - 1) * p.W + c.x0 - 1) * 16;
         okbits = 0;
 #pragma unroll
@@ -106,7 +95,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if constexpr (FA) fv[b] = __builtin_bit_cast(u32x4, vs_raw_buffer_load_b128(frsrc, ok ? base + rel_off[b] : -1, 0, 0));
         }
     };
-    auto write_x_fa = [&](const Coord& c) {             // FA: apply pass on the staged fragments, [+ the applied gradient of the centre voxels to fa_dx]
+    auto write_x_fa = [&](const TileCoord& c) {             // FA: apply pass on the staged fragments, [+ the applied gradient of the centre voxels to fa_dx]
         f32x2 r2[4], s2[4], a2[4], b2[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -162,18 +151,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
 
     // ---- first tile in flight, weights into registers, tables -------------------------------------------------------------
-    // XCD-aware walk: consecutive workgroup ids land on different XCDs (8, each with its own L2).  XCD x owns the contiguous run
-    // [x*T/8, (x+1)*T/8) of the tile list and its workgroups deal that run round-robin, so neighbouring tiles share an L2 AND every
-    // XCD gets the same number of tiles (k3b's first walk gave the remainder T mod G to XCD 0 and 1: their CUs ran 9 tiles against
-    // 6 elsewhere at 96^3, and the launch took as long as they did).  Identity walk when the grid is not a multiple of 8.
     int t, t_end, G;
-    if (((int)gridDim.x & 7) == 0) {
-        const int xcd = (int)blockIdx.x & 7;
-        G = (int)gridDim.x >> 3;
-        t = (int)(((long long)total_tiles * xcd) >> 3) + ((int)blockIdx.x >> 3);
-        t_end = (int)(((long long)total_tiles * (xcd + 1)) >> 3);
-    } else { G = (int)gridDim.x; t = (int)blockIdx.x; t_end = total_tiles; }
-    Coord cur = tile_coord(t < t_end ? t : 0), nxt = cur;
+    tile_walk(total_tiles, t, t_end, G);
+    TileCoord cur = tile_coord<YT, 32>(p, t < t_end ? t : 0), nxt = cur;
     u32x4 wa[9];
     {
         const u32x4* __restrict__ wp = (const u32x4*)p.wp;
@@ -235,7 +215,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int cg = 0; cg < YT; ++cg)
                 mk[cg] = __builtin_bit_cast(u32x2, vs_raw_buffer_load_b64(mrsrc, (zx_ok && y0 + cg < p.H) ? ebase + cg * p.W * 16 : -1, 0, 0));
         }
-        nxt = tile_coord(t + G < t_end ? t + G : t);
+        nxt = tile_coord<YT, 32>(p, t + G < t_end ? t + G : t);
         if (t + G < t_end) load_x(nxt);
         K3_TICK(4);
 
@@ -376,9 +356,7 @@ static int k3t_launch_t(const G1Params& p_in, hipStream_t stream) {
     const long long tiles = (long long)p.tiles_per_sample * p.N;
     // buffer offsets are 32-bit bytes, signed on the device
     if ((long long)p.N * p.D * p.H * p.W * 16 >= 2147483648ll || tiles >= 2147483647ll) return VS_ESHAPE;
-    k3b_fastdiv(p.tiles_per_sample, p.fd_m[0], p.fd_s[0]);
-    k3b_fastdiv(p.txn * p.tyn, p.fd_m[1], p.fd_s[1]);
-    k3b_fastdiv(p.txn, p.fd_m[2], p.fd_s[2]);
+    tile_fastdiv_fill(p);
     if (SUMS != (p.sums != nullptr) || (SUMS && !FA && p.x_stats != nullptr)) return VS_EINVAL;
     if (FA && (!p.x_stats || !p.fa_x || !p.fa_sums)) return VS_EINVAL;
     auto kern = k3t_kernel<EPI, SUMS, YT, HS, T, FA>;

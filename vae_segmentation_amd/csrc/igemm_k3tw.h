@@ -17,7 +17,7 @@
 // gradient), +13.8 us on the plain one, against 22.5 us per layer in the grouped launch; in the step: profiles/r05_ab_fuse_wgrad_*.json.
 #pragma once
 #include <stdlib.h>
-#include "igemm.h"
+#include "igemm_tile.h"
 #include "igemm_k3t.h"
 
 typedef __attribute__((ext_vector_type(4))) short k3tw_s16x4;
@@ -95,18 +95,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             cbits |= (tv < TV && tz_ >= 1 && tz_ <= 4 && ty_ >= 1 && ty_ <= YT && tx_ >= 1 && tx_ <= 32) ? (1u << b) : 0u;
         }
     }
-    struct Coord { int n, z0, y0, x0; };
-    auto tile_coord = [&](int t) {
-        Coord c;
-        c.n = fdiv(t, p.fd_m[0], p.fd_s[0]);
-        const int tl = t - c.n * p.tiles_per_sample;
-        const int tz = fdiv(tl, p.fd_m[1], p.fd_s[1]);
-        const int r = tl - tz * (p.txn * p.tyn);
-        const int ty = fdiv(r, p.fd_m[2], p.fd_s[2]);
-        c.z0 = tz * 4; c.y0 = ty * YT; c.x0 = (r - ty * p.txn) * 32;
-        return c;
-    };
-    auto load_x = [&](const Coord& c) {
+    auto load_x = [&](const TileCoord& c) {
         const int base = (((c.n * p.D + c.z0 - 1) * p.H + c.y0 - 1) * p.W + c.x0 - 1) * 16;
         okbits = 0;
 #pragma unroll
@@ -129,7 +118,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         }
     };
-    auto write_x_sm = [&](const Coord& c) {              // softmax2_bwd_kernel (misc.hip) on the staged voxels
+    auto write_x_sm = [&](const TileCoord& c) {              // softmax2_bwd_kernel (misc.hip) on the staged voxels
         const int base = (((c.n * p.D + c.z0 - 1) * p.H + c.y0 - 1) * p.W + c.x0 - 1) * 16;
 #pragma unroll
         for (int b = 0; b < NIT; ++b) {
@@ -150,7 +139,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if (ok && ((cbits >> b) & 1u)) { bsum[0] += H16<T>::lo(v[0]); bsum[1] += H16<T>::hi(v[0]); }      // the stored (rounded) values, as vs_bias_grad summed them
         }
     };
-    auto write_x_fa = [&](const Coord& c) {
+    auto write_x_fa = [&](const TileCoord& c) {
         f32x2 r2[4], s2[4], a2[4], b2[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -187,13 +176,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
 
     int t, t_end, G;
-    if (((int)gridDim.x & 7) == 0) {
-        const int xcd = (int)blockIdx.x & 7;
-        G = (int)gridDim.x >> 3;
-        t = (int)(((long long)total_tiles * xcd) >> 3) + ((int)blockIdx.x >> 3);
-        t_end = (int)(((long long)total_tiles * (xcd + 1)) >> 3);
-    } else { G = (int)gridDim.x; t = (int)blockIdx.x; t_end = total_tiles; }
-    Coord cur = tile_coord(t < t_end ? t : 0), nxt = cur;
+    tile_walk(total_tiles, t, t_end, G);
+    TileCoord cur = tile_coord<YT, 32>(p, t < t_end ? t : 0), nxt = cur;
     u32x4 wa[9];
     {
         const u32x4* __restrict__ wp = (const u32x4*)p.wp;
@@ -258,7 +242,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int cg = 0; cg < YT; ++cg)
             mk[cg] = __builtin_bit_cast(u32x2, vs_raw_buffer_load_b64(mrsrc, (zx_ok && y0 + cg < p.H) ? ebase + cg * p.W * 16 : -1, 0, 0));
-        nxt = tile_coord(t + G < t_end ? t + G : t);
+        nxt = tile_coord<YT, 32>(p, t + G < t_end ? t + G : t);
         if (t + G < t_end) load_x(nxt);
 
         f32x4 acc[YT];
@@ -441,9 +425,7 @@ static int k3tw_launch(const G1Params& p_in, hipStream_t stream) {
     p.tiles_per_sample = ((p.D + 3) / 4) * p.tyn * p.txn;
     const long long tiles = (long long)p.tiles_per_sample * p.N;
     if ((long long)p.N * p.D * p.H * p.W * 16 >= 2147483648ll || tiles >= 2147483647ll) return VS_ESHAPE;
-    k3b_fastdiv(p.tiles_per_sample, p.fd_m[0], p.fd_s[0]);
-    k3b_fastdiv(p.txn * p.tyn, p.fd_m[1], p.fd_s[1]);
-    k3b_fastdiv(p.txn, p.fd_m[2], p.fd_s[2]);
+    tile_fastdiv_fill(p);
     const int gx = k3tw_grid(p.N, p.D, p.H, p.W);
 #define K3TW_GO(MODEV, WGV)                                                                                                              \
     {                                                                                                                                    \

@@ -15,7 +15,7 @@
 // VS_F32X3 image).  Storage stays fp32 on both sides: 16-byte fragments are 4 channels of one voxel.
 #pragma once
 #include <stdlib.h>
-#include "igemm.h"
+#include "igemm_tile.h"
 
 #include "chain.h"
 #define K3X_LDS_RED 0          // float[4][64][2]
@@ -110,22 +110,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, CK == 8 
 
     u32x4 xv[NIT], wv[NWI], fv[FA ? NIT : 1];
     unsigned int okbits = 0;
-    struct Coord { int n, z0, y0, x0; };
-    auto tile_coord = [&](int t) {
-        Coord c;
-        c.n = fdiv(t, p.fd_m[0], p.fd_s[0]);
-        const int tl = t - c.n * p.tiles_per_sample;
-        const int tz = fdiv(tl, p.fd_m[1], p.fd_s[1]);
-        const int r = tl - tz * (p.txn * p.tyn);
-        const int ty = fdiv(r, p.fd_m[2], p.fd_s[2]);
-        c.z0 = tz * 4; c.y0 = ty * YT; c.x0 = (r - ty * p.txn) * 16;
-        return c;
-    };
     auto load_w = [&](int ch) {
 #pragma unroll
         for (int i = 0; i < NWI; ++i) wv[i] = wp[w_off[i] + ch * (NKGC * 192)];
     };
-    auto load_x = [&](const Coord& c, int ch) {
+    auto load_x = [&](const TileCoord& c, int ch) {
         const int base = ((((c.n * p.D + c.z0 - 1) * p.H + c.y0 - 1) * p.W + c.x0 - 1) * p.C + ch * CK) * 4;
         okbits = 0;
 #pragma unroll
@@ -137,7 +126,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, CK == 8 
             if constexpr (FA) fv[b] = __builtin_bit_cast(u32x4, vs_raw_buffer_load_b128(frsrc, ok ? base + rel_off[b] : -1, 0, 0));
         }
     };
-    auto write_x_fa = [&](const Coord& c, int ch) {     // FA: apply pass in fp32 on the staged fragments, then the limb split [+ the applied gradient of the centre voxels]
+    auto write_x_fa = [&](const TileCoord& c, int ch) {     // FA: apply pass in fp32 on the staged fragments, then the limb split [+ the applied gradient of the centre voxels]
         float rr[4], ss[4], aa[4], bb[4];
         const int c0 = c.n * p.C + ch * CK + part * 4;
 #pragma unroll
@@ -200,15 +189,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, CK == 8 
         for (int i = 0; i < NWI; ++i) *(u32x4*)(s_w + (tid + i * 256) * 16) = wv[i];
     };
 
-    // ---- XCD-aware persistent walk (igemm_k3b.h) ----
+    // ---- XCD-aware persistent walk (igemm_tile.h) ----
     int t, t_end, G;
-    if (((int)gridDim.x & 7) == 0) {
-        const int xcd = (int)blockIdx.x & 7;
-        G = (int)gridDim.x >> 3;
-        t = (int)(((long long)total_tiles * xcd) >> 3) + ((int)blockIdx.x >> 3);
-        t_end = (int)(((long long)total_tiles * (xcd + 1)) >> 3);
-    } else { G = (int)gridDim.x; t = (int)blockIdx.x; t_end = total_tiles; }
-    Coord cur = tile_coord(t), nxt = cur;
+    tile_walk(total_tiles, t, t_end, G);
+    TileCoord cur = tile_coord<YT, 16>(p, t), nxt = cur;
     load_w(0);
     load_x(cur, 0);
     float bv[RB][4];
@@ -300,7 +284,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, CK == 8 
             }
             {
                 const int tn = last_ch ? t + G : t;
-                if (last_ch) nxt = tile_coord(tn);
+                if (last_ch) nxt = tile_coord<YT, 16>(p, tn);
                 if (tn < t_end) {
                     if constexpr (MULTI) load_w(last_ch ? 0 : ch + 1);
                     load_x(last_ch ? nxt : cur, last_ch ? 0 : ch + 1);
@@ -473,13 +457,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, CK == 8 
 // (one wave per SIMD), whatever the LDS would allow (the first version counted LDS only: 288 workgroups waited for 32 that could not start, and the fault word said so)
 static inline int k3x_ea_max_wgs(int, int, int) { return 256; }
 
-// (m, s) with n / d == (mulhi(n, m) + n) >> s for every 0 <= n < 2^31
-static inline void k3x_fastdiv(int d, unsigned int& m, unsigned int& s) {
-    s = 0;
-    while ((1ll << s) < d) ++s;
-    m = (unsigned int)((((1ull << (32 + s)) + (unsigned long long)d - 1) / (unsigned long long)d) - (1ull << 32));
-}
-
 template <int CK, int MT, int EPI, bool SUMS, bool HS, bool MULTI, bool FA = false, int YT = 4, bool EA = false>
 static int k3x_launch_t(const G1Params& p_in, int tiles_total, int row_tiles, hipStream_t stream) {
     using GEO = K3XGeom<CK, MT, YT>;
@@ -495,9 +472,7 @@ static int k3x_launch_t(const G1Params& p_in, int tiles_total, int row_tiles, hi
     if (lds > 160 * 1024) return VS_ESHAPE;
     // buffer offsets are 32-bit bytes, signed on the device
     if ((long long)p.N * p.D * p.H * p.W * p.C * 4 >= 2147483648ll || (long long)p.N * p.D * p.H * p.W * p.M * 4 >= 2147483648ll) return VS_ESHAPE;
-    k3x_fastdiv(p.tiles_per_sample, p.fd_m[0], p.fd_s[0]);
-    k3x_fastdiv(p.txn * p.tyn, p.fd_m[1], p.fd_s[1]);
-    k3x_fastdiv(p.txn, p.fd_m[2], p.fd_s[2]);
+    tile_fastdiv_fill(p);
     if (SUMS != (p.sums != nullptr) || (SUMS && !FA && p.x_stats != nullptr) || MULTI != (p.nch > 1)) return VS_EINVAL;
     auto kern = k3x_kernel<CK, MT, EPI, SUMS, HS, MULTI, FA, YT, EA>;
     static const hipError_t attr_err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -627,18 +602,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     }
     u32x4 xv[NIT], wv[NWI], fv[FA ? NIT : 1];
     unsigned int okbits = 0;
-    struct Coord { int n, z0, y0, x0; };
-    auto tile_coord = [&](int t) {
-        Coord c;
-        c.n = fdiv(t, p.fd_m[0], p.fd_s[0]);
-        const int tl = t - c.n * p.tiles_per_sample;
-        const int tz = fdiv(tl, p.fd_m[1], p.fd_s[1]);
-        const int r = tl - tz * (p.txn * p.tyn);
-        const int ty = fdiv(r, p.fd_m[2], p.fd_s[2]);
-        c.z0 = tz * 4; c.y0 = ty * 2; c.x0 = (r - ty * p.txn) * 32;
-        return c;
-    };
-    auto load_x = [&](const Coord& c) {
+    auto load_x = [&](const TileCoord& c) {
         const int base = (((c.n * p.D + c.z0 - 1) * p.H + c.y0 - 1) * p.W + c.x0 - 1) * 8 * 4;
         okbits = 0;
 #pragma unroll
@@ -650,7 +614,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
             if constexpr (FA) fv[b] = __builtin_bit_cast(u32x4, vs_raw_buffer_load_b128(frsrc, ok ? base + rel_off[b] : -1, 0, 0));
         }
     };
-    auto write_x_fa = [&](const Coord& c) {             // FA: apply pass in fp32 on the staged fragments, then the limb split [+ the applied gradient of the centre voxels]
+    auto write_x_fa = [&](const TileCoord& c) {             // FA: apply pass in fp32 on the staged fragments, then the limb split [+ the applied gradient of the centre voxels]
         float rr[4], ss[4], aa[4], bb[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -707,13 +671,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     };
 
     int t, t_end, G;
-    if (((int)gridDim.x & 7) == 0) {
-        const int xcd = (int)blockIdx.x & 7;
-        G = (int)gridDim.x >> 3;
-        t = (int)(((long long)total_tiles * xcd) >> 3) + ((int)blockIdx.x >> 3);
-        t_end = (int)(((long long)total_tiles * (xcd + 1)) >> 3);
-    } else { G = (int)gridDim.x; t = (int)blockIdx.x; t_end = total_tiles; }
-    Coord cur = tile_coord(t), nxt = cur;
+    tile_walk(total_tiles, t, t_end, G);
+    TileCoord cur = tile_coord<2, 32>(p, t), nxt = cur;
 #pragma unroll
     for (int i = 0; i < NWI; ++i) wv[i] = wp[w_off[i]];
     load_x(cur);
@@ -772,7 +731,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
                 mk[cg] = __builtin_bit_cast(u32x4, vs_raw_buffer_load_b128(mrsrc, valid ? ebase + cg * p.W * 32 : -1, 0, 0));
             }
         }
-        nxt = tile_coord(t + G);
+        nxt = tile_coord<2, 32>(p, t + G);
         if (t + G < t_end) load_x(nxt);
 #pragma unroll
         for (int kg = 0; kg < 9; ++kg) {
@@ -885,9 +844,7 @@ static int k3xt_launch_t(const G1Params& p_in, hipStream_t stream) {
     if (lds > 160 * 1024 || p.N * 8 > (FA ? 192 : 256)) return VS_ESHAPE;          // FA: waves 1 .. 3 build the fused-apply tables
     if (FA && (!p.x_stats || !p.fa_x || !p.fa_sums)) return VS_EINVAL;
     if ((long long)p.N * p.D * p.H * p.W * 8 * 4 >= 2147483648ll) return VS_ESHAPE;
-    k3x_fastdiv(p.tiles_per_sample, p.fd_m[0], p.fd_s[0]);
-    k3x_fastdiv(p.txn * p.tyn, p.fd_m[1], p.fd_s[1]);
-    k3x_fastdiv(p.txn, p.fd_m[2], p.fd_s[2]);
+    tile_fastdiv_fill(p);
     if (SUMS != (p.sums != nullptr) || (SUMS && !FA && p.x_stats != nullptr) || p.C != 8 || p.M != 8) return VS_EINVAL;
     auto kern = k3xt_kernel<EPI, SUMS, HS, FA>;
     static const hipError_t attr_err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

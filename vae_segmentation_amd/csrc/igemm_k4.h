@@ -21,7 +21,7 @@
 //               (store + fused InstanceNorm-backward sums of the block's lazy input).
 #pragma once
 #include <stdlib.h>
-#include "igemm.h"
+#include "igemm_tile.h"
 
 #ifdef VS_STAMPS   // diagnostic build only (tools/build_stamps.sh, tools/stamps_k4.py): per-phase cycle sums of wave 0
 __device__ unsigned long long g_k4_stamps[2048 * 8];
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CK == 32 &&
     u32x4 xv[NIT], wv[NWI];
     unsigned int okbits = 0;
     struct Coord { int n, z0, y0, x0; };
-    auto tile_coord = [&](int t) {
+    auto tile_coord = [&](int t) {                        // not igemm_tile.h's tile_coord<4, 16>: through that one this kernel's spill size and hazard nops change
         Coord c;
         c.n = fdiv(t, p.fd_m[0], p.fd_s[0]);
         const int tl = t - c.n * p.tiles_per_sample;
@@ -158,12 +158,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CK == 32 &&
     };
 
     int t, t_end, G;
-    if (((int)gridDim.x & 7) == 0) {
-        const int xcd = (int)blockIdx.x & 7;
-        G = (int)gridDim.x >> 3;
-        t = (int)(((long long)total_tiles * xcd) >> 3) + ((int)blockIdx.x >> 3);
-        t_end = (int)(((long long)total_tiles * (xcd + 1)) >> 3);
-    } else { G = (int)gridDim.x; t = (int)blockIdx.x; t_end = total_tiles; }
+    tile_walk(total_tiles, t, t_end, G);
     Coord cur = tile_coord(t), nxt = cur;
     load_w(0);
     load_x(cur, 0);
@@ -436,17 +431,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         w_off[i] = (rb0 + rb) * (p.nch * NT * 64) + r;
     }
     u32x4 xv[NIT], wv[NWI];
-    struct Coord { int n, z0, y0, x0; };
-    auto tile_coord = [&](int t) {
-        Coord c;
-        c.n = fdiv(t, p.fd_m[0], p.fd_s[0]);
-        const int tl = t - c.n * p.tiles_per_sample;
-        const int tz = fdiv(tl, p.fd_m[1], p.fd_s[1]);
-        const int r = tl - tz * (p.txn * p.tyn);
-        const int ty = fdiv(r, p.fd_m[2], p.fd_s[2]);
-        c.z0 = tz * 4; c.y0 = ty * 4; c.x0 = (r - ty * p.txn) * 16;
-        return c;
-    };
     auto chunk_off = [&](int ch) {                        // byte offset of the chunk's first sub-voxel / channel group inside a coarse voxel's 2x2x2 block
         if (Co >= 32) {
             const int cb = Co / 32, pp = ch / cb, c32 = ch - pp * cb;
@@ -459,7 +443,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < NWI; ++i) wv[i] = wp[w_off[i] + ch * (NT * 64)];
     };
-    auto load_x = [&](const Coord& c, int ch) {
+    auto load_x = [&](const TileCoord& c, int ch) {
         const int base = (((c.n * 2 * p.D + 2 * (c.z0 - 1)) * FH + 2 * (c.y0 - 1)) * FW + 2 * (c.x0 - 1)) * Co * 2 + chunk_off(ch);
 #pragma unroll
         for (int b = 0; b < NIT; ++b) {
@@ -481,13 +465,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
 
     int t, t_end, G;
-    if (((int)gridDim.x & 7) == 0) {
-        const int xcd = (int)blockIdx.x & 7;
-        G = (int)gridDim.x >> 3;
-        t = (int)(((long long)total_tiles * xcd) >> 3) + ((int)blockIdx.x >> 3);
-        t_end = (int)(((long long)total_tiles * (xcd + 1)) >> 3);
-    } else { G = (int)gridDim.x; t = (int)blockIdx.x; t_end = total_tiles; }
-    Coord cur = tile_coord(t), nxt = cur;
+    tile_walk(total_tiles, t, t_end, G);
+    TileCoord cur = tile_coord<4, 16>(p, t), nxt = cur;
     load_w(0);
     load_x(cur, 0);
     const i32x4 yrsrc = make_rsrc(p.y, (unsigned int)((long long)p.N * p.D * p.H * p.W * p.M * 2));
@@ -556,7 +535,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
             {
                 const int tn = last_ch ? t + G : t;
-                if (last_ch) nxt = tile_coord(tn);
+                if (last_ch) nxt = tile_coord<4, 16>(p, tn);
                 if (tn < t_end) {
                     load_w(last_ch ? 0 : ch + 1);
                     load_x(last_ch ? nxt : cur, last_ch ? 0 : ch + 1);
@@ -655,12 +634,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------------------------------------------
-static inline void k4_fastdiv(int d, unsigned int& m, unsigned int& s) {
-    s = 0;
-    while ((1ll << s) < d) ++s;
-    m = (unsigned int)((((1ull << (32 + s)) + (unsigned long long)d - 1) / (unsigned long long)d) - (1ull << 32));
-}
-
 static inline int k4_grid_x(int tiles_total, int row_tiles) {
     const int per_cu = vs_cfg().up_wgs_per_cu;      // tuning knob
     int wg = 256 * per_cu / (row_tiles < per_cu ? row_tiles : per_cu);
@@ -674,9 +647,7 @@ static int k4t_launch_t(G1Params p, hipStream_t stream) {
     const size_t lds = K4_LDS_TILE + (size_t)((NU + 255) / 256) * 4096 + (size_t)((NWF + 255) / 256) * 4096 + (size_t)2 * p.N * p.C * 4 + (size_t)27 * RB * 16 * 4;
     if (lds > 160 * 1024) return VS_ESHAPE;
     const int row_tiles = (p.rb_total + RB - 1) / RB;
-    k4_fastdiv(p.tiles_per_sample, p.fd_m[0], p.fd_s[0]);
-    k4_fastdiv(p.txn * p.tyn, p.fd_m[1], p.fd_s[1]);
-    k4_fastdiv(p.txn, p.fd_m[2], p.fd_s[2]);
+    tile_fastdiv_fill(p);
     auto kern = k4t_kernel<CK, RB, HS, T, W1>;
     static const hipError_t attr_err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (attr_err != hipSuccess) return (int)attr_err;
@@ -708,9 +679,7 @@ static int k4g_launch_t(G1Params p, hipStream_t stream) {
     const size_t lds = K4_LDS_TILE + (size_t)((648 * 4 + 255) / 256) * 4096 + (size_t)((NWF + 255) / 256) * 4096 + (size_t)2 * p.N * p.M * 4;
     if (lds > 160 * 1024 || p.nch * NT > 512) return VS_ESHAPE;
     const int row_tiles = (p.rb_total + RB - 1) / RB;
-    k4_fastdiv(p.tiles_per_sample, p.fd_m[0], p.fd_s[0]);
-    k4_fastdiv(p.txn * p.tyn, p.fd_m[1], p.fd_s[1]);
-    k4_fastdiv(p.txn, p.fd_m[2], p.fd_s[2]);
+    tile_fastdiv_fill(p);
     auto kern = k4g_kernel<MT, NT, SUMS, T>;
     static const hipError_t attr_err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (attr_err != hipSuccess) return (int)attr_err;

@@ -638,9 +638,8 @@ __device__ __forceinline__ void latent_pair(unsigned int q, unsigned long long s
 #pragma clang fp contract(off)
     unsigned int w0, w1, w2, w3;
     vs_philox4x32_10(q, (unsigned int)draw, 0x200u, (unsigned int)(draw >> 32), (unsigned int)seed, (unsigned int)(seed >> 32), w0, w1, w2, w3);
-    const double u1 = ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6) + 0.5) * 0x1p-53;
-    const double u2 = ((double)(w2 >> 5) * 67108864.0 + (double)(w3 >> 6)) * 0x1p-53;
-    const double r = sqrt(-2.0 * log(u1)), a = 2.0 * M_PI * u2;
+    double r, a;
+    vs_philox_box_muller(w0, w1, w2, w3, r, a);
     even = (float)(r * cos(a));
     odd = (float)(r * sin(a));
 }

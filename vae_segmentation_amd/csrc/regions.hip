@@ -18,7 +18,7 @@
 // depend on the order of arrival — both builds of the library, eager launches and graph replay give the same bits.  The first launch of a call
 // writes the table's initial state (no memset node), the second accumulates; nothing waits for another workgroup, nothing is read back.
 #include <limits.h>
-#include "common.h"
+#include "volume.h"
 
 namespace {
 
@@ -28,20 +28,10 @@ constexpr int RG_LDS_VOXELS = 16384;         // voxels per workgroup on the LDS 
 constexpr long long RG_MAX_CELLS = 1ll << 22;
 constexpr int RG_COLS = 10;                  // count, zmin, ymin, xmin, zmax, ymax, xmax, sum_z, sum_y, sum_x
 
-typedef long long i64;
-typedef unsigned long long u64;
-
-__device__ __forceinline__ void rg_add(i64* p, i64 v) { atomicAdd(reinterpret_cast<u64*>(p), (u64)v); }
 __device__ __forceinline__ void rg_min(i64* p, i64 v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void rg_max(i64* p, i64 v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ __forceinline__ int rg_ctz(u64 m) { return __ffsll((long long)m) - 1; }      // m != 0
 
-// length of the run that starts at `lane`, from the ballot of the lanes whose key differs from the lane below (bit 0 always set)
-__device__ __forceinline__ int rg_run_length(u64 heads, int lane) {
-    const u64 above = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1ull);
-    return (above ? rg_ctz(above) : 64) - lane;
-}
 
 // a record of voxels (z, y, x0 + bit) for the set bits of m: wave-uniform
 struct rg_record {
@@ -59,23 +49,23 @@ struct rg_record {
         sy += (i64)y * k;
         zmin = min(zmin, z); zmax = max(zmax, z);
         ymin = min(ymin, y); ymax = max(ymax, y);
-        xmin = min(xmin, x0 + rg_ctz(m));
+        xmin = min(xmin, x0 + run_ctz(m));
         xmax = max(xmax, x0 + 63 - __clzll((long long)m));
         i64 pos = 0;                                    // sum of the set bits' positions, run by run
         while (m) {
-            const int s = rg_ctz(m);
+            const int s = run_ctz(m);
             const u64 t = m >> s;
-            const int len = t == ~0ull ? 64 : rg_ctz(~t);
+            const int len = t == ~0ull ? 64 : run_ctz(~t);
             pos += (i64)len * s + (i64)len * (len - 1) / 2;
             m &= ~((len == 64 ? ~0ull : (1ull << len) - 1ull) << s);
         }
         sx += (i64)x0 * k + pos;
     }
     __device__ __forceinline__ void flush(i64* row) const {
-        rg_add(row + 0, cnt);
+        run_add(row + 0, cnt);
         rg_min(row + 1, zmin); rg_min(row + 2, ymin); rg_min(row + 3, xmin);
         rg_max(row + 4, zmax); rg_max(row + 5, ymax); rg_max(row + 6, xmax);
-        rg_add(row + 7, sz); rg_add(row + 8, sy); rg_add(row + 9, sx);
+        run_add(row + 7, sz); run_add(row + 8, sy); run_add(row + 9, sx);
     }
 };
 
@@ -130,7 +120,7 @@ __global__ __launch_bounds__(256) void rg_props_kernel(const int* __restrict__ l
             u64 m = pend_key ? __ballot(key == pend_key) : 0ull;
             if (!m) {
                 if (pend_key && lane == 0) pend.flush(T + (size_t)(pend_key - 1) * RG_COLS);
-                pend_key = __shfl(key, rg_ctz(fg));
+                pend_key = __shfl(key, run_ctz(fg));
                 pend.clear();
                 m = __ballot(key == pend_key);
             }
@@ -138,12 +128,12 @@ __global__ __launch_bounds__(256) void rg_props_kernel(const int* __restrict__ l
             const int below = __shfl_up(key, 1);
             const u64 heads = __ballot(lane == 0 || key != below);
             if (key > 0 && key != pend_key && (lane == 0 || key != below)) {
-                const int len = rg_run_length(heads, lane);
+                const int len = run_length(heads, lane);
                 i64* r = T + (size_t)(key - 1) * RG_COLS;
-                rg_add(r + 0, len);
+                run_add(r + 0, len);
                 rg_min(r + 1, z); rg_min(r + 2, y); rg_min(r + 3, x);
                 rg_max(r + 4, z); rg_max(r + 5, y); rg_max(r + 6, x + len - 1);
-                rg_add(r + 7, (i64)z * len); rg_add(r + 8, (i64)y * len); rg_add(r + 9, (i64)x * len + (i64)len * (len - 1) / 2);
+                run_add(r + 7, (i64)z * len); run_add(r + 8, (i64)y * len); run_add(r + 9, (i64)x * len + (i64)len * (len - 1) / 2);
             }
         }
         if (lane == 0) {
@@ -187,13 +177,13 @@ __global__ __launch_bounds__(256) void rg_contingency_lds_kernel(const int* __re
         const int below = __shfl_up(key, 1);
         const bool head = lane == 0 || key != below;
         const u64 heads = __ballot(head);
-        if (head && key >= 0) atomicAdd(&cells[key], (unsigned int)rg_run_length(heads, lane));
+        if (head && key >= 0) atomicAdd(&cells[key], (unsigned int)run_length(heads, lane));
     }
     if (lane == 0 && bad) atomicAdd(&bad_total, bad);
     __syncthreads();
     i64* T = table + (size_t)plane * ncells;
     for (int i = threadIdx.x; i < ncells; i += 256)
-        if (cells[i]) rg_add(T + i, (i64)cells[i]);
+        if (cells[i]) run_add(T + i, (i64)cells[i]);
     if (threadIdx.x == 0 && bad_total) atomicAdd(overflow + plane, bad_total);
 }
 
@@ -221,8 +211,8 @@ __global__ __launch_bounds__(256) void rg_contingency_kernel(const int* __restri
             if (!counted) continue;
             u64 m = pend_key >= 0 ? __ballot(key == pend_key) : 0ull;
             if (!m) {
-                if (pend_key >= 0 && lane == 0) rg_add(T + pend_key, pend_cnt);
-                pend_key = __shfl(key, rg_ctz(counted));
+                if (pend_key >= 0 && lane == 0) run_add(T + pend_key, pend_cnt);
+                pend_key = __shfl(key, run_ctz(counted));
                 pend_cnt = 0;
                 m = __ballot(key == pend_key);
             }
@@ -230,10 +220,10 @@ __global__ __launch_bounds__(256) void rg_contingency_kernel(const int* __restri
             const int below = __shfl_up(key, 1);
             const bool head = lane == 0 || key != below;
             const u64 heads = __ballot(head);
-            if (head && key >= 0 && key != pend_key) rg_add(T + key, (i64)rg_run_length(heads, lane));
+            if (head && key >= 0 && key != pend_key) run_add(T + key, (i64)run_length(heads, lane));
         }
         if (lane == 0) {
-            if (pend_key >= 0) rg_add(T + pend_key, pend_cnt);
+            if (pend_key >= 0) run_add(T + pend_key, pend_cnt);
             if (bad) atomicAdd(overflow + plane, bad);
         }
     }

@@ -24,7 +24,7 @@
 // index is clamped into its axis and every store is bounded by (x, y, z) alone, so no geometry can address outside either buffer.
 #include <math.h>
 #include <stdint.h>
-#include "common.h"
+#include "volume.h"
 
 namespace {
 
@@ -33,11 +33,6 @@ struct sc_geom {
     int n1[3];       // the 1 mm grid (D1, H1, W1)
     int x, y, z;     // the raw grid
     int flip[3];     // oriented axis order: (y, x, z)
-};
-
-struct sc_axis {
-    int i0, i1;      // the two 1 mm indices (nearest: both the same)
-    double t;        // the weight of i1
 };
 
 constexpr long long SC_GRID_CAP = 1 << 16;
@@ -49,9 +44,9 @@ struct alignas(4 * sizeof(T)) sc_vec4 {
 
 // the 1 mm coordinate of oriented index o along an axis of n_o oriented and n_1 1 mm rows
 template <int LINEAR>
-__device__ __forceinline__ void sc_coord(int o, int n_o, int n_1, sc_axis& a) {
+__device__ __forceinline__ void sc_coord(int o, int n_o, int n_1, rs_axis& a) {
     const double q = ((double)o + 0.5) * n_1 / n_o - 0.5;
-    if (LINEAR) {
+    if (LINEAR) {                                              // reflected at both ends before the clamp: not rs_axis_at's rule
         const double top = (double)(n_1 - 1);
         double c = q < 0.0 ? -q : (q > top ? 2.0 * top - q : q);
         c = fmin(fmax(c, 0.0), top);
@@ -60,9 +55,8 @@ __device__ __forceinline__ void sc_coord(int o, int n_o, int n_1, sc_axis& a) {
         a.i1 = i + 1 < n_1 ? i + 1 : n_1 - 1;
         a.t = c - (double)i;
     } else {
-        const double r = fmin(fmax(floor(q + 0.5), 0.0), (double)(n_1 - 1));
-        a.i0 = a.i1 = (int)r;
         a.t = 0.0;
+        rs_axis_at<0>(q, n_1, a);
     }
 }
 
@@ -109,7 +103,7 @@ __global__ __launch_bounds__(256) void scan_native_kernel(const float* __restric
         const int i1 = (int)(r % g.y), i0 = (int)(r / g.y);
         const int z0 = 4 * qd, n = g.z - z0 < 4 ? g.z - z0 : 4;
         const size_t vrow = (size_t)r * g.z + z0;
-        sc_axis ad, ah, aw[4];
+        rs_axis ad, ah, aw[4];
         sc_coord<LINEAR>(g.flip[0] ? g.y - 1 - i1 : i1, g.y, g.n1[0], ad);
         sc_coord<LINEAR>(g.flip[1] ? g.x - 1 - i0 : i0, g.x, g.n1[1], ah);
 #pragma unroll
@@ -117,10 +111,7 @@ __global__ __launch_bounds__(256) void scan_native_kernel(const float* __restric
             const int i2 = z0 + e < g.z ? z0 + e : g.z - 1;
             sc_coord<LINEAR>(g.flip[2] ? g.z - 1 - i2 : i2, g.z, g.n1[2], aw[e]);
         }
-        // the four 1 mm rows this thread reads and their weights
-        const size_t r00 = ((size_t)ad.i0 * H1 + ah.i0) * W1, r01 = ((size_t)ad.i0 * H1 + ah.i1) * W1;
-        const size_t r10 = ((size_t)ad.i1 * H1 + ah.i0) * W1, r11 = ((size_t)ad.i1 * H1 + ah.i1) * W1;
-        const double w00 = (1.0 - ad.t) * (1.0 - ah.t), w01 = (1.0 - ad.t) * ah.t, w10 = ad.t * (1.0 - ah.t), w11 = ad.t * ah.t;
+        const rs_rows rows(ad, ah, H1, W1);                    // the four 1 mm rows this thread reads and their weights
         float best[4];
         int arg[4] = {0, 0, 0, 0};
         for (int k = 0; k < g.k; ++k) {
@@ -128,15 +119,7 @@ __global__ __launch_bounds__(256) void scan_native_kernel(const float* __restric
             float a[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                if (LINEAR) {
-                    const int xa = aw[e].i0, xb = aw[e].i1;
-                    const double ta = 1.0 - aw[e].t, tb = aw[e].t;
-                    const double sa = w00 * (double)plane[r00 + xa] + w01 * (double)plane[r01 + xa] + w10 * (double)plane[r10 + xa] + w11 * (double)plane[r11 + xa];
-                    const double sb = w00 * (double)plane[r00 + xb] + w01 * (double)plane[r01 + xb] + w10 * (double)plane[r10 + xb] + w11 * (double)plane[r11 + xb];
-                    a[e] = (float)(ta * sa + tb * sb);
-                } else {
-                    a[e] = plane[r00 + aw[e].i0];
-                }
+                a[e] = rows.sample<LINEAR>(plane, aw[e]);
                 if (k == 0) {
                     best[e] = a[e];
                 } else if (a[e] > best[e] || (a[e] != a[e] && best[e] == best[e])) {
@@ -173,7 +156,7 @@ __global__ __launch_bounds__(256) void scan_native_label_kernel(const unsigned c
         const long long r = i / nq;
         const int i1 = (int)(r % g.y), i0 = (int)(r / g.y);
         const int z0 = 4 * qd, n = g.z - z0 < 4 ? g.z - z0 : 4;
-        sc_axis ad, ah, aw;
+        rs_axis ad, ah, aw;
         sc_coord<0>(g.flip[0] ? g.y - 1 - i1 : i1, g.y, g.n1[0], ad);
         sc_coord<0>(g.flip[1] ? g.x - 1 - i0 : i0, g.x, g.n1[1], ah);
         const unsigned char* row = src + ((size_t)ad.i0 * g.n1[1] + ah.i0) * g.n1[2];

@@ -201,28 +201,6 @@ __global__ __launch_bounds__(256) void sf_line_kernel(T* __restrict__ G, long lo
 }
 
 // ---- metric reduction ----------------------------------------------------------------------------------------------------------------------
-template <int NT>
-__device__ __forceinline__ int sf_block_excl_scan(int val, int* total, int* lds) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = val;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) lds[wv] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int j = 0; j < NT / 64; ++j) {
-        const int s = lds[j];
-        if (j < wv) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - val;
-}
 
 // a fixed tree: xor butterflies inside the wave, then the waves in order
 template <int NT, typename T>
@@ -294,7 +272,7 @@ __global__ __launch_bounds__(256) void sf_chunk_kernel(const unsigned char* __re
         const T v = on ? m[e] : (T)0;
         if (SCATTER) {
             int tot;
-            const int ex = sf_block_excl_scan<256>(on, &tot, lds_i);
+            const int ex = block_excl_scan<256>(on, &tot, lds_i);
             if (on) list[(size_t)p * g.cap + first + carry + ex] = v;
             carry += tot;
         } else {
@@ -305,7 +283,7 @@ __global__ __launch_bounds__(256) void sf_chunk_kernel(const unsigned char* __re
     }
     if (!SCATTER) {
         int tot;
-        sf_block_excl_scan<256>(carry, &tot, lds_i);
+        block_excl_scan<256>(carry, &tot, lds_i);
         const double s = sf_block_sum<256, double>(sum, lds_d);
         const T x = sf_block_max<256>(mx, lds_t);
         if (threadIdx.x == 0) {
@@ -346,7 +324,7 @@ __global__ __launch_bounds__(SF_SEL_NT) void sf_scan_kernel(int* __restrict__ cn
                 mx = maxs[at + i] > mx ? maxs[at + i] : mx;
             }
             int tot;
-            const int ex = sf_block_excl_scan<SF_SEL_NT>(val, &tot, lds_i);
+            const int ex = block_excl_scan<SF_SEL_NT>(val, &tot, lds_i);
             if (i < g.nb) cnts[at + i] = carry + ex;
             carry += tot;
         }

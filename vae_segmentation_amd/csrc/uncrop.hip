@@ -19,7 +19,7 @@
 // clamped to [0, P - 1] and every store is bounded by (D, H, W) alone, so no geometry can address outside either buffer.
 #include <math.h>
 #include <stdint.h>
-#include "common.h"
+#include "volume.h"
 
 namespace {
 
@@ -29,31 +29,16 @@ struct uc_geom {
     int side;
 };
 
-struct uc_axis {
-    int i0, i1;      // the two patch indices (nearest: both the same)
-    double t;        // the weight of i1
-};
-
 constexpr long long UC_GRID_CAP = 1 << 20;
 
 // the patch coordinate of scan index v along one axis, or false outside the cube's rows
 template <int LINEAR>
-__device__ __forceinline__ bool uc_coord(int v, int lo, int hi, int off, int side, int p, uc_axis& a) {
+__device__ __forceinline__ bool uc_coord(int v, int lo, int hi, int off, int side, int p, rs_axis& a) {
     a.i0 = a.i1 = 0;
     a.t = 0.0;
     if (v < lo || v >= hi) return false;
     const double u = (double)v - (double)lo + (double)off;
-    const double q = (u + 0.5) * p / side - 0.5;
-    if (LINEAR) {
-        const double c = fmin(fmax(q, 0.0), (double)(p - 1));
-        const int i = (int)floor(c);
-        a.i0 = i;
-        a.i1 = i + 1 < p ? i + 1 : p - 1;
-        a.t = c - (double)i;
-    } else {
-        const double r = fmin(fmax(floor(q + 0.5), 0.0), (double)(p - 1));
-        a.i0 = a.i1 = (int)r;
-    }
+    rs_axis_at<LINEAR>((u + 0.5) * p / side - 0.5, p, a);
     return true;
 }
 
@@ -67,17 +52,14 @@ __global__ __launch_bounds__(256) void uncrop_kernel(const float* __restrict__ p
         const int y = (int)(r % g.h), z = (int)(r / g.h);
         const int x0 = 4 * qd, n = g.w - x0 < 4 ? g.w - x0 : 4;
         const size_t vrow = ((size_t)z * g.h + y) * g.w + x0;
-        uc_axis az, ay, ax[4];
+        rs_axis az, ay, ax[4];
         const bool in_z = uc_coord<LINEAR>(z, g.lo[0], g.hi[0], g.off[0], g.side, g.p, az);
         const bool in_zy = uc_coord<LINEAR>(y, g.lo[1], g.hi[1], g.off[1], g.side, g.p, ay) && in_z;
         unsigned in = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (uc_coord<LINEAR>(x0 + e, g.lo[2], g.hi[2], g.off[2], g.side, g.p, ax[e]) && in_zy && e < n) in |= 1u << e;
-        // the four patch rows this thread reads and their weights
-        const size_t r00 = ((size_t)az.i0 * g.p + ay.i0) * g.p, r01 = ((size_t)az.i0 * g.p + ay.i1) * g.p;
-        const size_t r10 = ((size_t)az.i1 * g.p + ay.i0) * g.p, r11 = ((size_t)az.i1 * g.p + ay.i1) * g.p;
-        const double w00 = (1.0 - az.t) * (1.0 - ay.t), w01 = (1.0 - az.t) * ay.t, w10 = az.t * (1.0 - ay.t), w11 = az.t * ay.t;
+        const rs_rows rows(az, ay, g.p, g.p);                  // the four patch rows this thread reads and their weights
         float best[4];
         int arg[4] = {0, 0, 0, 0};
         for (int k = 0; k < g.k; ++k) {
@@ -86,18 +68,7 @@ __global__ __launch_bounds__(256) void uncrop_kernel(const float* __restrict__ p
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 a[e] = k == 0 ? 1.f : 0.f;
-                if (in & (1u << e)) {
-                    if (LINEAR) {
-                        const int xa = ax[e].i0, xb = ax[e].i1;
-                        const double ta = 1.0 - ax[e].t, tb = ax[e].t;
-                        const double sa = w00 * (double)plane[r00 + xa] + w01 * (double)plane[r01 + xa] + w10 * (double)plane[r10 + xa] + w11 * (double)plane[r11 + xa];
-                        const double sb = w00 * (double)plane[r00 + xb] + w01 * (double)plane[r01 + xb] + w10 * (double)plane[r10 + xb] + w11 * (double)plane[r11 + xb];
-                        const double s = ta * sa + tb * sb;
-                        a[e] = (float)s;
-                    } else {
-                        a[e] = plane[r00 + ax[e].i0];
-                    }
-                }
+                if (in & (1u << e)) a[e] = rows.sample<LINEAR>(plane, ax[e]);
                 if (k == 0) {
                     best[e] = a[e];
                 } else if (a[e] > best[e] || (a[e] != a[e] && best[e] == best[e])) {
