@@ -694,6 +694,33 @@ int vs_joint_histogram(const float* x, const float* y, int n, int c, int d, int 
 int vs_mutual_information(const long long* table, int n, int c, int bins_x, int bins_y, double sigma, int normalized, double* workspace, double* mi,
                           void* stream);
 
+/* ---- exact percentiles and the piecewise-linear intensity map (csrc/quantile.hip) -------------------------------------------
+ * x: planar fp32 (planes, d, h, w), contiguous; every plane is its own problem; d*h*w < 2^31.
+ *   vs_quantile  A voxel is SELECTED iff it is finite, use_above == 0 or x > above (strict fp32 comparison), and mask == NULL or its mask byte
+ *                (uint8, x's shape) is not 0.  Non-finite voxels are never selected and are counted in rejected, whatever the selectors say.
+ *                With v[0] <= ... <= v[n-1] the selected values in fp64 and p01[i] in [0, 1] (HOST doubles, Q of them, 1 <= Q <= 16):
+ *                h = (double)(n - 1) * p01, k = floor(h), k1 = min(k + 1, n - 1), t = h - k, a = v[k], b = v[k1], d = b - a,
+ *                q_out = t >= 0.5 ? b - d * (1 - t) : a + d * t, every product and sum rounded separately (no fused multiply-add): the bits of
+ *                np.percentile(selected.astype(np.float64), 100 * p01).  lo_out = (float)a, hi_out = (float)b.  n == 0: the three are NaN.
+ *                q_out: fp64 (planes, Q); lo_out, hi_out: fp32 (planes, Q); count = n and rejected: int64 (planes).
+ *                A radix select over the order-preserving integer image of the fp32 bits, four passes of 8 bits for the 2 Q ranks at once; NINE
+ *                launches whatever the data.  workspace: vs_quantile_workspace_bytes(planes, d*h*w, Q) bytes (0 for arguments vs_quantile refuses),
+ *                16-byte aligned, contents undefined on entry: the first launch writes its initial state.
+ *   vs_intensity_map  src: fp64 (planes, L) in DEVICE memory, ascending landmarks per plane (vs_quantile's q_out); dst: fp64 (L) in device memory,
+ *                strictly ascending; 2 <= L <= 16.  For a finite voxel x, j = the largest index in [0, L - 2] with src[j] <= x (0 when x < src[0]),
+ *                w = src[j+1] - src[j], slope = w > 0 ? (dst[j+1] - dst[j]) / w : 0, y = dst[j] + (x - src[j]) * slope in fp64, products and sums
+ *                rounded separately, rounded to fp32 once.  clamp 0: the end segments run on; clamp 1: y is clamped to [dst[0], dst[L-1]].  A
+ *                non-finite voxel is written unchanged; a plane with a NaN landmark (nothing was selected) is copied.  One launch; y may be x.
+ * Nothing is allocated, synchronised or read back; no kernel waits for another workgroup; both calls can be captured in a HIP graph.  Every count is an
+ * integer added with vector-lane atomics: the same bits on every run, under replay and in both builds.  A null pointer (mask may be NULL), Q outside
+ * [1, 16], a p01 that is NaN or outside [0, 1], a NaN threshold, L outside [2, 16], clamp outside {0, 1}: VS_EINVAL; an empty plane or one of 2^31
+ * voxels or more: VS_ESHAPE; x, y, lo_out, hi_out not 4-byte, q_out, count, rejected, src, dst not 8-byte, workspace not 16-byte aligned: VS_EALIGN;
+ * all answered on the host before any launch. */
+size_t vs_quantile_workspace_bytes(int planes, long long V, int Q);
+int vs_quantile(const float* x, const unsigned char* mask, int use_above, float above, const double* p01, int Q, double* q_out, float* lo_out,
+                float* hi_out, long long* count, long long* rejected, void* workspace, int planes, int d, int h, int w, void* stream);
+int vs_intensity_map(const float* x, const double* src, const double* dst, int L, int clamp, float* y, int planes, int d, int h, int w, void* stream);
+
 /* ---- sliding-window prediction of a whole volume (csrc/window.hip; no counterpart in the reference) -------------------------------
  * A volume (C, D, H, W) is tiled with overlapping cubic windows of side `patch`, a network maps batches (B, C, P, P, P) of them to planar
  * probabilities (B, K, P, P, P), and the windows are blended: prob[k][v] = sum_i w_i(v) p_i[k](v) / sum_i w_i(v) over the windows i that cover

@@ -42,16 +42,6 @@ static_assert(HS_WG_VOXELS % (256 * HS_UNROLL) == 0, "every thread of a workgrou
 
 enum { HS_AUTO = 0, HS_LDS32 = 1, HS_PACKED = 2, HS_GLOBAL = 3 };
 
-
-
-// fp32 bits <-> an unsigned integer with the same order as the values (finite values never map to 0 or 0xffffffff)
-__device__ __forceinline__ unsigned int hs_enc(float f) {
-    const unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float hs_dec(unsigned int e) { return __uint_as_float((e & 0x80000000u) ? (e ^ 0x80000000u) : ~e); }
-__device__ __forceinline__ bool hs_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
-
 // np.linspace's edge: the product and the sum are rounded separately
 __device__ __forceinline__ double hs_edge(int i, double step, double lo) {
 #pragma clang fp contract(off)
@@ -131,8 +121,8 @@ __global__ __launch_bounds__(256) void hs_init_kernel(hs_job j) {
 }
 
 __device__ __forceinline__ void hs_minmax_fold(float v, bool live, unsigned int& mn, unsigned int& mx) {
-    if (live && hs_finite(v)) {
-        const unsigned int e = hs_enc(v);
+    if (live && key_finite(v)) {
+        const unsigned int e = key_enc(v);
         mn = min(mn, e);
         mx = max(mx, e);
     }
@@ -180,8 +170,8 @@ __global__ __launch_bounds__(256) void hs_edges_kernel(hs_job j) {
             const u64 mn = reinterpret_cast<const u64*>(E)[0], mx = reinterpret_cast<const u64*>(E)[B];
             lo = hi = 0.0;
             if (mn <= mx) {                                  // + 0.0: a zero bound is +0.0 whichever zero the data held
-                lo = (double)hs_dec((unsigned int)mn) + 0.0;
-                hi = (double)hs_dec((unsigned int)mx) + 0.0;
+                lo = (double)key_dec((unsigned int)mn) + 0.0;
+                hi = (double)key_dec((unsigned int)mx) + 0.0;
             }
         }
         if (lo == hi) {

@@ -1,5 +1,6 @@
 // Pieces the volume utility kernels share.  Included inside each translation unit: everything here has internal linkage.
 //   runs       regions.hip and hist.hip walk 64-voxel segments run by run: the 64-bit integer atomic add, the bit scan and a run's length from the ballot of heads
+//   keys       hist.hip and quantile.hip order fp32 values through an unsigned integer image of their bits
 //   resample   scan.hip and uncrop.hip map a (K, D, H, W) probability volume onto another grid, four consecutive x per thread: the two source indices and the
 //              weight of an axis, the trilinear blend in fp64
 #pragma once
@@ -18,6 +19,14 @@ __device__ __forceinline__ int run_length(u64 heads, int lane) {
     const u64 above = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1ull);
     return (above ? run_ctz(above) : 64) - lane;
 }
+
+// fp32 bits <-> an unsigned integer with the same order as the values (finite values never map to 0 or 0xffffffff)
+__device__ __forceinline__ unsigned int key_enc(float f) {
+    const unsigned int u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_dec(unsigned int e) { return __uint_as_float((e & 0x80000000u) ? (e ^ 0x80000000u) : ~e); }
+__device__ __forceinline__ bool key_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
 
 struct rs_axis {
     int i0, i1;      // the two source indices (nearest: both the same)

@@ -6,6 +6,8 @@ same names, constructor arguments and dict-in / dict-out protocol, operating on 
     MySpatialTransform        utils/utils.py:927-968   (batchgenerators augment_spatial: elastic deformation — which main_source.py:198 switches off;
                                                         here it needs a noise source chosen, see the class — rotation, scale, random crop)
     Clip, CenterIntensities   utils/utils.py:508-533, 575-618
+    IntensityStandardizer     no counterpart in the reference, whose window is a constant: a scan's own percentiles mapped onto that window (or, with fit(),
+                              onto a Nyul-Udupa standard scale) before everything else, exact order statistics found on the device
     IntensityAugment          no counterpart in the reference's loaders: the batchgenerators / nnU-Net intensity transforms it inherits and leaves off
                               (noise, blur, brightness, contrast, simulated low resolution, gamma, mirror), applied after CenterIntensities; intensity_augment is its functional form
 
@@ -435,6 +437,100 @@ class CenterIntensities(BaseTransform):
                 x = data_dict[f].contiguous()
                 check(lib.vs_data_clip_center(x.data_ptr(), x.numel(), -3.0e38, 3.0e38, float(self.subtrahend), float(self.divisor), _stream()), "data_clip_center")
                 data_dict[f] = x
+        return data_dict
+
+
+class IntensityStandardizer(BaseTransform):
+    """Intensity standardisation of scans by their own order statistics, on the device (no counterpart in the reference, whose window is written for one
+    protocol): the exact `percentiles` of a scan — of its voxels above `above`, under `mask` — are landmarks, and the scan is mapped piecewise linearly so
+    that they land on the standard scale (ops.quantile -> ops.intensity_map, the landmarks never leave the device).  Two percentiles (nnU-Net: 0.5, 99.5):
+    the standard scale IS `target`, e.g. the window Clip expects, and nothing is fitted.  More (Nyul and Udupa, e.g. (1, 10, 20, ..., 90, 99)): fit() forms
+    the scale from training scans.  extrapolate: "linear" lets the end segments run on, "clamp" holds the ends of the scale.  fields: what __call__
+    standardises in a data dict (the BaseTransform convention).  DESIGN 3.18 holds the two rules."""
+
+    def __init__(self, percentiles=(0.5, 99.5), target=(-200.0, 400.0), above=None, extrapolate="linear", fields="venous"):
+        from .ops import INTENSITY_MAP_EXTRAPOLATE, INTENSITY_MAP_MAX_L
+        super().__init__(fields)
+        try:
+            ps, tg = tuple(float(p) for p in percentiles), tuple(float(t) for t in target)
+        except (TypeError, ValueError):
+            raise ValueError("IntensityStandardizer: percentiles and target are sequences of numbers, got %r and %r" % (percentiles, target)) from None
+        if not 2 <= len(ps) <= INTENSITY_MAP_MAX_L:
+            raise ValueError("IntensityStandardizer: 2 to %d percentiles, got %d" % (INTENSITY_MAP_MAX_L, len(ps)))
+        if not all(np.isfinite(p) and 0.0 <= p <= 100.0 for p in ps) or any(b <= a for a, b in zip(ps, ps[1:])):
+            raise ValueError("IntensityStandardizer: percentiles are strictly ascending in [0, 100], got %r" % (ps,))
+        if len(tg) != 2 or not all(np.isfinite(t) for t in tg) or not tg[0] < tg[1]:
+            raise ValueError("IntensityStandardizer: target is an ascending pair of finite numbers, got %r" % (tg,))
+        if above is not None and not np.isfinite(float(above)):
+            raise ValueError("IntensityStandardizer: above is a finite number or None, got %r" % (above,))
+        if extrapolate not in INTENSITY_MAP_EXTRAPOLATE:
+            raise ValueError("IntensityStandardizer: extrapolate is 'linear' or 'clamp', got %r" % (extrapolate,))
+        self.percentiles, self.target, self.extrapolate = ps, tg, extrapolate
+        self.above = None if above is None else float(above)
+        self.scale = list(tg) if len(ps) == 2 else None           # the standard scale, host floats; None until fit()
+        self._dst = {}
+
+    def landmarks(self, x, mask=None):
+        """the percentiles of every (D, H, W) plane of x -> fp64 (..., L) on the device (NaN rows where nothing is selected)"""
+        from . import ops
+        return ops.quantile(x, self.percentiles, above=self.above, mask=mask)["q"]
+
+    def fit(self, volumes, masks=None):
+        """The standard scale from training scans (Nyul and Udupa): the landmarks s of each scan mapped affinely so that s[0] -> target[0] and
+        s[L-1] -> target[1], averaged over the scans in list order, in fp64 on the device.  One read-back, at the end, checks the scale."""
+        volumes = list(volumes)
+        masks = [None] * len(volumes) if masks is None else list(masks)
+        if not volumes or len(masks) != len(volumes):
+            raise ValueError("IntensityStandardizer.fit: at least one volume, and a mask (or None) for each")
+        total, cases = None, 0
+        for x, m in zip(volumes, masks):
+            s = self.landmarks(x, m).reshape(-1, len(self.percentiles))
+            mapped = self.target[0] + (s - s[:, :1]) * ((self.target[1] - self.target[0]) / (s[:, -1:] - s[:, :1]))
+            for row in mapped:
+                total = row.clone() if total is None else total + row
+                cases += 1
+        scale = (total / cases).cpu().tolist()
+        if not all(np.isfinite(v) for v in scale) or any(b <= a for a, b in zip(scale, scale[1:])):
+            raise ValueError("IntensityStandardizer.fit: the fitted scale is not finite and strictly ascending (a scan without selected voxels, or "
+                             "percentiles that coincide in every scan): %r" % (scale,))
+        self.scale, self._dst = scale, {}
+        return self
+
+    def _scale_on(self, device):
+        if self.scale is None:
+            raise RuntimeError("IntensityStandardizer: %d percentiles need a standard scale: call fit() or load_state_dict() before transform()"
+                               % len(self.percentiles))
+        key = str(device)
+        if key not in self._dst:
+            self._dst[key] = torch.tensor(self.scale, dtype=torch.float64, device=device)
+        return self._dst[key]
+
+    def transform(self, x, mask=None):
+        """x float32 (..., D, H, W) on the device -> its standardised copy; ten launches, nothing synchronised or read back"""
+        from . import ops
+        dst = self._scale_on(x.device)
+        return ops.intensity_map(x, self.landmarks(x, mask), dst, extrapolate=self.extrapolate)
+
+    def state_dict(self):
+        return {"percentiles": tuple(self.percentiles), "target": tuple(self.target), "above": self.above, "extrapolate": self.extrapolate,
+                "scale": None if self.scale is None else list(self.scale)}
+
+    def load_state_dict(self, state):
+        other = IntensityStandardizer(state["percentiles"], state["target"], state["above"], state.get("extrapolate", "linear"), self.fields)
+        scale = state["scale"]
+        if scale is not None:
+            scale = [float(v) for v in scale]
+            if len(scale) != len(other.percentiles) or not all(np.isfinite(v) for v in scale) or any(b <= a for a, b in zip(scale, scale[1:])):
+                raise ValueError("IntensityStandardizer.load_state_dict: the scale has one finite value per percentile, strictly ascending, got %r" % (scale,))
+            other.scale = scale
+        self.percentiles, self.target, self.above, self.extrapolate, self.scale, self._dst = (other.percentiles, other.target, other.above,
+                                                                                              other.extrapolate, other.scale, {})
+        return self
+
+    def __call__(self, data_dict):
+        for f in self.fields:
+            if data_dict.get(f) is not None:
+                data_dict[f] = self.transform(data_dict[f].contiguous())
         return data_dict
 
 

@@ -115,7 +115,20 @@ class DeviceCaseLoader:
             lowres = {"p_lowres": p_lr} if p_lr > 0 else {}
             self.intensity = data_gpu.IntensityAugment(IMG_KEY, LABEL_KEY, rng=np.random.RandomState(seed + 1000 * rank + 500), noise="philox",
                                                        seed=seed + 1000 * rank, **lowres)
+        self.standardize = None
+        if getattr(args, "standardize", None) is not None:
+            # --standardize: the case's percentile window onto Clip's, before anything else sees the image; the pipeline behind it keeps its constants
+            from . import evaluation
+            self.standardize = data_gpu.IntensityStandardizer(tuple(args.standardize), target=evaluation.INTENSITY_CLIP,
+                                                              above=getattr(args, "standardize_above", None))
         self._dg = data_gpu
+
+    def _load(self, name):
+        """a case's merge array on the device; with --standardize its image channel standardised"""
+        merge = torch.from_numpy(np.load(os.path.join(self.root, name)).astype(np.float32)).cuda(non_blocking=True)
+        if self.standardize is not None:
+            merge[..., 0] = self.standardize.transform(merge[..., 0].contiguous())
+        return merge
 
     def set_epoch(self, epoch):
         self.epoch = epoch
@@ -126,7 +139,7 @@ class DeviceCaseLoader:
     def whole_cases(self):
         """--val_whole_volume: every case as it is on disk — (raw image (D, H, W), relabelled label (D, H, W)) on the device, in list order, uncropped"""
         for name in self.names:
-            merge = torch.from_numpy(np.load(os.path.join(self.root, name)).astype(np.float32)).cuda(non_blocking=True)
+            merge = self._load(name)
             yield merge[..., 0].contiguous(), self._dg.relabel(merge[..., 1].contiguous(), self.mask_index)
 
     def __iter__(self):
@@ -136,7 +149,7 @@ class DeviceCaseLoader:
         for b in range(len(self)):
             imgs, labs = [], []
             for i in order[b * self.bs:(b + 1) * self.bs]:
-                merge = torch.from_numpy(np.load(os.path.join(self.root, self.names[i])).astype(np.float32)).cuda(non_blocking=True)
+                merge = self._load(self.names[i])
                 extra = {} if self.intensity is None else {"intensity": self.intensity}
                 img, lab = self._dg.train_sample(merge, self.patch, self.mask_index, self.transform, field=IMG_KEY, shift=self.shift, **extra)
                 imgs.append(img); labs.append(lab)
@@ -985,14 +998,29 @@ def _probability(text):
     return v
 
 
+def _percentile_pair(text):
+    import argparse
+    try:
+        lo, hi = (float(v) for v in text.split(","))
+    except ValueError:
+        lo = hi = float("nan")
+    if not 0.0 <= lo < hi <= 100.0:
+        raise argparse.ArgumentTypeError("two ascending percentiles P_LO,P_HI in [0, 100], got %r" % text)
+    return lo, hi
+
+
 def check_aug_flags(parser, a):
-    """--aug_elastic and --aug_intensity act on the augmented training samples: with --no_aug there are none"""
+    """--aug_elastic and --aug_intensity act on the augmented training samples: with --no_aug there are none; --standardize reads real cases"""
     if getattr(a, "aug_elastic", 0.0) > 0 and getattr(a, "no_aug", False):
         parser.error("--aug_elastic deforms the augmented training samples: it cannot be combined with --no_aug")
     if getattr(a, "aug_intensity", False) and getattr(a, "no_aug", False):
         parser.error("--aug_intensity changes the grey values of the augmented training samples: it cannot be combined with --no_aug")
     if getattr(a, "aug_lowres", 0.0) > 0 and not getattr(a, "aug_intensity", False):
         parser.error("--aug_lowres is a stage of the intensity augmentation: it needs --aug_intensity")
+    if getattr(a, "standardize", None) is not None and not getattr(a, "real_data", False):
+        parser.error("--standardize reads the percentiles of merge.npy cases: it needs --real_data")
+    if getattr(a, "standardize_above", None) is not None and getattr(a, "standardize", None) is None:
+        parser.error("--standardize_above selects the voxels --standardize reads: it needs --standardize")
     return a
 
 
@@ -1010,6 +1038,12 @@ def add_native_flags(parser):
     g.add_argument("--aug_lowres", type=_probability, default=0.0, metavar="P", help="with --aug_intensity: nnU-Net's simulated low resolution of a training "
                    "sample with probability P (nnU-Net: 0.25), between contrast and the gammas — per channel with probability 0.5 a zoom from U(0.5, 1), "
                    "down by nearest neighbour, back up by a cubic spline with edge boundaries, clipped, on the device (ops.simulate_lowres); 0 = off")
+    g.add_argument("--standardize", type=_percentile_pair, default=None, metavar="P_LO,P_HI", help="with --real_data: map every case's image, right after "
+                   "the load and before every other transform, linearly so that its P_LO and P_HI percentiles (nnU-Net: 0.5,99.5) land on the window "
+                   "Clip expects (-200, 400), exact percentiles found on the device (data_gpu.IntensityStandardizer) — for scans whose unit is not "
+                   "Hounsfield; training, validation and pseudo-label loaders alike; off: the reference's setting")
+    g.add_argument("--standardize_above", type=float, default=None, metavar="T", help="with --standardize: the percentiles are those of the voxels above T "
+                   "(strictly), e.g. to leave the air around the body out")
     g.add_argument("--latent_noise", default="torch", choices=["torch", "philox"], help="vae_train / embed_train / refine_vae: where the VAE's latent noise "
                    "comes from — torch: torch.randn per call, the step launched eagerly (the reference's draw); philox: a stated Philox4x32-10 stream per "
                    "rank (ops.LatentStream, seed 1000 rank + 700) drawn inside the forward launch from a counter in device memory, so the step is captured "

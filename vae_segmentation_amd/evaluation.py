@@ -561,7 +561,7 @@ def _window_intensities(data_dict):
 
 @torch.no_grad()
 def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", batch=1, keep_largest=1, min_size=0, interp="linear", graph=False, tta=None,
-                           want_prob=False):
+                           want_prob=False, standardize=None):
     """Label-free segmentation of a raw scan `image` (D, H, W) on the device, returned in the scan's own geometry.  The composition of the public pieces:
       coarse   Clip / CenterIntensities -> sliding_window_predict with cubic windows of side `patch` -> localise (keep_largest, min_size) -> data_gpu.bounding_box
                (the chain's one host synchronisation)
@@ -573,12 +573,16 @@ def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", bat
     tta (tta_flips): mirror test-time augmentation of both passes.  The coarse pass receives it; the fine pass is a sliding-window pass over the crop
     itself — one window, constant blend — so its probabilities are the mean of the un-flipped answers, summed in the order of the codes.
     want_prob=True adds "prob": the pasted probabilities (K, D, H, W) fp32 of ops.uncrop(want_prob=True) — (1, 0, ..., 0) outside the crop and
-    everywhere when nothing was found."""
+    everywhere when nothing was found.
+    standardize (a data_gpu.IntensityStandardizer): its transform of the scan takes the scan's place before anything else — for scans whose unit is not
+    the one INTENSITY_CLIP is written in; None: nothing more is launched."""
     from . import data_gpu
     ops._require_cuda(image)
     if image.dim() != 3:
         raise ValueError("coarse_to_fine_predict: expected a (D, H, W) scan, got shape %s" % (tuple(image.shape),))
     img = image.detach().float().contiguous()
+    if standardize is not None:
+        img = standardize.transform(img)
     model_fn = segmentation_model_fn(seg)
     lo_v, hi_v = INTENSITY_CLIP
     cval = (min(max(0.0, lo_v), hi_v) - INTENSITY_CENTRE[0]) / INTENSITY_CENTRE[1]
@@ -609,10 +613,11 @@ def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", bat
 
 @torch.no_grad()
 def predict_scan(seg, raw, affine_diag, patch, overlap=0.5, blend="gaussian", batch=1, keep_largest=1, min_size=0, interp="linear", graph=False, tta=None,
-                 native_interp="linear", details=False):
+                 native_interp="linear", details=False, standardize=None):
     """A scan as the scanner wrote it in, a label on that scan's own voxel grid out, without leaving the device.  raw (X, Y, Z): CUDA int16 / uint8 /
     int8 / float32; affine_diag: the signed diagonal of its affine.  By definition the two-step composition of the public pieces:
       data_gpu.preprocess_scan               orient + resize to the 1 mm grid (data_process.py:23-34)
+      standardize.transform                  only with standardize (a data_gpu.IntensityStandardizer): the 1 mm image onto the standard scale
       coarse_to_fine_predict(want_prob=True) with the options of that function: probabilities pasted onto the 1 mm grid by ops.uncrop(interp)
       ops.to_native(native_interp)           those probabilities resampled onto the raw grid, argmax
     The two resamplings (crop -> 1 mm, 1 mm -> raw) are NOT fused into one map: that would change the values.
@@ -620,7 +625,7 @@ def predict_scan(seg, raw, affine_diag, patch, overlap=0.5, blend="gaussian", ba
     from . import data_gpu
     pre = data_gpu.preprocess_scan(raw, affine_diag)
     res = coarse_to_fine_predict(seg, pre["image"], patch, overlap=overlap, blend=blend, batch=batch, keep_largest=keep_largest, min_size=min_size,
-                                 interp=interp, graph=graph, tta=tta, want_prob=True)
+                                 interp=interp, graph=graph, tta=tta, want_prob=True, standardize=standardize)
     label = ops.to_native(res["prob"], pre["geometry"], interp=native_interp)["label"]
     if not details:
         return label

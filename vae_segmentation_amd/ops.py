@@ -3283,6 +3283,85 @@ def simulate_lowres(x, target_shape, order_down=0, order_up=3):
     return zoom_edge(t, (d, h, w), order_up, clip=order_up > 0)
 
 
+# ---- exact percentiles and the piecewise-linear intensity map (csrc/quantile.hip) --------------------------------------------------------
+QUANTILE_MAX_Q = 16
+QUANTILE_WG_VOXELS = 16384          # csrc/quantile.hip QS_WG_VOXELS: the voxels of a plane one workgroup of a counting pass reads (a hand-kept mirror,
+                                    # as INTENSITY_MAP_WG_VOXELS is of IM_WG_VOXELS: the library does not export them; change both files together)
+INTENSITY_MAP_MAX_L = 16
+INTENSITY_MAP_WG_VOXELS = 4096      # csrc/quantile.hip IM_WG_VOXELS
+INTENSITY_MAP_EXTRAPOLATE = ("linear", "clamp")
+
+
+def quantile(x, q, above=None, mask=None):
+    """Exact percentiles of every (D, H, W) plane of a contiguous CUDA float32 tensor (..., D, H, W); q: 1 to 16 percentiles in [0, 100], host floats.
+    A voxel is selected iff it is finite, `above` is None or x > np.float32(above) (strict), and `mask` (uint8 or bool, x's shape) is None or non-zero
+    there.  With v the n selected values sorted, in fp64: h = (n - 1) * (p / 100), k = floor(h), t = h - k, a = v[k], b = v[min(k + 1, n - 1)] and
+    t >= 0.5 ? b - (b - a) (1 - t) : a + (b - a) t, each operation rounded on its own — the bits of np.percentile(selected.astype(float64), p).
+    -> {"q": fp64 (..., Q); "lo", "hi": float32 (..., Q), a and b; "count": int64 (...), n; "rejected": int64 (...), the non-finite voxels}, on the
+    device; n == 0 gives NaN.  A radix select, nine launches whatever the data; nothing is synchronised or read back (vs_quantile)."""
+    import math
+    planes, d, h, w = _aug_planes(x, "quantile")
+    try:
+        ps = [float(v) for v in (q if hasattr(q, "__iter__") else [q])]
+    except (TypeError, ValueError):
+        raise ValueError("quantile: q is a percentile or a sequence of percentiles, got %r" % (q,)) from None
+    if not 1 <= len(ps) <= QUANTILE_MAX_Q:
+        raise ValueError("quantile: 1 to %d percentiles, got %d" % (QUANTILE_MAX_Q, len(ps)))
+    if any(not math.isfinite(p) or p < 0.0 or p > 100.0 for p in ps):
+        raise ValueError("quantile: percentiles are finite numbers in [0, 100], got %r" % (ps,))
+    use_above, thr = 0, 0.0
+    if above is not None:
+        thr = float(above)
+        if math.isnan(thr):
+            raise ValueError("quantile: above is a number, got %r" % (above,))
+        use_above = 1
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
+            raise TypeError("quantile: mask is a uint8 or bool tensor, got %s" % getattr(mask, "dtype", type(mask)))
+        if mask.shape != x.shape or mask.device != x.device or not mask.is_contiguous():
+            raise ValueError("quantile: mask is a contiguous tensor of x's shape on x's device, got %s on %s" % (tuple(mask.shape), mask.device))
+    nq, lead = len(ps), tuple(x.shape[:-3])
+    p01 = (_ctypes.c_double * nq)(*[p / 100.0 for p in ps])
+    out = {"q": torch.empty(lead + (nq,), dtype=torch.float64, device=x.device),
+           "lo": torch.empty(lead + (nq,), dtype=torch.float32, device=x.device),
+           "hi": torch.empty(lead + (nq,), dtype=torch.float32, device=x.device),
+           "count": torch.empty(lead, dtype=torch.int64, device=x.device),
+           "rejected": torch.empty(lead, dtype=torch.int64, device=x.device)}
+    ws = torch.empty((int(lib.vs_quantile_workspace_bytes(planes, d * h * w, nq)) + 15) // 16 * 2, dtype=torch.float64, device=x.device)
+    check(lib.vs_quantile(x.data_ptr(), _p(mask), use_above, thr, _ctypes.addressof(p01), nq, out["q"].data_ptr(), out["lo"].data_ptr(),
+                          out["hi"].data_ptr(), out["count"].data_ptr(), out["rejected"].data_ptr(), ws.data_ptr(), planes, d, h, w, _stream()), "quantile")
+    return out
+
+
+def intensity_map(x, src, dst, extrapolate="linear", out=None):
+    """The piecewise-linear map of every (D, H, W) plane of a contiguous CUDA float32 tensor (..., D, H, W) through landmarks on the device: src fp64
+    (..., L), one ascending row per plane (quantile's "q", never copied to the host); dst fp64 (L,), strictly ascending, for all planes; 2 <= L <= 16.
+    A finite voxel x with j the largest index in [0, L - 2] with src[j] <= x (0 below src[0]): y = dst[j] + (x - src[j]) * slope, slope =
+    (dst[j+1] - dst[j]) / (src[j+1] - src[j]) or 0 for a segment of no width, in fp64, each operation rounded on its own, rounded to float32 once.
+    extrapolate "linear": the end segments run on; "clamp": y is clamped to [dst[0], dst[L-1]].  A non-finite voxel and a plane with NaN landmarks
+    are written unchanged.  -> float32 of x's shape (`out`, which may be x).  One launch, no synchronisation (vs_intensity_map)."""
+    planes, d, h, w = _aug_planes(x, "intensity_map")
+    if extrapolate not in INTENSITY_MAP_EXTRAPOLATE:
+        raise ValueError("intensity_map: extrapolate is 'linear' or 'clamp', got %r" % (extrapolate,))
+    for t, what in ((src, "src"), (dst, "dst")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise TypeError("intensity_map: %s is a float64 tensor on the device, got %s" % (what, getattr(t, "dtype", type(t))))
+        if t.device != x.device or not t.is_contiguous():
+            raise ValueError("intensity_map: %s is contiguous and on x's device" % what)
+    if dst.dim() != 1 or not 2 <= dst.shape[0] <= INTENSITY_MAP_MAX_L:
+        raise ValueError("intensity_map: dst has shape (L,) with 2 <= L <= %d, got %s" % (INTENSITY_MAP_MAX_L, tuple(dst.shape)))
+    nl = int(dst.shape[0])
+    if tuple(src.shape) != tuple(x.shape[:-3]) + (nl,):
+        raise ValueError("intensity_map: src has shape %s for x %s and L = %d, got %s" % (tuple(x.shape[:-3]) + (nl,), tuple(x.shape), nl, tuple(src.shape)))
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.shape == x.shape and out.device == x.device and out.is_contiguous()):
+        raise ValueError("intensity_map: out is a contiguous float32 tensor of x's shape on x's device")
+    check(lib.vs_intensity_map(x.data_ptr(), src.data_ptr(), dst.data_ptr(), nl, int(extrapolate == "clamp"), out.data_ptr(), planes, d, h, w, _stream()),
+          "intensity_map")
+    return out
+
+
 def instnorm_stats(x):
     n, c = x.shape[0], x.shape[-1]
     st = _new_stats(n, c, x.device)
