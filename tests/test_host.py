@@ -431,3 +431,64 @@ def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path):
     assert all(np.array_equal(a[k], b[k]) for k in a)
     r = a["recon"]
     assert r.ndim == 1 and n // 4 < r.size < n and np.all(np.diff(r) > 0) and np.array_equal(r, np.round(r)) and r[-1] < n
+
+
+VOLUME_NAMES = (
+    "cc_max_components", "cc_label", "keep_largest",
+    "SURFACE_RECORD_FIELDS", "surface", "edt", "surface_distances",
+    "MORPH_OPS", "morph", "binary_dilation", "binary_erosion", "binary_opening", "binary_closing", "fill_holes",
+    "REGION_COLUMNS", "CONTINGENCY_MAX_CELLS", "region_props", "contingency",
+    "HISTOGRAM_MAX_BINS", "HISTOGRAM_MAX_CELLS", "MI_MAX_RADIUS", "MI_MAX_PLANES", "histogram", "joint_histogram", "mutual_information",
+    "SW_BLENDS", "SW_GAUSSIAN_FLOOR", "sw_plan_host", "sw_plan", "sw_weights", "sw_flips", "sw_gather", "sw_accumulate", "sw_finalize",
+    "UNCROP_INTERPS", "uncrop",
+    "SCAN_DTYPES", "scan_orient", "to_native",
+    "AUG_MAX_SIGMA", "AUG_OPS", "aug_stats", "philox_normal", "gaussian_weights", "blur_tile", "gaussian_blur3d", "aug_flip", "aug_stage",
+    "ZOOM_EDGE_ORDERS", "ZOOM_EDGE_MAX_LEN", "zoom_edge_bundle", "zoom_edge", "simulate_lowres",
+    "QUANTILE_MAX_Q", "QUANTILE_WG_VOXELS", "INTENSITY_MAP_MAX_L", "INTENSITY_MAP_WG_VOXELS", "INTENSITY_MAP_EXTRAPOLATE", "quantile", "intensity_map")
+
+
+def test_volume_names_reexported():
+    """the forward-only volume utilities live in volume.py; ops re-exports its public names, the very objects, and none of its private ones"""
+    from vae_segmentation_amd import ops, volume
+    assert len(VOLUME_NAMES) == len(set(VOLUME_NAMES)) == 60
+    for name in VOLUME_NAMES:
+        assert getattr(ops, name) is getattr(volume, name), name
+    assert set(volume.__all__) == set(VOLUME_NAMES)
+    assert not hasattr(ops, "_check_connectivity") and not hasattr(ops, "_rows")
+
+
+def test_volume_imports_without_ops():
+    """the data pipeline and the volume utilities load without the autograd wrappers"""
+    code = ("import sys; sys.path.insert(0, %r); import vae_segmentation_amd.volume, vae_segmentation_amd.data_gpu; "
+            "assert 'vae_segmentation_amd.ops' not in sys.modules; print('ok')" % REPO)
+    run = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    assert run.returncode == 0 and run.stdout.decode().strip().endswith("ok"), run.stdout.decode()
+
+
+def test_on_backward_end():
+    """ops._on_backward_end: nothing is queued outside a backward pass; inside one, a registry's callback is queued once and runs once, after the pass"""
+    from vae_segmentation_amd import ops
+    reg, ran, seen = {"callback": False}, [], []
+
+    def fn():
+        ran.append(1)
+
+    assert ops._on_backward_end(reg, fn) is False and reg["callback"] is False and not ran
+
+    class Twice(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            return x * 2
+
+        @staticmethod
+        def backward(ctx, g):
+            seen.append((ops._on_backward_end(reg, fn), ops._on_backward_end(reg, fn), reg["callback"], len(ran)))
+            return g * 2
+
+    x = torch.ones(3, requires_grad=True)
+    y = Twice.apply(x).sum()
+    assert not seen and not ran
+    y.backward()
+    assert seen == [(True, True, True, 0)]                   # queued by the first call alone, and not run before backward() returned
+    assert ran == [1] and reg["callback"] is True            # run once, after the pass; clearing the mark is the callback's own business
+    assert torch.equal(x.grad, torch.full((3,), 2.0))

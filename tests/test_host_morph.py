@@ -155,10 +155,10 @@ def _three_class_case(shape=(10, 14, 14)):
 
 
 def test_postprocess_bookkeeping(monkeypatch):
-    from vae_segmentation_amd import evaluation
+    from vae_segmentation_amd import evaluation, volume
     fake = _CpuOps()
     for name in ("binary_closing", "fill_holes", "keep_largest"):
-        monkeypatch.setattr(evaluation.ops, name, getattr(fake, name))
+        monkeypatch.setattr(volume, name, getattr(fake, name))
     hot = _three_class_case()
     x = torch.from_numpy(hot)
     # the no-op configuration is the driver's keep_largest call and nothing else

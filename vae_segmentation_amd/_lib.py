@@ -11,7 +11,7 @@ import re
 # PyTorch-ROCm ships its own libamdhip64.so; libvaeseg.so links against the same SONAME.  torch must be loaded FIRST so
 # that the single HIP runtime in the process is torch's (the one that owns the device context and the streams we are
 # handed): loading libvaeseg.so first pulls /opt/rocm's copy instead and torch then fails with hipErrorNoDevice (100).
-import torch  # noqa: F401  (load order matters)
+import torch  # load order matters
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vaeseg.h")
@@ -118,3 +118,23 @@ def check(code, what=""):
     if code != 0:
         msg = lib.vs_strerror(code)
         raise VaesegError("libvaeseg %s failed (%d): %s" % (what, code, msg.decode() if msg else "?"))
+
+
+# what every wrapper of a launch needs (ops.py, volume.py)
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _require_cuda(*ts):
+    for t in ts:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("vae_segmentation_amd runs on the GPU only (libvaeseg HIP kernels); "
+                               "got a CPU tensor — there is no CPU fallback")
+
+
+def _contig(t):
+    return t if t.is_contiguous() else t.contiguous()

@@ -21,6 +21,7 @@ import ctypes
 import numpy as np
 import torch
 
+from . import volume
 from ._lib import check, lib
 
 
@@ -177,13 +178,12 @@ def preprocess_scan(raw, affine_diag, label=None, label_affine_diag=None, trunca
     -> {"image": (D1, H1, W1) fp32, "label": fp32 or None, "geometry": the image's ScanGeometry}, on the device.
     truncate=True applies the astype(int16) / astype(int8) truncation towards zero that img.npy / label.npy / merge.npy store; the tensors stay float32
     and hold those integers (values inside the integer types' range, which CT intensities and labels are)."""
-    from . import ops
     geometry = ScanGeometry(tuple(raw.shape), affine_diag)
-    image = resize(ops.scan_orient(raw, geometry), geometry.shape_1mm)
+    image = resize(volume.scan_orient(raw, geometry), geometry.shape_1mm)
     lab = None
     if label is not None:
         lgeo = ScanGeometry(tuple(label.shape), affine_diag if label_affine_diag is None else label_affine_diag)
-        lab = resize(ops.scan_orient(label, lgeo), geometry.shape_1mm, order=0, anti_aliasing=False)
+        lab = resize(volume.scan_orient(label, lgeo), geometry.shape_1mm, order=0, anti_aliasing=False)
     if truncate:
         image = image.trunc_()
         lab = None if lab is None else lab.trunc_()
@@ -449,21 +449,20 @@ class IntensityStandardizer(BaseTransform):
     standardises in a data dict (the BaseTransform convention).  DESIGN 3.18 holds the two rules."""
 
     def __init__(self, percentiles=(0.5, 99.5), target=(-200.0, 400.0), above=None, extrapolate="linear", fields="venous"):
-        from .ops import INTENSITY_MAP_EXTRAPOLATE, INTENSITY_MAP_MAX_L
         super().__init__(fields)
         try:
             ps, tg = tuple(float(p) for p in percentiles), tuple(float(t) for t in target)
         except (TypeError, ValueError):
             raise ValueError("IntensityStandardizer: percentiles and target are sequences of numbers, got %r and %r" % (percentiles, target)) from None
-        if not 2 <= len(ps) <= INTENSITY_MAP_MAX_L:
-            raise ValueError("IntensityStandardizer: 2 to %d percentiles, got %d" % (INTENSITY_MAP_MAX_L, len(ps)))
+        if not 2 <= len(ps) <= volume.INTENSITY_MAP_MAX_L:
+            raise ValueError("IntensityStandardizer: 2 to %d percentiles, got %d" % (volume.INTENSITY_MAP_MAX_L, len(ps)))
         if not all(np.isfinite(p) and 0.0 <= p <= 100.0 for p in ps) or any(b <= a for a, b in zip(ps, ps[1:])):
             raise ValueError("IntensityStandardizer: percentiles are strictly ascending in [0, 100], got %r" % (ps,))
         if len(tg) != 2 or not all(np.isfinite(t) for t in tg) or not tg[0] < tg[1]:
             raise ValueError("IntensityStandardizer: target is an ascending pair of finite numbers, got %r" % (tg,))
         if above is not None and not np.isfinite(float(above)):
             raise ValueError("IntensityStandardizer: above is a finite number or None, got %r" % (above,))
-        if extrapolate not in INTENSITY_MAP_EXTRAPOLATE:
+        if extrapolate not in volume.INTENSITY_MAP_EXTRAPOLATE:
             raise ValueError("IntensityStandardizer: extrapolate is 'linear' or 'clamp', got %r" % (extrapolate,))
         self.percentiles, self.target, self.extrapolate = ps, tg, extrapolate
         self.above = None if above is None else float(above)
@@ -472,8 +471,7 @@ class IntensityStandardizer(BaseTransform):
 
     def landmarks(self, x, mask=None):
         """the percentiles of every (D, H, W) plane of x -> fp64 (..., L) on the device (NaN rows where nothing is selected)"""
-        from . import ops
-        return ops.quantile(x, self.percentiles, above=self.above, mask=mask)["q"]
+        return volume.quantile(x, self.percentiles, above=self.above, mask=mask)["q"]
 
     def fit(self, volumes, masks=None):
         """The standard scale from training scans (Nyul and Udupa): the landmarks s of each scan mapped affinely so that s[0] -> target[0] and
@@ -507,9 +505,8 @@ class IntensityStandardizer(BaseTransform):
 
     def transform(self, x, mask=None):
         """x float32 (..., D, H, W) on the device -> its standardised copy; ten launches, nothing synchronised or read back"""
-        from . import ops
         dst = self._scale_on(x.device)
-        return ops.intensity_map(x, self.landmarks(x, mask), dst, extrapolate=self.extrapolate)
+        return volume.intensity_map(x, self.landmarks(x, mask), dst, extrapolate=self.extrapolate)
 
     def state_dict(self):
         return {"percentiles": tuple(self.percentiles), "target": tuple(self.target), "above": self.above, "extrapolate": self.extrapolate,
@@ -583,19 +580,17 @@ def _plane_ops(ops_list, channels, c, shape):
         elif name == "blur":
             sigma = _per_channel(args[0], channels, "blur sigma")[c]
             if sigma is not None:
-                from . import ops
-                ops.gaussian_weights(sigma)                                   # the range check, before anything is launched
+                volume.gaussian_weights(sigma)                                # the range check, before anything is launched
                 out.append(("blur", float(sigma)))
         elif name == "lowres":
             zoom = _per_channel(args[0], channels, "lowres zoom")[c]
             order_down, order_up = (int(args[1]) if len(args) > 1 else 0), (int(args[2]) if len(args) > 2 else 3)
-            from . import ops
-            if order_down not in ops.ZOOM_EDGE_ORDERS or order_up not in ops.ZOOM_EDGE_ORDERS:
+            if order_down not in volume.ZOOM_EDGE_ORDERS or order_up not in volume.ZOOM_EDGE_ORDERS:
                 raise ValueError("intensity_augment: lowres orders are 0, 1 or 3, got %r" % ((order_down, order_up),))
             if zoom is not None:
                 target = lowres_target_shape(shape, zoom, args[3] if len(args) > 3 else ())      # the range check, before anything is launched
-                if 3 in (order_down, order_up) and max(shape + target) > ops.ZOOM_EDGE_MAX_LEN:
-                    raise ValueError("intensity_augment: lowres with order 3 takes axes of at most %d voxels, got %s" % (ops.ZOOM_EDGE_MAX_LEN, shape))
+                if 3 in (order_down, order_up) and max(shape + target) > volume.ZOOM_EDGE_MAX_LEN:
+                    raise ValueError("intensity_augment: lowres with order 3 takes axes of at most %d voxels, got %s" % (volume.ZOOM_EDGE_MAX_LEN, shape))
                 out.append(("lowres", target, order_down, order_up))
         elif name == "brightness":
             m = _per_channel(args[0], channels, "brightness m")[c]
@@ -632,20 +627,19 @@ def _augment_plane(x, plane_ops, channel):
         contrast | power | restat  [flip]      the op is driven by the record of the stage's input, so nothing may precede it in its stage
     A stage whose successor needs statistics writes the record of what it stores; after a blur or a lowres (stages of their own), or at the start,
     ops.aug_stats makes the same record."""
-    from . import ops
     cur, rec, rec_power_in, k, n = x, None, None, 0, len(plane_ops)
     while k < n:
         name = plane_ops[k][0]
         if name == "blur":
-            cur, rec, k = ops.gaussian_blur3d(cur, plane_ops[k][1]), None, k + 1
+            cur, rec, k = volume.gaussian_blur3d(cur, plane_ops[k][1]), None, k + 1
             continue
         if name == "lowres":
-            cur, rec, k = ops.simulate_lowres(cur, *plane_ops[k][1:]), None, k + 1
+            cur, rec, k = volume.simulate_lowres(cur, *plane_ops[k][1:]), None, k + 1
             continue
         st = {}
         if name in _STAT_OPS:
             if rec is None:
-                rec = ops.aug_stats(cur)
+                rec = volume.aug_stats(cur)
             op = plane_ops[k]
             if name == "contrast":
                 st.update(op="contrast", p=op[1], flag=op[2], rec=rec)
@@ -670,7 +664,7 @@ def _augment_plane(x, plane_ops, channel):
         if "flip" not in st and k < n and plane_ops[k][0] == "flip":
             st.update(flip=plane_ops[k][1], flip_first=False)
             k += 1
-        cur, rec = ops.aug_stage(cur, want_rec=k < n and plane_ops[k][0] in _STAT_OPS, **st)
+        cur, rec = volume.aug_stage(cur, want_rec=k < n and plane_ops[k][0] in _STAT_OPS, **st)
     return cur
 
 
@@ -718,20 +712,19 @@ class IntensityAugment:
                  p_blur_per_channel=0.5, p_brightness=0.15, brightness=(0.75, 1.25), p_contrast=0.15, contrast=(0.75, 1.25), preserve_range=True,
                  p_gamma_inverted=0.1, p_gamma=0.3, gamma=(0.7, 1.5), retain_stats=True, p_mirror=0.5, p_lowres=0.0, lowres_zoom=(0.5, 1.0),
                  p_lowres_per_channel=0.5, lowres_orders=(0, 3), lowres_ignore_axes=()):
-        from .ops import AUG_MAX_SIGMA, ZOOM_EDGE_ORDERS
         if noise not in (None, "numpy", "philox"):
             raise ValueError("IntensityAugment: noise is None, 'numpy' or 'philox', got %r" % (noise,))
         if p_noise > 0 and noise is None:
             raise NotImplementedError("IntensityAugment: Gaussian noise needs a noise source: choose noise='numpy' (the normals are drawn from rng) or "
                                       "noise='philox' (made on the device from seed), or pass p_noise=0")
-        if not 0 < blur_sigma[0] <= blur_sigma[1] <= AUG_MAX_SIGMA:
-            raise ValueError("IntensityAugment: blur takes 0 < sigma[0] <= sigma[1] <= %g, got %r" % (AUG_MAX_SIGMA, blur_sigma))
+        if not 0 < blur_sigma[0] <= blur_sigma[1] <= volume.AUG_MAX_SIGMA:
+            raise ValueError("IntensityAugment: blur takes 0 < sigma[0] <= sigma[1] <= %g, got %r" % (volume.AUG_MAX_SIGMA, blur_sigma))
         for name, (lo, hi) in (("noise_s", noise_s), ("brightness", brightness), ("contrast", contrast), ("gamma", gamma)):
             if not (np.isfinite(lo) and np.isfinite(hi) and 0 <= lo <= hi):
                 raise ValueError("IntensityAugment: %s is a range 0 <= lo <= hi, got %r" % (name, (lo, hi)))
         if not (len(lowres_zoom) == 2 and 0 < lowres_zoom[0] <= lowres_zoom[1] <= 1):
             raise ValueError("IntensityAugment: lowres_zoom is a range 0 < lo <= hi <= 1, got %r" % (lowres_zoom,))
-        if len(lowres_orders) != 2 or any(o not in ZOOM_EDGE_ORDERS for o in lowres_orders):
+        if len(lowres_orders) != 2 or any(o not in volume.ZOOM_EDGE_ORDERS for o in lowres_orders):
             raise ValueError("IntensityAugment: lowres_orders are (down, up), each 0, 1 or 3, got %r" % (lowres_orders,))
         if any(a not in (0, 1, 2) for a in lowres_ignore_axes):
             raise ValueError("IntensityAugment: lowres_ignore_axes index the axes (0, 1, 2) of a plane, got %r" % (lowres_ignore_axes,))
@@ -779,7 +772,6 @@ class IntensityAugment:
         return ops_list
 
     def __call__(self, data_dict, params=None):
-        from . import ops
         data, seg = data_dict.get(self.data_key), data_dict.get(self.label_key)
         out_d, out_s = [], []
         for b in range(data.shape[0]):
@@ -790,7 +782,7 @@ class IntensityAugment:
                 for op in ops_list:
                     if op[0] == "flip":
                         mask ^= int(op[1])                   # mirrors compose by exclusive or
-                out_s.append(ops.aug_flip(seg[b].contiguous(), mask) if mask else seg[b])
+                out_s.append(volume.aug_flip(seg[b].contiguous(), mask) if mask else seg[b])
         data_dict[self.data_key] = out_d[0][None] if len(out_d) == 1 else torch.stack(out_d)
         if seg is not None:
             data_dict[self.label_key] = out_s[0][None] if len(out_s) == 1 else torch.stack(out_s)

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ddp, ops, optim
+from . import ddp, ops, optim, volume
 from . import train as T
 from .evaluation import EPS_EVALUATION, EPS_MAIN_SOURCE, avg_dsc
 from .modules import Embed, Encoder, Fusion, Joint, Joint2, Segmentation, VAE, set_kernel_dtype
@@ -293,9 +293,9 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
         if surface:
             hard = ops.hard_onehot(pred)
             if filtered is not None:
-                surf_raw[i] = ops.surface_distances(hard[:, lo:], gt[:, lo:])
+                surf_raw[i] = volume.surface_distances(hard[:, lo:], gt[:, lo:])
                 hard = filtered
-            surf[i] = ops.surface_distances(hard[:, lo:], gt[:, lo:])
+            surf[i] = volume.surface_distances(hard[:, lo:], gt[:, lo:])
         if lesion and method != "discriminator_train":
             from .evaluation import confusion, lesion_metrics
             hard = filtered if filtered is not None else ops.hard_onehot(pred)
@@ -307,7 +307,7 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
             image = batch[IMG_KEY].cuda(non_blocking=True).float()[:, :1].contiguous()
             sides = {}
             for name, hot in (("pred", hard), ("label", gt)):
-                rec = ops.histogram(image, int(intensity), range=INTENSITY_RANGE, labels=hot.argmax(1, keepdim=True).to(torch.int32), rows=nc - 1)
+                rec = volume.histogram(image, int(intensity), range=INTENSITY_RANGE, labels=hot.argmax(1, keepdim=True).to(torch.int32), rows=nc - 1)
                 sides[name] = (rec["table"][:, 0, lo:], rec["outside"][:, 0], hot[:, lo:].sum((2, 3, 4)))
             nmi = torch.stack([mutual_information_3d(pred[:, k], gt[:, k]) for k in range(lo, nc)])
             inten[i] = (sides, nmi)
@@ -539,7 +539,7 @@ def check_intensity_flags(a, script="main_source.py"):
     bins = getattr(a, "val_intensity", 0)
     if not bins:
         return
-    need(1 <= bins <= ops.HISTOGRAM_MAX_BINS, "--val_intensity is a number of bins between 1 and %d" % ops.HISTOGRAM_MAX_BINS)
+    need(1 <= bins <= volume.HISTOGRAM_MAX_BINS, "--val_intensity is a number of bins between 1 and %d" % volume.HISTOGRAM_MAX_BINS)
     need(a.method != "discriminator_train", "--val_intensity reads the image inside a segmentation, --method discriminator_train predicts none")
     need(not getattr(a, "val_finetune", 0), "--val_intensity rides on the plain validation pass: it cannot be combined with --val_finetune")
 

@@ -5,6 +5,7 @@ utils/evaluation.py uses 1e-6, main_source.py's own copy 1e-4."""
 import torch
 
 from . import ops
+from . import volume as V       # not `volume`: histogram, SlidingWindow.__call__ and sliding_window_predict take a parameter of that name
 
 EPS_EVALUATION = 1e-6
 EPS_MAIN_SOURCE = 1e-4
@@ -69,7 +70,7 @@ def avg_dsc(data_dict, source_key='align_lung', target_key='source_lung', binary
 def keep_largest_components(A, k=1, min_size=0, connectivity=26):
     """utils/utils.py:776-796 (predict_vol step 2) on the device: per (n, c) plane of a planar (N, C, D, H, W) mask, binarize (>= 0.5), keep the k largest
     connected components that hold at least min_size voxels, re-binarise.  predict_vol itself hard-codes k=2, min_size=10000, full connectivity."""
-    return ops.keep_largest(A, k=k, min_size=min_size, connectivity=connectivity)
+    return V.keep_largest(A, k=k, min_size=min_size, connectivity=connectivity)
 
 
 def check_connection(tumor_index, image):
@@ -81,7 +82,7 @@ def check_connection(tumor_index, image):
     shape = tuple(np.shape(image))
     mask = np.zeros(shape, dtype=np.float32)
     mask[idx[:, 0], idx[:, 1], idx[:, 2]] = 1
-    labels, _, _ = ops.cc_label(torch.from_numpy(mask).cuda().view((1, 1) + shape), connectivity=26)
+    labels, _, _ = V.cc_label(torch.from_numpy(mask).cuda().view((1, 1) + shape), connectivity=26)
     cc = labels.view(shape).cpu().numpy()[idx[:, 0], idx[:, 1], idx[:, 2]]
     # the device numbers components by their first voxel in raster order; the reference by their first appearance in tumor_index
     _, first = np.unique(cc, return_index=True)
@@ -107,7 +108,7 @@ def surface_metrics(A, B, spacing=None, connectivity=6):
     either surface is empty gives NaN where medpy raises."""
     a, single = _planar(A)
     b, _ = _planar(B)
-    rec = ops.surface_distances(a.detach(), b.detach(), spacing=spacing, connectivity=connectivity)
+    rec = V.surface_distances(a.detach(), b.detach(), spacing=spacing, connectivity=connectivity)
     return {k: v.reshape(()) for k, v in rec.items()} if single else rec
 
 
@@ -148,8 +149,8 @@ def _spacing3(spacing, what):
 
 def _components(X, connectivity, what):
     """(labels int32, sizes int32 (N, C, maxk)) of the binarised mask's components"""
-    ops._check_connectivity(connectivity, what)
-    labels, _, sizes = ops.cc_label(X.detach(), connectivity=connectivity)
+    V._check_connectivity(connectivity, what)
+    labels, _, sizes = V.cc_label(X.detach(), connectivity=connectivity)
     return labels, sizes
 
 
@@ -160,11 +161,11 @@ def region_props(mask, spacing=None, connectivity=26, max_components=4096):
     "volume" fp64 = count x sz x sy x sx (voxels without a spacing), "n_components" int32 and "labels" int32, the label volume.  With
     spacing = (sz, sy, sx) the centroid is in the spacing's unit (index x spacing), otherwise in voxels; NaN for a component that does not exist."""
     sp = _spacing3(spacing, "region_props")
-    ops._rows(max_components, "region_props: max_components", 1)
+    V._rows(max_components, "region_props: max_components", 1)
     x, single = _planar(mask)
-    ops._check_connectivity(connectivity, "region_props")
-    labels, counts, _ = ops.cc_label(x.detach(), connectivity=connectivity)
-    out = ops.region_props(labels, max_components=max_components)
+    V._check_connectivity(connectivity, "region_props")
+    labels, counts, _ = V.cc_label(x.detach(), connectivity=connectivity)
+    out = V.region_props(labels, max_components=max_components)
     unit = 1.0
     if sp is not None:
         out["centroid"] = out["centroid"] * torch.tensor(sp, dtype=torch.float64, device=labels.device)
@@ -197,10 +198,10 @@ def confusion(pred_label, gt_label, n_class):
     With tp = table[k, k], p = the row sum (predicted k) and g = the column sum (labelled k): dice = 2 tp / (p + g), iou = tp / (p + g - tp),
     sensitivity = tp / g, precision = tp / p.  A class that is empty on both sides scores 1.0 everywhere; sensitivity of a class nobody labelled but
     somebody predicted — and precision the other way round — is 0.0."""
-    k = ops._rows(n_class, "confusion: n_class", 1)
+    k = V._rows(n_class, "confusion: n_class", 1)
     a, single = _label_map(pred_label, "confusion")
     b, _ = _label_map(gt_label, "confusion")
-    table, overflow = ops.contingency(a, b, k - 1, k - 1)
+    table, overflow = V.contingency(a, b, k - 1, k - 1)
     tp = torch.diagonal(table, dim1=-2, dim2=-1)
     p, g = table.sum(-1), table.sum(-2)
     out = {"table": table, "dice": _ratio(2 * tp, p + g, p + g), "iou": _ratio(tp, p + g - tp, p + g), "sensitivity": _ratio(tp, g, p),
@@ -217,10 +218,10 @@ def lesion_metrics(pred, gt, connectivity=26, min_overlap=1, min_size=0, max_com
     fn = n_gt - tp, fp — int64; sensitivity = tp / n_gt, precision = (n_pred - fp) / n_pred, f1 = 2 tp / (2 tp + fp + fn) — fp64, a ratio with
     denominator 0 being 1.0 when the other side is empty too and 0.0 otherwise; overflow — int32, voxels of components numbered above
     min(max_components, 2047), the most the table holds per side: the record is then not valid, and lesion_record_to_host raises."""
-    ops._check_connectivity(connectivity, "lesion_metrics")
-    ops._rows(max_components, "lesion_metrics: max_components", 1)
-    ops._rows(min_overlap, "lesion_metrics: min_overlap", 1)
-    ops._rows(min_size, "lesion_metrics: min_size", 0)
+    V._check_connectivity(connectivity, "lesion_metrics")
+    V._rows(max_components, "lesion_metrics: max_components", 1)
+    V._rows(min_overlap, "lesion_metrics: min_overlap", 1)
+    V._rows(min_size, "lesion_metrics: min_size", 0)
     a, single = _planar(pred)
     b, _ = _planar(gt)
     if a.shape != b.shape:
@@ -228,7 +229,7 @@ def lesion_metrics(pred, gt, connectivity=26, min_overlap=1, min_size=0, max_com
     P, sizes_p = _components(a, connectivity, "lesion_metrics")
     G, sizes_g = _components(b, connectivity, "lesion_metrics")
     rows = min(max_components, LESION_TABLE_ROWS, sizes_p.shape[-1])
-    table, overflow = ops.contingency(P, G, rows, rows)
+    table, overflow = V.contingency(P, G, rows, rows)
     least = max(min_size, 1)
     keep_p, keep_g = sizes_p[..., :rows] >= least, sizes_g[..., :rows] >= least            # a dropped component: its row / column is not looked at
     shared = table[..., 1:, 1:] * (keep_p.unsqueeze(-1) & keep_g.unsqueeze(-2))
@@ -277,7 +278,7 @@ def histogram(volume, bins, range=None, mask=None):
         if m.shape != x.shape:
             raise ValueError("histogram: the mask's shape %s is not the volume's %s" % (tuple(mask.shape), tuple(volume.shape)))
         lab = (m.detach() >= 0.5).to(torch.int32).contiguous()
-    rec = ops.histogram(x, bins, range=range, labels=lab, rows=0 if lab is None else 1)
+    rec = V.histogram(x, bins, range=range, labels=lab, rows=0 if lab is None else 1)
     out = {"table": rec["table"][:, :, -1], "edges": rec["edges"], "outside": rec["outside"]}
     if lab is not None:
         out["complement"] = rec["table"][:, :, 0]
@@ -292,7 +293,7 @@ def joint_histogram(a, b, bins=256, range=None):
     y, _ = _intensities(b, "joint_histogram")
     if x.shape != y.shape:
         raise ValueError("joint_histogram: the two volumes differ in shape: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
-    rec = ops.joint_histogram(x, y, bins=bins, range=range)
+    rec = V.joint_histogram(x, y, bins=bins, range=range)
     return {k: v[0, 0] for k, v in rec.items()} if single else rec
 
 
@@ -308,8 +309,8 @@ def mutual_information_3d(x, y, sigma=1, normalized=True):
         raise ValueError("mutual_information_3d: x and y have one non-empty shape, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
     a, _ = _intensities(x.reshape(1, 1, 1, 1, -1), "mutual_information_3d")
     b, _ = _intensities(y.reshape(1, 1, 1, 1, -1), "mutual_information_3d")
-    rec = ops.joint_histogram(a, b, bins=(256, 256), range=None)
-    return ops.mutual_information(rec["table"], sigma=sigma, normalized=normalized)[0, 0]
+    rec = V.joint_histogram(a, b, bins=(256, 256), range=None)
+    return V.mutual_information(rec["table"], sigma=sigma, normalized=normalized)[0, 0]
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -317,7 +318,7 @@ def mutual_information_3d(x, y, sigma=1, normalized=True):
 # ----------------------------------------------------------------------------------------------------
 def _morph(name, X, **kw):
     x, single = _planar(X)
-    out = getattr(ops, name)(x.detach(), **kw)
+    out = getattr(V, name)(x.detach(), **kw)
     return out[0, 0] if single else out
 
 
@@ -375,9 +376,9 @@ def postprocess(hard, closing=0, fill_holes=False, keep_largest=0, min_size=0, l
             cur = (x[:, c:c + 1] >= 0.5).float()
             new = cur
             if closing > 0:
-                new = ops.binary_closing(new, iterations=int(closing), connectivity=26, border_value=0)
+                new = V.binary_closing(new, iterations=int(closing), connectivity=26, border_value=0)
             if fill_holes:
-                new = ops.fill_holes(new, connectivity=6)
+                new = V.fill_holes(new, connectivity=6)
             if lo < 1:                                           # no background channel to trade with
                 x[:, c:c + 1] = new
                 continue
@@ -386,7 +387,7 @@ def postprocess(hard, closing=0, fill_holes=False, keep_largest=0, min_size=0, l
             x[:, c:c + 1] = cur + gain - lose
             x[:, 0:1] += lose - gain
     if keep_largest > 0:
-        x = ops.keep_largest(x, k=int(keep_largest), min_size=int(min_size), connectivity=26, lo_channel=lo, to_background=True)
+        x = V.keep_largest(x, k=int(keep_largest), min_size=int(min_size), connectivity=26, lo_channel=lo, to_background=True)
     return x
 
 
@@ -408,7 +409,7 @@ def tta_flips(axes):
             raise ValueError("tta: the axes are distinct letters of \"dhw\", got %r" % (axes,))
         mask = sum(TTA_AXES[a] for a in axes)
         return tuple(c for c in range(8) if c & ~mask == 0)
-    ops.sw_flips(axes)
+    V.sw_flips(axes)
     return tuple(int(c) for c in axes)
 
 
@@ -434,8 +435,8 @@ class SlidingWindow:
             raise ValueError("SlidingWindow: shape is (C, D, H, W) or (D, H, W) and batch >= 1, got %r, %r" % (shape, batch))
         self.model_fn, self.shape, self.patch, self.batch, self.cval = model_fn, shape, int(patch), int(batch), float(cval)
         self.device = torch.device(device)
-        self.origins, self.nw = ops.sw_plan(shape[1:], self.patch, overlap, device=self.device)
-        self.weights = ops.sw_weights(self.patch, blend, device=self.device)
+        self.origins, self.nw = V.sw_plan(shape[1:], self.patch, overlap, device=self.device)
+        self.weights = V.sw_weights(self.patch, blend, device=self.device)
         self.tta = tta_flips(tta)
         self.n_items = self.nw * (len(self.tta) if self.tta else 1)
         self.n_batches = (self.n_items + self.batch - 1) // self.batch
@@ -446,7 +447,7 @@ class SlidingWindow:
         self.use_graph, self.graph = bool(graph), None
 
     def _one_batch(self):
-        ops.sw_gather(self.volume, self.origins, self.first, self.batch, cval=self.cval, out=self.windows, flips=self.tta)
+        V.sw_gather(self.volume, self.origins, self.first, self.batch, cval=self.cval, out=self.windows, flips=self.tta)
         prob = self.model_fn(self.windows)
         if prob.dim() != 5 or prob.shape[0] != self.batch or tuple(prob.shape[2:]) != (self.patch,) * 3:
             raise ValueError("sliding window: model_fn must return (B, K, P, P, P) = (%d, K, %d, %d, %d), got %s"
@@ -456,7 +457,7 @@ class SlidingWindow:
                 raise RuntimeError("sliding window: the accumulators must exist before a capture starts")
             self.acc = torch.zeros((prob.shape[1],) + self.shape[1:], dtype=torch.float32, device=self.device)
             self.wsum = torch.zeros(self.shape[1:], dtype=torch.float32, device=self.device)
-        ops.sw_accumulate(prob, self.acc, self.wsum, self.origins, self.first, self.weights, flips=self.tta)
+        V.sw_accumulate(prob, self.acc, self.wsum, self.origins, self.first, self.weights, flips=self.tta)
         self.first.add_(self.batch)
 
     def _reset(self):
@@ -496,7 +497,7 @@ class SlidingWindow:
                     self.graph.replay()
                 else:
                     self._one_batch()
-            prob, label, hot = ops.sw_finalize(self.acc, self.wsum, label=True, onehot=onehot)
+            prob, label, hot = V.sw_finalize(self.acc, self.wsum, label=True, onehot=onehot)
         out = {"prob": prob, "label": label, "wsum": self.wsum.clone(), "tta": self.tta}
         if onehot:
             out["onehot"] = hot
@@ -542,7 +543,7 @@ def localise(prob_or_label, keep_largest=1, min_size=0, lo_channel=1):
         raise ValueError("localise: expected probabilities (K, D, H, W) or a label map (D, H, W), got shape %s" % (tuple(x.shape),))
     lo = min(int(lo_channel), hard.shape[1] - 1)
     if keep_largest > 0:
-        hard = ops.keep_largest(hard, k=int(keep_largest), min_size=int(min_size), connectivity=26, lo_channel=lo)
+        hard = V.keep_largest(hard, k=int(keep_largest), min_size=int(min_size), connectivity=26, lo_channel=lo)
     return hard[0, lo:].amax(0).contiguous()
 
 
@@ -604,7 +605,7 @@ def coarse_to_fine_predict(seg, image, patch, overlap=0.5, blend="gaussian", bat
         fine = model_fn(crop[_FIELD][None, None])[0]
     else:
         fine = sliding_window_predict(model_fn, crop[_FIELD], patch, overlap=0.0, blend="constant", batch=batch, tta=tta)["prob"]
-    pasted = ops.uncrop(fine, geometry, tuple(img.shape), interp=interp, want_prob=want_prob)
+    pasted = V.uncrop(fine, geometry, tuple(img.shape), interp=interp, want_prob=want_prob)
     res = {"label": pasted["label"], "coarse_label": coarse["label"], "geometry": geometry, "found": True}
     if want_prob:
         res["prob"] = pasted["prob"]
@@ -626,7 +627,7 @@ def predict_scan(seg, raw, affine_diag, patch, overlap=0.5, blend="gaussian", ba
     pre = data_gpu.preprocess_scan(raw, affine_diag)
     res = coarse_to_fine_predict(seg, pre["image"], patch, overlap=overlap, blend=blend, batch=batch, keep_largest=keep_largest, min_size=min_size,
                                  interp=interp, graph=graph, tta=tta, want_prob=True, standardize=standardize)
-    label = ops.to_native(res["prob"], pre["geometry"], interp=native_interp)["label"]
+    label = V.to_native(res["prob"], pre["geometry"], interp=native_interp)["label"]
     if not details:
         return label
     return {"label": label, "label_1mm": res["label"], "coarse_label": res["coarse_label"], "geometry": pre["geometry"], "crop_geometry": res["geometry"],
