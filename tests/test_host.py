@@ -55,6 +55,59 @@ def test_argument_validation_without_gpu():
     assert lib.vs_conv_gather_fwd(fake, None, fake, None, fake, None, 1, 4, 4, 4, 24, 8, 0, 1, 1e-5, None) == -2             # channel count not 8 / 16 / 32k
     assert lib.vs_conv_gather_fwd(fake + 4, None, fake, None, fake, None, 1, 4, 4, 4, 8, 8, 0, 1, 1e-5, None) == -5          # VS_EALIGN
     assert lib.vs_conv_gather_fwd(fake, None, fake, None, fake, None, 0, 4, 4, 4, 8, 8, 0, 1, 1e-5, None) == -2              # empty batch
+    # every launcher of csrc/conv_api.hip refuses on the host, with the code of the FIRST check that fails (-1 EINVAL, -2 ESHAPE, -3 EDTYPE, -5 EALIGN);
+    # none of these argument lists is one a launcher accepts
+    ea = lib.vs_conv_k3_bwd_data_applied                   # (x, w, y, mask_x, mask_stats, sums, sync, fault, n, d, h, w, c, m, dtype, eps, stream)
+    assert ea(fake, fake, fake, None, fake, fake, fake, fake, 2, 24, 24, 24, 32, 32, 1, 1e-5, None) == -1                    # without mask
+    assert ea(fake, fake, fake, fake, fake, fake, fake + 64, fake, 2, 24, 24, 24, 32, 32, 1, 1e-5, None) == -5               # sync not 128-byte aligned
+    assert ea(fake, fake, fake, fake, fake, fake, fake, fake, 2, 24, 24, 24, 8, 8, 1, 1e-5, None) == -2                      # 8 -> 8: no epilogue-apply kernel
+    assert ea(fake, fake, fake, fake, fake, fake, fake, fake, 2, 96, 96, 96, 32, 32, 1, 1e-5, None) == -2                    # more than one resident round
+    s2 = lib.vs_conv_s2_bwd_data_applied                   # (x, w, y, mask_x, mask_stats, sums, add, sync, fault, n, d, h, w, c, m, scatter, dtype, eps, stream)
+    assert s2(fake, fake, fake, fake, fake, fake, fake + 8, fake, fake, 2, 24, 24, 24, 32, 32, 0, 1, 1e-5, None) == -5       # add misaligned
+    assert s2(fake, fake, fake, fake, fake, fake, None, fake, fake, 2, 4, 4, 4, 512, 512, 0, 1, 1e-5, None) == -2            # wider than 256 channels
+    assert s2(fake, fake, fake, fake, fake, fake, None, fake, fake, 2, 96, 96, 96, 8, 8, 1, 1, 1e-5, None) == -2             # full resolution: never resident
+    fa = lib.vs_conv_k3_bwd_data_fused_apply               # (g, act_x, act_stats, act_sums, w, y, mask_x, mask_stats, sums, dx_out, n, d, h, w, c, m, dtype, eps, stream)
+    assert fa(fake, fake, fake, fake, fake, fake, fake, fake, None, None, 2, 96, 96, 96, 8, 8, 1, 1e-5, None) == -1          # mask without sums
+    assert fa(fake, fake, None, fake, fake, fake, None, None, None, None, 2, 96, 96, 96, 8, 8, 1, 1e-5, None) == -1          # no activation statistics
+    assert fa(fake, fake, fake, fake, fake, fake, None, None, None, None, 2, 24, 24, 24, 32, 32, 1, 1e-5, None) == -2        # 32-channel chunks keep the standalone apply
+    assert fa(fake, fake, fake, fake, fake, fake, None, None, None, None, 2, 24, 24, 24, 32, 32, 0, 1e-5, None) == -2        # ... in fp32 too
+    wg = lib.vs_conv_k3_bwd_data_wgrad                     # (g, act_x, act_stats, act_sums, w, y, mask_x, mask_stats, sums, slabs, n, d, h, w, c, m, dtype, eps, stream)
+    assert wg(fake, None, None, None, fake, fake, fake, fake, fake, fake, 2, 48, 48, 48, 16, 16, 1, 1e-5, None) == -2        # 8 -> 8 only
+    assert wg(fake, fake, None, fake, fake, fake, fake, fake, fake, fake, 2, 96, 96, 96, 8, 8, 1, 1e-5, None) == -1          # act_x without its statistics
+    assert lib.vs_conv_gather_bwd_data(fake, fake, fake, fake, fake, None, 2, 24, 24, 24, 32, 32, 0, 1, 1e-5, None) == -1    # without sums
+    assert lib.vs_conv_gather_fwd(fake, None, fake, None, fake, None, 1, 4, 4, 4, 8, 12, 0, 1, 1e-5, None) == -1             # m_out not a multiple of 8
+    assert lib.vs_conv_gather_fwd(fake, None, fake, None, fake, None, 1, 4, 4, 4, 8, 8, 2, 1, 1e-5, None) == -1              # kind: neither K3 nor K2S2
+    assert lib.vs_conv_gather_fwd(fake, None, fake, None, fake, None, 1, 4, 4, 4, 8, 1024, 0, 1, 1e-5, None) == -2           # more than 512 output channels
+    assert lib.vs_conv_scatter_fwd(fake, None, fake, None, fake + 8, 1, 4, 4, 4, 8, 8, 1, 1e-5, None) == -1                  # y at +8 bytes
+    assert lib.vs_conv_scatter_bwd_data(fake, fake, fake, None, fake, fake, 1, 4, 4, 4, 8, 8, 1, 1e-5, None) == -1           # without mask
+    sb = lib.vs_conv_k3_softmax2_bwd_data                  # (prob, gprob, gprob_cl, w, y, mask_x, mask_stats, sums, slabs, bias_part, n, d, h, w, dtype, eps, drop_p, seed, stream)
+    assert sb(fake, fake, None, fake, fake, fake, fake, fake, None, fake, 1, 16, 16, 16, 1, 1e-5, 0.0, 0, None) == -1        # bias partials without slabs
+    assert sb(fake, fake, None, fake, fake, fake, fake, fake, fake, fake, 1, 16, 16, 16, 0, 1e-5, 0.0, 0, None) == -2        # fp32
+    sf = lib.vs_conv_k3_softmax2_cl_fwd                    # (x, x_stats, w, bias, prob, prob_cl, n, d, h, w, c, dtype, eps, drop_p, seed, stream)
+    assert sf(fake, None, fake, None, fake, None, 1, 16, 16, 16, 8, 1, 1e-5, 1.0, 0, None) == -1                             # drop_p 1.0
+    assert sf(fake, None, fake, None, fake, None, 1, 16, 16, 16, 16, 1, 1e-5, 0.0, 0, None) == -2                            # 16 input channels
+    assert sf(fake, None, fake, None, fake, fake, 1, 16, 16, 16, 8, 0, 1e-5, 0.0, 0, None) == -3                             # channels-last copy in fp32
+
+
+def test_conv_plan_answers_are_pinned():
+    """The conv launch planner's answers (csrc/conv_api.hip; the host queries of tools/conv_plan_table.py) over 6336 shapes under the default vs_config
+    and ten single changes of it equal tests/golden/conv_plan.npz, a table made from the build BEFORE planning was split from launching: every entry, no exceptions."""
+    import numpy as np
+    from vae_segmentation_amd._lib import lib
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    try:
+        import conv_plan_table as P
+    finally:
+        sys.path.pop(0)
+    want = np.load(os.path.join(REPO, "tests", "golden", "conv_plan.npz"), allow_pickle=False)
+    got = P.table(lib.loaded()[0])
+    assert want["answers"].shape == (len(P.CONFIGS), 6336, len(P.QUERIES))
+    assert np.array_equal(got["tuples"], want["tuples"])
+    assert got["answers"].dtype == want["answers"].dtype and (got["answers"] == want["answers"]).all()
+    # the fixture itself is the table that was recorded then: tuples answering 1 by default, tuples whose six support answers move per configuration change
+    a = want["answers"]
+    assert [int((a[0, :, j] == 1).sum()) for j in range(6)] == [1114, 906, 1075, 1380, 2223, 192]
+    assert [int((a[k, :, :6] != a[0, :, :6]).any(axis=1).sum()) for k in range(1, len(P.CONFIGS))] == [387, 14, 178, 32, 598, 502, 96, 3167, 192, 0]
 
 
 def test_grouped_weight_gradient_planning_without_gpu():

@@ -1,16 +1,21 @@
 // C-ABI launchers of the implicit-GEMM convolutions (forward / backward-data).
+// Planning is apart from launching: plan_gather / plan_scatter turn the VALUES of a launch (ConvAsk: shape, kind, dtype, which optional parts it has) into a
+// ConvPlan — geometry, tiling, the status code the shape earns, which fused forms exist for it.  A launcher plans once, adds its pointers to the plan's
+// G1Params and dispatches; a *_supported query reads the same plan.  Which kernel carries which form is asked of the dispatch units' own predicates.
 #include <stdlib.h>
 #include "igemm_dispatch.h"
 
 int g1_dispatch_k3_f32(const G1Params& p, int ck, int mt, int epi, int tiles, int row_tiles, hipStream_t s);
 int g1_dispatch_k3_bf16(const G1Params& p, int ck, int mt, int epi, int tiles, int row_tiles, hipStream_t s);
 int g1_dispatch_k3_f16(const G1Params& p, int ck, int mt, int epi, int tiles, int row_tiles, hipStream_t s);
-int g1_k3_fa_supported(const G1Params& p, int ck, int mt);
-int k3tw_slab_count(int n, int d, int h, int w);
-int k3x_ea_capacity(int n, int c, int m);            // igemm_k3x.hip: the same for the parity mode's k3x_kernel<8, 16, .., EA>
-int k3b_ea_capacity(int n, int c, int m);            // igemm_k3_bf16.hip: workgroups of a k3b_kernel<.., EA> launch that are certainly resident together
-int k2s2_scatter8_launch(const G1Params& p, int dtype, hipStream_t stream);      // k2s2_scatter8.hip        // igemm_k3_bf16.hip: workgroups (= slabs) of a k3tw_kernel launch
 int g1_dispatch_k3_x3(const G1Params& p, int ck, int mt, int epi, int tiles, int row_tiles, hipStream_t s);
+// is there a fused-apply (FA) / epilogue-apply (EA, with fused sums and without FA) kernel for an already tiled 3x3x3 backward-data launch of wgs workgroups?
+int g1_k3_fa_supported(const G1Params& p, int ck, int mt, int lazy_in);                // igemm_k3_bf16.hip: the same for both 16-bit storage types
+int g1_k3_ea_supported(const G1Params& p, int ck, int mt, long long wgs);
+int k3x_fa_supported(const G1Params& p, int ck, int mt);                               // igemm_k3x.hip: the limb kernels of the fp32 parity mode
+int k3x_ea_supported(const G1Params& p, int ck, int mt, long long wgs);
+int k3tw_slab_count(int n, int d, int h, int w);                                       // igemm_k3_bf16.hip: workgroups (= slabs) of a k3tw_kernel launch
+int k2s2_scatter8_launch(const G1Params& p, int dtype, hipStream_t stream);            // k2s2_scatter8.hip
 
 // fp32 parity mode: the 3x3x3 convolutions run on the bf16 matrix cores through exact three-limb operand splitting (igemm_k3x.h); their packed
 // weights are VS_F32X3 images (pack.hip).  VS_F32_LIMBS=0 keeps the exact-f32 MFMA kernels (igemm_k3.h) and the plain fp32 images.
@@ -24,21 +29,29 @@ extern "C" int vs_conv_k3_f32_limbs(int d, int h, int w, int c_in) {
     return 1;
 }
 
-static int dispatch_k3(const G1Params& p, int dtype, int ck, int mt, int epi, int tiles, int row_tiles, hipStream_t s) {
-    if (dtype == VS_F32 && vs_conv_k3_f32_limbs(p.D, p.H, p.W, p.C)) {
-        G1Params q = p;
-        const int ckx = vs_k3x_ck(p.C);
-        q.nch = p.C / ckx;
-        const int rows16 = epi == EPI_SOFTMAX2 ? 16 : p.rb_total * 16;
-        // 32-row workgroups (B fragments shared by two row blocks) when that still fills the chip; chunks of 16 channels with a 32-row weight block
-        // fill the 160 KB of LDS exactly, so the per-(n,c) tables must be small
-        int mtx = 16;
-        if (rows16 % 32 == 0 && (long long)tiles * (rows16 / 32) >= 256 && (ckx == 8 || (size_t)2 * p.N * (p.C + p.M) * sizeof(float) <= 3000)) mtx = 32;
-        return g1_dispatch_k3_x3(q, ckx, mtx, epi, tiles, rows16 / mtx, s);
-    }
-    if (dtype == VS_F32) return g1_dispatch_k3_f32(p, ck, mt, epi, tiles, row_tiles, s);
-    if (dtype == VS_BF16) return g1_dispatch_k3_bf16(p, ck, mt, epi, tiles, row_tiles, s);
-    return g1_dispatch_k3_f16(p, ck, mt, epi, tiles, row_tiles, s);
+// channel chunk and row tile as a dispatcher gets them
+struct ConvTiles { int ck, mt, row_tiles; bool limbs; };
+
+// ... of a 3x3x3 launch; sets p.nch to match.  The fp32 parity mode re-plans both for the limb kernels.
+static ConvTiles k3_tiles(G1Params& p, int dtype, int ck, int mt, int rows16, long long tiles) {
+    ConvTiles t = {ck, mt, rows16 / mt, false};
+    p.nch = p.C / ck;
+    if (dtype != VS_F32 || !vs_conv_k3_f32_limbs(p.D, p.H, p.W, p.C)) return t;
+    t.limbs = true;
+    t.ck = vs_k3x_ck(p.C);
+    p.nch = p.C / t.ck;
+    // 32-row workgroups (B fragments shared by two row blocks) when that still fills the chip; chunks of 16 channels with a 32-row weight block
+    // fill the 160 KB of LDS exactly, so the per-(n,c) tables must be small
+    t.mt = (rows16 % 32 == 0 && tiles * (rows16 / 32) >= 256 && (t.ck == 8 || (size_t)2 * p.N * (p.C + p.M) * sizeof(float) <= 3000)) ? 32 : 16;
+    t.row_tiles = rows16 / t.mt;
+    return t;
+}
+
+static int dispatch_k3(const G1Params& p, int dtype, const ConvTiles& t, int epi, int tiles, hipStream_t s) {
+    if (t.limbs) return g1_dispatch_k3_x3(p, t.ck, t.mt, epi, tiles, t.row_tiles, s);
+    if (dtype == VS_F32) return g1_dispatch_k3_f32(p, t.ck, t.mt, epi, tiles, t.row_tiles, s);
+    if (dtype == VS_BF16) return g1_dispatch_k3_bf16(p, t.ck, t.mt, epi, tiles, t.row_tiles, s);
+    return g1_dispatch_k3_f16(p, t.ck, t.mt, epi, tiles, t.row_tiles, s);
 }
 
 static int pick_mt(int rows16, long long tiles) {
@@ -61,168 +74,214 @@ static int pick_mt(int rows16, long long tiles) {
 // the fused / epilogue-apply / composed / chain paths were sized for the default widths and decline anything wider (ops.py takes the per-layer path)
 static inline bool wide_layer(int c_in, int m_out) { return c_in > 256 || m_out > 256; }
 
-static int check_common(const void* x, const void* w, int n, int d, int h, int w_, int c_in, int dtype) {
-    if (!x || !w) return VS_EINVAL;
+// What the input's shape earns, in the order the C ABI reports it.  A launcher's alignment check has its place in that order (misaligned); a planner has no pointers.
+static int shape_status(int n, int d, int h, int w_, int c_in, int dtype, bool misaligned = false) {
     if (n <= 0 || d <= 0 || h <= 0 || w_ <= 0) return VS_ESHAPE;
     if (!(c_in == 8 || c_in == 16 || (c_in % 32 == 0 && c_in > 0 && c_in <= VS_MAX_CHANNELS))) return VS_ESHAPE;
     if (!vs_dtype_ok(dtype)) return VS_EDTYPE;
-    if (((uintptr_t)x & 15) || ((uintptr_t)w & 15)) return VS_EALIGN;
-    if ((double)n * d * h * w_ * c_in >= 2147483648.0) return VS_ESHAPE;      // kernels index activations with 32-bit element offsets
-    return VS_OK;
+    if (misaligned) return VS_EALIGN;
+    return (double)n * d * h * w_ * c_in >= 2147483648.0 ? VS_ESHAPE : VS_OK;      // kernels index activations with 32-bit element offsets
 }
 
-static inline long long g1_ea_capacity() { return 256; }     // g1_kernel<..., epilogue apply>: workgroups of one launch that are certainly resident together (one per CU)
+static int check_common(const void* x, const void* w, int n, int d, int h, int w_, int c_in, int dtype) {
+    if (!x || !w) return VS_EINVAL;
+    return shape_status(n, d, h, w_, c_in, dtype, ((uintptr_t)x & 15) || ((uintptr_t)w & 15));
+}
 
-static int gather_impl(const void* x, const double* x_stats, const void* w_packed, const float* bias,
-                       void* y, double* y_stats, const void* mask_x, const double* mask_stats, double* sums,
-                       int n, int d, int h, int w, int c_in, int m_out, int kind, int dtype, float eps, void* stream,
-                       const void* fa_x = nullptr, const double* fa_sums = nullptr, void* fa_dx = nullptr, int* fa_query = nullptr, float* wg_ws = nullptr,
-                       unsigned int* ea_sync = nullptr, unsigned int* ea_fault = nullptr, int* ea_query = nullptr, const void* ea_add = nullptr) {
-    int rc = check_common(x, w_packed, n, d, h, w, c_in, dtype);
-    if (rc) return rc;
-    if (!y || m_out <= 0 || m_out % 8 || ((uintptr_t)y & 15)) return VS_EINVAL;
-    if (m_out > VS_MAX_CHANNELS) return VS_ESHAPE;
-    if (kind != VS_CONV_K3 && kind != VS_CONV_K2S2) return VS_EINVAL;
-    if (wide_layer(c_in, m_out)) {
-        if (ea_query != nullptr) { *ea_query = 0; return VS_OK; }
-        if (fa_query != nullptr) { *fa_query = 0; return VS_OK; }
-        if (ea_sync != nullptr || fa_x != nullptr || wg_ws != nullptr) return VS_ESHAPE;
-    }
-    if (kind == VS_CONV_K2S2 && ((d | h | w) & 1)) return VS_ESHAPE;
-    G1Params p{};
-    p.x = x; p.x_stats = x_stats; p.wp = w_packed; p.bias = bias; p.y = y; p.y_stats = y_stats; p.prob = nullptr;
-    p.mask_x = mask_x; p.mask_stats = mask_stats; p.sums = sums;
-    p.fa_x = fa_x; p.fa_sums = fa_sums; p.fa_dx = fa_dx; p.wg_ws = wg_ws;
-    p.ea_sync = ea_sync; p.ea_fault = ea_fault; p.ea_add = ea_add;
-    if (sums && (!mask_x || !mask_stats || y_stats)) return VS_EINVAL;
-    p.N = n; p.D = d; p.H = h; p.W = w;
-    p.C = c_in; p.M = m_out;
-    p.rb_total = (m_out + 15) / 16;
-    const int ck = c_in < 32 ? c_in : 32;
-    p.nch = c_in / ck;
-    p.eps = eps;
-    p.inv_count_in = 1.0 / ((double)d * h * w);
+// a launch without its tensors.  kind: VS_CONV_K3 / VS_CONV_K2S2 (plan_gather), VS_CONV_T2S2 (plan_scatter); parts: the optional ones it has —
+// input statistics, a bias, fused IN-backward sums, the fused apply, the fused weight gradient, the epilogue apply
+enum { X_STATS = 1, BIAS = 2, SUMS = 4, FA = 8, WGRAD = 16, EA = 32 };
+struct ConvAsk { int n, d, h, w, c_in, m_out, kind, dtype, parts; };
+
+struct ConvPlan {
+    ConvAsk ask;
+    G1Params g;                   // the geometry part; every pointer null
+    ConvTiles t;
     long long tiles;
-    if (kind == VS_CONV_K3) {
-        p.Do = d; p.Ho = h; p.Wo = w;
-        p.tyn = (h + 3) / 4; p.txn = (w + 15) / 16;
-        p.tiles_per_sample = ((d + 3) / 4) * p.tyn * p.txn;
+    int status;                   // VS_OK: a kernel takes this launch with every part it asks for
+    bool fa_ok, ea_ok, wg_ok;     // the fused-apply / epilogue-apply / fused-weight-gradient form exists for this shape (the other parts of the ask as given)
+    bool stream8;                 // stride-2 scatter: the streaming 8 -> 8 kernel goes first
+};
+
+// g1_kernel's epilogue apply (igemm.h: the stride-2 kinds, any storage type): 16-row workgroups, all wgs of the launch resident together — one per CU is certain
+// (up to 256 VGPRs + AGPRs)
+static void g1_ea_plan(ConvPlan& pl, long long wgs) {
+    pl.ea_ok = pl.t.mt == 16 && wgs <= 256;
+    if (pl.ask.parts & EA) pl.g.ea_items = pl.g.tiles_per_sample * pl.t.row_tiles;
+}
+
+// what both planners start from: the status of the shape, then the fields every kind fills alike.  rows: those of the packed weight
+static ConvPlan plan_begin(const ConvAsk& a, int rows) {
+    ConvPlan pl{};
+    pl.ask = a;
+    pl.status = shape_status(a.n, a.d, a.h, a.w, a.c_in, a.dtype);
+    if (!pl.status && (a.m_out <= 0 || a.m_out % 8)) pl.status = VS_EINVAL;
+    if (!pl.status && a.m_out > VS_MAX_CHANNELS) pl.status = VS_ESHAPE;
+    if (pl.status) return pl;
+    G1Params& p = pl.g;
+    p.N = a.n; p.D = a.d; p.H = a.h; p.W = a.w;
+    p.C = a.c_in; p.M = a.m_out;
+    p.rb_total = (rows + 15) / 16;
+    pl.t.ck = a.c_in < 32 ? a.c_in : 32;
+    p.nch = a.c_in / pl.t.ck;
+    p.inv_count_in = 1.0 / ((double)a.d * a.h * a.w);
+    return pl;
+}
+
+// VS_CONV_K3 / VS_CONV_K2S2
+static ConvPlan plan_gather(const ConvAsk& a) {
+    ConvPlan pl = plan_begin(a, a.m_out);
+    const bool k3 = a.kind == VS_CONV_K3, sums = a.parts & SUMS, fa = a.parts & FA, ea = a.parts & EA;
+    if (!pl.status && !k3 && a.kind != VS_CONV_K2S2) pl.status = VS_EINVAL;
+    if (!pl.status && wide_layer(a.c_in, a.m_out) && (a.parts & (EA | FA | WGRAD))) pl.status = VS_ESHAPE;
+    if (!pl.status && !k3 && ((a.d | a.h | a.w) & 1)) pl.status = VS_ESHAPE;
+    if (pl.status) return pl;
+    G1Params& p = pl.g;
+    const int ck = pl.t.ck;
+    if (k3) {                                              // the column grid is the input grid, walked in 4 x 4 x 16 tiles
+        p.Do = a.d; p.Ho = a.h; p.Wo = a.w;
+        p.tyn = (a.h + 3) / 4; p.txn = (a.w + 15) / 16;
+        p.tiles_per_sample = ((a.d + 3) / 4) * p.tyn * p.txn;
     } else {
-        p.Do = d / 2; p.Ho = h / 2; p.Wo = w / 2;
-        p.tyn = p.txn = 0;
+        p.Do = a.d / 2; p.Ho = a.h / 2; p.Wo = a.w / 2;
         p.tiles_per_sample = vs_ceil_div((long long)p.Do * p.Ho * p.Wo, 256);
         // few workgroups and several 32-channel chunks (the deep stride-2 convs: 8-32 workgroups, one memory round trip per chunk each):
         // 64-voxel column tiles whose four waves split the chunks (g1_kernel, splitw)
-        if (ck == 32 && p.nch >= 2 && (long long)p.tiles_per_sample * n * p.rb_total <= 64) {
+        if (ck == 32 && p.nch >= 2 && (long long)p.tiles_per_sample * a.n * p.rb_total <= 64) {
             p.tiles_per_sample = vs_ceil_div((long long)p.Do * p.Ho * p.Wo, 64);
             p.tyn = 64;
         }
     }
-    tiles = (long long)p.tiles_per_sample * n;
     p.inv_count_out = 1.0 / ((double)p.Do * p.Ho * p.Wo);
+    pl.tiles = (long long)p.tiles_per_sample * a.n;
     const int rows16 = p.rb_total * 16;
-    int mt = (kind != VS_CONV_K3 && p.tyn == 64) ? 16 : pick_mt(rows16, tiles);
+    int mt = (!k3 && p.tyn == 64) ? 16 : pick_mt(rows16, pl.tiles);
     // fused apply on 32-channel chunks: every row-block workgroup of a tile repeats the apply pass over the tile's halo, and the kernel runs one
     // workgroup per CU (512 VGPRs) — 32-row tiles halve both the repeats and the workgroup count (24^3 x 32: 144 workgroups, one round)
-    if (kind == VS_CONV_K3 && fa_x != nullptr && ck == 32 && mt == 16 && rows16 % 32 == 0) mt = 32;
-    const int row_tiles = rows16 / mt;
-    if (kind == VS_CONV_K2S2 && (ea_query != nullptr || ea_sync != nullptr)) {
-        // g1_kernel's epilogue apply (igemm.h): any storage type; every workgroup of the launch resident — one per CU is certain (up to 256 VGPRs + AGPRs)
-        const bool ok = sums != nullptr && mt == 16 && tiles * row_tiles <= g1_ea_capacity();      // the epilogue-apply instantiations: 16-row workgroups
-        if (ea_query != nullptr) { *ea_query = ok ? 1 : 0; return VS_OK; }
-        if (!ok) return VS_ESHAPE;
-        p.ea_items = p.tiles_per_sample * row_tiles;
+    if (k3 && fa && ck == 32 && mt == 16 && rows16 % 32 == 0) mt = 32;
+    pl.t = k3 ? k3_tiles(p, a.dtype, ck, mt, rows16, pl.tiles) : ConvTiles{ck, mt, rows16 / mt, false};
+    const long long wgs = pl.tiles * pl.t.row_tiles;
+    if (!k3) {
+        g1_ea_plan(pl, wgs);
+    } else if (a.dtype != VS_F32) {
+        pl.fa_ok = g1_k3_fa_supported(p, pl.t.ck, pl.t.mt, sums) != 0;
+        pl.ea_ok = g1_k3_ea_supported(p, pl.t.ck, pl.t.mt, wgs) != 0;
+        // the fused weight gradient (igemm_k3tw.h): 8 -> 8, the weight image is the Toeplitz one of k3t_kernel
+        pl.wg_ok = vs_cfg().fuse_wgrad && a.c_in == 8 && a.m_out == 8 && a.n * 8 <= 192 && (double)a.n * a.d * a.h * a.w * 16 < 2147483648.0 &&
+                   vs_k3_toeplitz(8, 8, 27, a.dtype);
+    } else if (pl.t.limbs) {
+        pl.fa_ok = k3x_fa_supported(p, pl.t.ck, pl.t.mt) != 0;
+        pl.ea_ok = k3x_ea_supported(p, pl.t.ck, pl.t.mt, wgs) != 0;
     }
-    if (ea_query != nullptr) {                             // planning only: does k3b_kernel<32, 16, .., EA> take this backward-data launch?  (16-bit storage, 32-channel
-        *ea_query = (kind == VS_CONV_K3 && dtype != VS_F32 && ck == 32 && mt == 16 && sums != nullptr && !fa_x &&        // chunks, not a k3s volume, one resident round)
-                     !((long long)(d + 2) * (h + 2) * (w + 2) <= 512 && c_in <= 1024) && tiles * row_tiles <= k3b_ea_capacity(n, c_in, m_out)) ? 1 : 0;
-        if (kind == VS_CONV_K3 && dtype == VS_F32 && sums != nullptr && !fa_x && vs_conv_k3_f32_limbs(d, h, w, c_in) && vs_k3x_ck(c_in) == 8 && c_in > 8) {
-            // parity mode: k3x_kernel<8, 16, .., MULTI, .., EA> — 8-channel chunks, 16-row workgroups (dispatch_k3 takes 32 rows only for launches of >= 256 workgroups)
-            const long long rows16 = p.rb_total;
-            const bool mt32 = (p.rb_total * 16) % 32 == 0 && tiles * (p.rb_total / 2) >= 256;
-            *ea_query = (!mt32 && tiles * rows16 <= k3x_ea_capacity(n, c_in, m_out)) ? 1 : 0;
-        }
-        return VS_OK;
-    }
-    if (fa_query != nullptr) {                             // planning only: would a fused-apply launch of this shape find a kernel?
-        if (dtype == VS_F32)                               // parity mode: the 8 -> 8 full-resolution layers (k3xt_kernel<..., FA>, igemm_k3x.h)
-            *fa_query = kind == VS_CONV_K3 && vs_conv_k3_f32_limbs(d, h, w, c_in) &&
-                        ((c_in == 8 && m_out == 8 && n * 8 <= 192 && vs_k3x_toeplitz(8, 8, 27)) ||
-                         (c_in == 16 && m_out == 16 && n * 16 <= 192 && vs_k3x_ck(16) == 8));      // k3xt_kernel / k3x_kernel<8, 16, ..., FA> (igemm_k3x.h)
-        else
-            *fa_query = kind == VS_CONV_K3 ? g1_k3_fa_supported(p, ck, mt) : 0;
-        return VS_OK;
-    }
-    if (kind == VS_CONV_K3) {
-        return dispatch_k3(p, dtype, ck, mt, EPI_RAW, (int)tiles, row_tiles, (hipStream_t)stream);
-    }
-    return g1_dispatch_k2s2(p, dtype, ck, mt, (int)tiles, row_tiles, (hipStream_t)stream);
+    pl.ea_ok = pl.ea_ok && sums && !fa && vs_cfg().epilogue_apply;
+    if ((fa && !pl.fa_ok) || (ea && !pl.ea_ok) || ((a.parts & WGRAD) && !pl.wg_ok)) pl.status = VS_ESHAPE;
+    return pl;
 }
 
-extern "C" int vs_conv_gather_fwd(const void* x, const double* x_stats, const void* w_packed, const float* bias,
-                                  void* y, double* y_stats, int n, int d, int h, int w, int c_in, int m_out,
-                                  int kind, int dtype, float eps, void* stream) {
-    return gather_impl(x, x_stats, w_packed, bias, y, y_stats, nullptr, nullptr, nullptr, n, d, h, w, c_in, m_out, kind, dtype, eps, stream);
+// the stride-2 scatter (backward-data of Conv3d(k2, s2), forward of ConvTranspose3d(k2, s2)): the column grid is the input grid, 8 taps x m_out rows
+static ConvPlan plan_scatter(const ConvAsk& a) {
+    ConvPlan pl = plan_begin(a, 8 * a.m_out);
+    const bool sums = a.parts & SUMS, ea = a.parts & EA;
+    if (!pl.status && wide_layer(a.c_in, a.m_out) && ea) pl.status = VS_ESHAPE;
+    if (pl.status) return pl;
+    G1Params& p = pl.g;
+    p.Do = a.d; p.Ho = a.h; p.Wo = a.w;
+    p.inv_count_out = 1.0 / (8.0 * a.d * a.h * a.w);
+    p.tiles_per_sample = vs_ceil_div((long long)a.d * a.h * a.w, 256);
+    pl.tiles = (long long)p.tiles_per_sample * a.n;
+    // the 8 -> 8 backward-data scatter at full resolution (Down1): a streaming kernel instead of an MFMA tile per 256 coarse voxels (k2s2_scatter8.hip);
+    // it has no epilogue apply (full resolution: never resident) and hands the shapes it declines back with VS_ESHAPE
+    pl.stream8 = !ea && vs_cfg().k2s2_stream && sums && a.c_in == 8 && a.m_out == 8 && a.dtype != VS_F32 && !(a.parts & (BIAS | X_STATS));
+    const int rows16 = p.rb_total * 16;
+    const int mt = pick_mt(rows16, pl.tiles);
+    pl.t = ConvTiles{pl.t.ck, mt, rows16 / mt, false};
+    g1_ea_plan(pl, pl.tiles * pl.t.row_tiles);
+    pl.ea_ok = pl.ea_ok && sums && vs_cfg().epilogue_apply;
+    if (ea && !pl.ea_ok) pl.status = VS_ESHAPE;
+    return pl;
 }
 
-extern "C" int vs_conv_gather_bwd_data(const void* x, const void* w_packed, void* y, const void* mask_x,
-                                       const double* mask_stats, double* sums, int n, int d, int h, int w, int c_in,
-                                       int m_out, int kind, int dtype, float eps, void* stream) {
+// validate the pointers every launch has, then dispatch.  p: the plan's geometry with the call's pointers and eps filled in
+static int launch_conv(const ConvPlan& pl, const G1Params& p, void* stream) {
+    const ConvAsk& a = pl.ask;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = check_common(p.x, p.wp, a.n, a.d, a.h, a.w, a.c_in, a.dtype);
+    if (rc) return rc;
+    if (!p.y || ((uintptr_t)p.y & 15)) return VS_EINVAL;
+    if (pl.status) return pl.status;
+    if (a.kind == VS_CONV_K3) return dispatch_k3(p, a.dtype, pl.t, EPI_RAW, (int)pl.tiles, s);
+    if (a.kind == VS_CONV_K2S2) return g1_dispatch_k2s2(p, a.dtype, pl.t.ck, pl.t.mt, (int)pl.tiles, pl.t.row_tiles, s);
+    if (pl.stream8) {
+        rc = k2s2_scatter8_launch(p, a.dtype, s);
+        if (rc != VS_ESHAPE) return rc;
+    }
+    return g1_dispatch_pw(p, a.dtype, pl.t.ck, pl.t.mt, (int)pl.tiles, pl.t.row_tiles, s);
+}
+
+extern "C" int vs_conv_gather_fwd(const void* x, const double* x_stats, const void* w_packed, const float* bias, void* y, double* y_stats,
+                                  int n, int d, int h, int w, int c_in, int m_out, int kind, int dtype, float eps, void* stream) {
+    const ConvPlan pl = plan_gather({n, d, h, w, c_in, m_out, kind, dtype, 0});
+    G1Params p = pl.g;
+    p.x = x; p.x_stats = x_stats; p.wp = w_packed; p.bias = bias; p.y = y; p.y_stats = y_stats; p.eps = eps;
+    return launch_conv(pl, p, stream);
+}
+
+// a backward-data launch with the fused IN-backward sums: the plan's geometry plus the pointers every such entry point has
+static G1Params bwd_params(const ConvPlan& pl, const void* x, const void* w_packed, void* y, const void* mask_x, const double* mask_stats, double* sums, float eps) {
+    G1Params p = pl.g;
+    p.x = x; p.wp = w_packed; p.y = y; p.mask_x = mask_x; p.mask_stats = mask_stats; p.sums = sums; p.eps = eps;
+    return p;
+}
+
+extern "C" int vs_conv_gather_bwd_data(const void* x, const void* w_packed, void* y, const void* mask_x, const double* mask_stats, double* sums,
+                                       int n, int d, int h, int w, int c_in, int m_out, int kind, int dtype, float eps, void* stream) {
     if (!mask_x || !mask_stats || !sums) return VS_EINVAL;
-    return gather_impl(x, nullptr, w_packed, nullptr, y, nullptr, mask_x, mask_stats, sums, n, d, h, w, c_in, m_out, kind, dtype, eps, stream);
+    const ConvPlan pl = plan_gather({n, d, h, w, c_in, m_out, kind, dtype, SUMS});
+    return launch_conv(pl, bwd_params(pl, x, w_packed, y, mask_x, mask_stats, sums, eps), stream);
 }
 
-extern "C" int vs_conv_k3_bwd_data_fused_apply(const void* g, const void* act_x, const double* act_stats, const double* act_sums,
-                                               const void* w_packed, void* y, const void* mask_x, const double* mask_stats, double* sums,
-                                               void* dx_out, int n, int d, int h, int w, int c_in, int m_out, int dtype, float eps,
-                                               void* stream) {
+static ConvPlan plan_fused_apply(int n, int d, int h, int w, int c_in, int m_out, bool lazy_input, int dtype) {
+    return plan_gather({n, d, h, w, c_in, m_out, VS_CONV_K3, dtype, X_STATS | FA | (lazy_input ? SUMS : 0)});
+}
+extern "C" int vs_conv_k3_bwd_data_fused_apply(const void* g, const void* act_x, const double* act_stats, const double* act_sums, const void* w_packed, void* y,
+                                               const void* mask_x, const double* mask_stats, double* sums, void* dx_out, int n, int d, int h, int w, int c_in,
+                                               int m_out, int dtype, float eps, void* stream) {
     if (!g || !act_x || !act_stats || !act_sums) return VS_EINVAL;
     if ((mask_x == nullptr) != (sums == nullptr) || (mask_x == nullptr) != (mask_stats == nullptr)) return VS_EINVAL;    // all three (lazy conv input) or none
-    if (dtype == VS_F32 && !vs_conv_k3_fused_apply_supported(n, d, h, w, c_in, m_out, mask_x != nullptr, dtype)) return VS_ESHAPE;
+    const ConvPlan pl = plan_fused_apply(n, d, h, w, c_in, m_out, mask_x != nullptr, dtype);
+    if (dtype == VS_F32 && pl.status) return VS_ESHAPE;
     if (((uintptr_t)act_x & 15) || (dx_out && ((uintptr_t)dx_out & 15))) return VS_EALIGN;
-    return gather_impl(g, act_stats, w_packed, nullptr, y, nullptr, mask_x, mask_stats, sums, n, d, h, w, c_in, m_out, VS_CONV_K3, dtype, eps,
-                       stream, act_x, act_sums, dx_out);
+    G1Params p = bwd_params(pl, g, w_packed, y, mask_x, mask_stats, sums, eps);
+    p.x_stats = act_stats; p.fa_x = act_x; p.fa_sums = act_sums; p.fa_dx = dx_out;
+    return launch_conv(pl, p, stream);
 }
 
 extern "C" int vs_conv_k3_fused_apply_supported(int n, int d, int h, int w, int c_in, int m_out, int lazy_input, int dtype) {
-    if (!vs_dtype_ok(dtype)) return 0;
-    static const char dummy[16] __attribute__((aligned(16))) = {0};        // planning only: no pointer is dereferenced
-    static double dsink[2];
-    int ok = 0;
-    const int rc = gather_impl(dummy, (const double*)dummy, dummy, nullptr, (void*)dummy, nullptr, lazy_input ? dummy : nullptr,
-                               lazy_input ? (const double*)dummy : nullptr, lazy_input ? dsink : nullptr, n, d, h, w, c_in, m_out, VS_CONV_K3,
-                               dtype, 1e-5f, nullptr, dummy, (const double*)dummy, nullptr, &ok);
-    return rc == VS_OK ? ok : 0;
+    return plan_fused_apply(n, d, h, w, c_in, m_out, lazy_input != 0, dtype).status == VS_OK;
 }
 
 // ---- backward-data whose epilogue applies the InstanceNorm+ReLU backward itself (igemm_k3b.h EA, round 6) ----
 extern "C" int vs_conv_k3_bwd_data_applied_supported(int n, int d, int h, int w, int c_in, int m_out, int dtype) {
-    const int on = vs_cfg().epilogue_apply;
-    if (!on || !vs_dtype_ok(dtype)) return 0;
-    static const char dummy[16] __attribute__((aligned(16))) = {0};        // planning only: no pointer is dereferenced
-    static double dsink[2];
-    int ok = 0;
-    const int rc = gather_impl(dummy, nullptr, dummy, nullptr, (void*)dummy, nullptr, dummy, (const double*)dummy, dsink, n, d, h, w, c_in, m_out, VS_CONV_K3, dtype,
-                               1e-5f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ok);
-    return rc == VS_OK ? ok : 0;
+    return plan_gather({n, d, h, w, c_in, m_out, VS_CONV_K3, dtype, SUMS | EA}).status == VS_OK;
 }
 
 extern "C" int vs_conv_k3_bwd_data_applied(const void* x, const void* w_packed, void* y, const void* mask_x, const double* mask_stats, double* sums,
                                            unsigned int* sync, unsigned int* fault, int n, int d, int h, int w, int c_in, int m_out, int dtype, float eps, void* stream) {
     if (!mask_x || !mask_stats || !sums || !sync || !fault) return VS_EINVAL;
     if (((uintptr_t)sync & 127) || ((uintptr_t)fault & 3)) return VS_EALIGN;
-    if (!vs_conv_k3_bwd_data_applied_supported(n, d, h, w, c_in, m_out, dtype)) return VS_ESHAPE;
-    return gather_impl(x, nullptr, w_packed, nullptr, y, nullptr, mask_x, mask_stats, sums, n, d, h, w, c_in, m_out, VS_CONV_K3, dtype, eps, stream,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, sync, fault);
+    const ConvPlan pl = plan_gather({n, d, h, w, c_in, m_out, VS_CONV_K3, dtype, SUMS | EA});
+    if (pl.status) return VS_ESHAPE;
+    G1Params p = bwd_params(pl, x, w_packed, y, mask_x, mask_stats, sums, eps);
+    p.ea_sync = sync; p.ea_fault = fault;
+    return launch_conv(pl, p, stream);
 }
 
 // ---- backward-data with the layer's weight gradient fused (igemm_k3tw.h) ----
+static ConvPlan plan_wgrad(int n, int d, int h, int w, int c_in, int m_out, bool act, int dtype) {
+    return plan_gather({n, d, h, w, c_in, m_out, VS_CONV_K3, dtype, SUMS | WGRAD | (act ? X_STATS | FA : 0)});      // act: an un-applied gradient comes in
+}
 extern "C" int vs_conv_k3_bwd_data_wgrad_supported(int n, int d, int h, int w, int c_in, int m_out, int dtype) {
-    const int on = vs_cfg().fuse_wgrad;
-    if (!on || (dtype != VS_BF16 && dtype != VS_F16)) return 0;
-    if (c_in != 8 || m_out != 8 || n <= 0 || n * 8 > 192 || d <= 0 || h <= 0 || w <= 0) return 0;
-    if ((double)n * d * h * w * 16 >= 2147483648.0) return 0;
-    return vs_k3_toeplitz(8, 8, 27, dtype) ? 1 : 0;     // the weight image is the Toeplitz one of k3t_kernel
+    return plan_wgrad(n, d, h, w, c_in, m_out, false, dtype).status == VS_OK;
 }
 
 extern "C" int vs_conv_k3_bwd_data_wgrad_slabs(int n, int d, int h, int w) {
@@ -235,10 +294,12 @@ extern "C" int vs_conv_k3_bwd_data_wgrad(const void* g, const void* act_x, const
                                          int m_out, int dtype, float eps, void* stream) {
     if (!g || !slabs || !mask_x || !mask_stats || !sums) return VS_EINVAL;
     if ((act_x == nullptr) != (act_stats == nullptr) || (act_x == nullptr) != (act_sums == nullptr)) return VS_EINVAL;     // all three (un-applied gradient in) or none
-    if (!vs_conv_k3_bwd_data_wgrad_supported(n, d, h, w, c_in, m_out, dtype)) return VS_ESHAPE;
+    const ConvPlan pl = plan_wgrad(n, d, h, w, c_in, m_out, act_x != nullptr, dtype);
+    if (pl.status) return VS_ESHAPE;
     if (((uintptr_t)slabs & 15) || (act_x && ((uintptr_t)act_x & 15))) return VS_EALIGN;
-    return gather_impl(g, act_stats, w_packed, nullptr, y, nullptr, mask_x, mask_stats, sums, n, d, h, w, c_in, m_out, VS_CONV_K3, dtype, eps,
-                       stream, act_x, act_sums, nullptr, nullptr, slabs);
+    G1Params p = bwd_params(pl, g, w_packed, y, mask_x, mask_stats, sums, eps);
+    p.x_stats = act_stats; p.fa_x = act_x; p.fa_sums = act_sums; p.wg_ws = slabs;
+    return launch_conv(pl, p, stream);
 }
 
 // out_block's backward in one launch: softmax backward while staging, backward-data with the fused IN-backward sums [, weight gradient slabs, bias partials]
@@ -247,91 +308,39 @@ extern "C" int vs_conv_k3_softmax2_bwd_data(const float* prob, const float* gpro
                                             float eps, float drop_p, unsigned long long drop_seed, void* stream) {
     if (!prob || (!gprob && !gprob_cl) || !w_packed || !y || !mask_x || !mask_stats || !sums) return VS_EINVAL;
     if (bias_part && !slabs) return VS_EINVAL;             // the bias partials travel with the weight gradient's slabs
-    if (!vs_conv_k3_bwd_data_wgrad_supported(n, d, h, w, 8, 8, dtype)) return VS_ESHAPE;
+    const ConvPlan pl = plan_wgrad(n, d, h, w, 8, 8, false, dtype);
+    if (pl.status) return VS_ESHAPE;
     if (((uintptr_t)w_packed & 15) || ((uintptr_t)y & 15) || ((uintptr_t)mask_x & 15) || (gprob_cl && ((uintptr_t)gprob_cl & 15)) || (slabs && ((uintptr_t)slabs & 15)) ||
         ((uintptr_t)prob & 3) || ((uintptr_t)gprob & 3)) return VS_EALIGN;
     if (!(drop_p >= 0.f && drop_p < 1.f)) return VS_EINVAL;
-    G1Params p{};
-    p.wp = w_packed; p.y = y; p.mask_x = mask_x; p.mask_stats = mask_stats; p.sums = sums;
+    G1Params p = bwd_params(pl, nullptr, w_packed, y, mask_x, mask_stats, sums, eps);      // no x: the gradient is formed from the probabilities while staging
     p.sm_prob = prob; p.sm_gprob = gprob; p.sm_gcl = gprob_cl; p.wg_ws = slabs; p.wg_bias = bias_part;
     p.drop_p = drop_p; p.drop_seed = drop_seed;
-    p.N = n; p.D = d; p.H = h; p.W = w; p.Do = d; p.Ho = h; p.Wo = w; p.C = 8; p.M = 8; p.rb_total = 1; p.nch = 1;
-    p.eps = eps;
-    p.inv_count_in = 1.0 / ((double)d * h * w); p.inv_count_out = p.inv_count_in;
-    return dispatch_k3(p, dtype, 8, 16, EPI_RAW, 0, 1, (hipStream_t)stream);
+    return dispatch_k3(p, dtype, pl.t, EPI_RAW, 0, (hipStream_t)stream);                    // k3tw_launch tiles the grid its own way
 }
 
-static int scatter_impl(const void* x, const double* x_stats, const void* w_packed, const float* bias, void* y,
-                        const void* mask_x, const double* mask_stats, double* sums, int n, int d, int h, int w, int c_in,
-                        int m_out, int dtype, float eps, void* stream,
-                        unsigned int* ea_sync = nullptr, unsigned int* ea_fault = nullptr, int* ea_query = nullptr, const void* ea_add = nullptr) {
-    int rc = check_common(x, w_packed, n, d, h, w, c_in, dtype);
-    if (rc) return rc;
-    if (!y || m_out <= 0 || m_out % 8 || ((uintptr_t)y & 15)) return VS_EINVAL;
-    if (m_out > VS_MAX_CHANNELS) return VS_ESHAPE;
-    if (wide_layer(c_in, m_out)) {
-        if (ea_query != nullptr) { *ea_query = 0; return VS_OK; }
-        if (ea_sync != nullptr) return VS_ESHAPE;
-    }
-    G1Params p{};
-    p.x = x; p.x_stats = x_stats; p.wp = w_packed; p.bias = bias; p.y = y; p.y_stats = nullptr; p.prob = nullptr;
-    p.mask_x = mask_x; p.mask_stats = mask_stats; p.sums = sums;
-    p.inv_count_out = 1.0 / (8.0 * d * h * w);
-    p.N = n; p.D = d; p.H = h; p.W = w;
-    p.Do = d; p.Ho = h; p.Wo = w;
-    p.C = c_in; p.M = m_out;
-    p.rb_total = (8 * m_out + 15) / 16;
-    const int ck = c_in < 32 ? c_in : 32;
-    p.nch = c_in / ck;
-    p.eps = eps;
-    p.inv_count_in = 1.0 / ((double)d * h * w);
-    p.tiles_per_sample = vs_ceil_div((long long)d * h * w, 256);
-    const long long tiles = (long long)p.tiles_per_sample * n;
-    // the 8 -> 8 backward-data scatter at full resolution (Down1): a streaming kernel instead of an MFMA tile per 256 coarse voxels (k2s2_scatter8.hip)
-    const int stream8 = vs_cfg().k2s2_stream;
-    const bool ea_asked = ea_query != nullptr || ea_sync != nullptr;
-    if (!ea_asked && stream8 && sums && c_in == 8 && m_out == 8 && dtype != VS_F32 && !bias && !x_stats) {
-        rc = k2s2_scatter8_launch(p, dtype, (hipStream_t)stream);
-        if (rc != VS_ESHAPE) return rc;
-    }
-    const int rows16 = p.rb_total * 16;
-    const int mt = pick_mt(rows16, tiles);
-    if (ea_asked) {                                        // g1_kernel's epilogue apply (see gather_impl); not the streaming 8 -> 8 kernel's shapes (full resolution: never resident)
-        const bool ok = sums != nullptr && mt == 16 && tiles * (rows16 / mt) <= g1_ea_capacity();
-        if (ea_query != nullptr) { *ea_query = ok ? 1 : 0; return VS_OK; }
-        if (!ok) return VS_ESHAPE;
-        p.ea_sync = ea_sync; p.ea_fault = ea_fault; p.ea_add = ea_add;
-        p.ea_items = p.tiles_per_sample * (rows16 / mt);
-    }
-    return g1_dispatch_pw(p, dtype, ck, mt, (int)tiles, rows16 / mt, (hipStream_t)stream);
+extern "C" int vs_conv_scatter_fwd(const void* x, const double* x_stats, const void* w_packed, const float* bias, void* y,
+                                   int n, int d, int h, int w, int c_in, int m_out, int dtype, float eps, void* stream) {
+    const ConvPlan pl = plan_scatter({n, d, h, w, c_in, m_out, VS_CONV_T2S2, dtype, (x_stats ? X_STATS : 0) | (bias ? BIAS : 0)});
+    G1Params p = pl.g;
+    p.x = x; p.x_stats = x_stats; p.wp = w_packed; p.bias = bias; p.y = y; p.eps = eps;
+    return launch_conv(pl, p, stream);
 }
 
-extern "C" int vs_conv_scatter_fwd(const void* x, const double* x_stats, const void* w_packed, const float* bias,
-                                   void* y, int n, int d, int h, int w, int c_in, int m_out, int dtype, float eps,
-                                   void* stream) {
-    return scatter_impl(x, x_stats, w_packed, bias, y, nullptr, nullptr, nullptr, n, d, h, w, c_in, m_out, dtype, eps, stream);
-}
-
-extern "C" int vs_conv_scatter_bwd_data(const void* x, const void* w_packed, void* y, const void* mask_x,
-                                        const double* mask_stats, double* sums, int n, int d, int h, int w, int c_in,
-                                        int m_out, int dtype, float eps, void* stream) {
+extern "C" int vs_conv_scatter_bwd_data(const void* x, const void* w_packed, void* y, const void* mask_x, const double* mask_stats, double* sums,
+                                        int n, int d, int h, int w, int c_in, int m_out, int dtype, float eps, void* stream) {
     if (!mask_x || !mask_stats || !sums) return VS_EINVAL;
-    return scatter_impl(x, nullptr, w_packed, nullptr, y, mask_x, mask_stats, sums, n, d, h, w, c_in, m_out, dtype, eps, stream);
+    const ConvPlan pl = plan_scatter({n, d, h, w, c_in, m_out, VS_CONV_T2S2, dtype, SUMS});
+    return launch_conv(pl, bwd_params(pl, x, w_packed, y, mask_x, mask_stats, sums, eps), stream);
 }
 
 // ---- the same for the stride-2 kinds (igemm.h g1_kernel's epilogue apply): scatter = 0: backward-data of ConvTranspose3d(k2, s2) (a stride-2 gather);
 // scatter = 1: backward-data of Conv3d(k2, s2) (the scatter form).  add (nullable): a second gradient of the same raw tensor, summed in after the apply ----
+static ConvPlan plan_s2_applied(int n, int d, int h, int w, int c_in, int m_out, int scatter, int dtype) {
+    return scatter ? plan_scatter({n, d, h, w, c_in, m_out, VS_CONV_T2S2, dtype, SUMS | EA}) : plan_gather({n, d, h, w, c_in, m_out, VS_CONV_K2S2, dtype, SUMS | EA});
+}
 extern "C" int vs_conv_s2_bwd_data_applied_supported(int n, int d, int h, int w, int c_in, int m_out, int scatter, int dtype) {
-    const int on = vs_cfg().epilogue_apply;
-    if (!on || !vs_dtype_ok(dtype)) return 0;
-    static const char dummy[16] __attribute__((aligned(16))) = {0};        // planning only: no pointer is dereferenced
-    static double dsink[2];
-    int ok = 0;
-    const int rc = scatter ? scatter_impl(dummy, nullptr, dummy, nullptr, (void*)dummy, dummy, (const double*)dummy, dsink, n, d, h, w, c_in, m_out, dtype, 1e-5f, nullptr,
-                                          nullptr, nullptr, &ok)
-                           : gather_impl(dummy, nullptr, dummy, nullptr, (void*)dummy, nullptr, dummy, (const double*)dummy, dsink, n, d, h, w, c_in, m_out, VS_CONV_K2S2, dtype,
-                                         1e-5f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ok);
-    return rc == VS_OK ? ok : 0;
+    return plan_s2_applied(n, d, h, w, c_in, m_out, scatter, dtype).status == VS_OK;
 }
 
 extern "C" int vs_conv_s2_bwd_data_applied(const void* x, const void* w_packed, void* y, const void* mask_x, const double* mask_stats, double* sums, const void* add,
@@ -339,10 +348,11 @@ extern "C" int vs_conv_s2_bwd_data_applied(const void* x, const void* w_packed, 
                                            void* stream) {
     if (!mask_x || !mask_stats || !sums || !sync || !fault) return VS_EINVAL;
     if (((uintptr_t)sync & 127) || ((uintptr_t)fault & 3) || (add && ((uintptr_t)add & 15))) return VS_EALIGN;
-    if (!vs_conv_s2_bwd_data_applied_supported(n, d, h, w, c_in, m_out, scatter, dtype)) return VS_ESHAPE;
-    if (scatter) return scatter_impl(x, nullptr, w_packed, nullptr, y, mask_x, mask_stats, sums, n, d, h, w, c_in, m_out, dtype, eps, stream, sync, fault, nullptr, add);
-    return gather_impl(x, nullptr, w_packed, nullptr, y, nullptr, mask_x, mask_stats, sums, n, d, h, w, c_in, m_out, VS_CONV_K2S2, dtype, eps, stream,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, sync, fault, nullptr, add);
+    const ConvPlan pl = plan_s2_applied(n, d, h, w, c_in, m_out, scatter, dtype);
+    if (pl.status) return VS_ESHAPE;
+    G1Params p = bwd_params(pl, x, w_packed, y, mask_x, mask_stats, sums, eps);
+    p.ea_sync = sync; p.ea_fault = fault; p.ea_add = add;
+    return launch_conv(pl, p, stream);
 }
 
 extern "C" int vs_conv_k3_softmax2_fwd(const void* x, const double* x_stats, const void* w_packed, const float* bias,
@@ -357,28 +367,17 @@ extern "C" int vs_conv_k3_softmax2_dropout_fwd(const void* x, const double* x_st
     return vs_conv_k3_softmax2_cl_fwd(x, x_stats, w_packed, bias, prob, nullptr, n, d, h, w, c_in, dtype, eps, drop_p, drop_seed, stream);
 }
 
-extern "C" int vs_conv_k3_softmax2_cl_fwd(const void* x, const double* x_stats, const void* w_packed, const float* bias,
-                                          float* prob, void* prob_cl, int n, int d, int h, int w, int c_in, int dtype, float eps,
-                                          float drop_p, unsigned long long drop_seed, void* stream) {
+extern "C" int vs_conv_k3_softmax2_cl_fwd(const void* x, const double* x_stats, const void* w_packed, const float* bias, float* prob, void* prob_cl,
+                                          int n, int d, int h, int w, int c_in, int dtype, float eps, float drop_p, unsigned long long drop_seed, void* stream) {
     if (drop_p < 0.f || drop_p >= 1.f) return VS_EINVAL;
     if (prob_cl && dtype == VS_F32) return VS_EDTYPE;
     if (prob_cl && ((uintptr_t)prob_cl & 15)) return VS_EALIGN;
     int rc = check_common(x, w_packed, n, d, h, w, c_in, dtype);
     if (rc) return rc;
     if (!prob || c_in != 8) return VS_ESHAPE;
-    G1Params p{};
-    p.x = x; p.x_stats = x_stats; p.wp = w_packed; p.bias = bias; p.y = prob_cl; p.y_stats = nullptr; p.prob = prob;
-    p.mask_x = nullptr; p.mask_stats = nullptr; p.sums = nullptr; p.inv_count_out = 1.0 / ((double)d * h * w);
+    const ConvPlan pl = plan_gather({n, d, h, w, 8, 8, VS_CONV_K3, dtype, 0});           // the two logits are stored in 8 channels: one 16-row block
+    G1Params p = pl.g;
+    p.x = x; p.x_stats = x_stats; p.wp = w_packed; p.bias = bias; p.y = prob_cl; p.prob = prob; p.eps = eps;
     p.drop_p = drop_p; p.drop_seed = drop_seed;
-    p.N = n; p.D = d; p.H = h; p.W = w;
-    p.Do = d; p.Ho = h; p.Wo = w;
-    p.C = c_in; p.M = 8;
-    p.rb_total = 1;
-    p.nch = 1;
-    p.eps = eps;
-    p.inv_count_in = 1.0 / ((double)d * h * w);
-    p.tyn = (h + 3) / 4; p.txn = (w + 15) / 16;
-    p.tiles_per_sample = ((d + 3) / 4) * p.tyn * p.txn;
-    const long long tiles = (long long)p.tiles_per_sample * n;
-    return dispatch_k3(p, dtype, 8, 16, EPI_SOFTMAX2, (int)tiles, 1, (hipStream_t)stream);
+    return dispatch_k3(p, dtype, pl.t, EPI_SOFTMAX2, (int)pl.tiles, (hipStream_t)stream);
 }

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k2s2_scatter8_kernel(const G1Params p, in
     }
 }
 
-// p as scatter_impl (conv_api.hip) fills it: x = gy on the coarse grid (N, D, H, W, C), y / mask_x on the fine grid, inv_count_out = 1 / fine voxels per sample
+// p as plan_scatter and the launcher (conv_api.hip) fill it: x = gy on the coarse grid (N, D, H, W, C), y / mask_x on the fine grid, inv_count_out = 1 / fine voxels per sample
 template <typename T, int CH>
 static int k2s8_go(const G1Params& p, hipStream_t stream) {
     using L = K2S8<CH>;
