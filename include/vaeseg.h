@@ -721,6 +721,46 @@ int vs_quantile(const float* x, const unsigned char* mask, int use_above, float 
                 float* hi_out, long long* count, long long* rejected, void* workspace, int planes, int d, int h, int w, void* stream);
 int vs_intensity_map(const float* x, const double* src, const double* dst, int L, int clamp, float* y, int planes, int d, int h, int w, void* stream);
 
+/* ---- training patches: foreground-oversampled windows of an unscaled volume, cut on the device (csrc/patch.hip) -------------------
+ * A training batch is made of windows of (pd, ph, pw) voxels cut from a volume (d, h, w); a share of them is forced to contain a uniformly chosen
+ * voxel of a uniformly chosen class that is present.  All arithmetic is integer; nothing here is inherited from another loader's random stream.
+ *   classes   A voxel of the label belongs to class k iff its value is the integer k, 0 <= k < n_class <= 8; any other value (NaN, a fraction, a
+ *             value >= n_class) belongs to no class.  label: fp32 (VS_PATCH_F32) or uint8 (VS_PATCH_U8), (d, h, w) contiguous, d*h*w < 2^31.
+ *   bounds    per axis, volume side S and patch side P: need = max(P - S, 0), lb = -(need / 2), ub = S + need / 2 + need % 2 - P.  S >= P gives
+ *             [0, S - P]; S < P gives lb == ub, the volume centred in the patch.
+ *   request   five unsigned 32-bit words (wc, wv, wz, wy, wx) and a flag `forced`.  A word w maps to a range of m values as (w * m) >> 32 with a
+ *             64-bit product: no rejection, no floating point.
+ *   forced    present = the classes of the call's list whose voxel count n_k is > 0, ascending, mc of them.  mc > 0: k = present[(wc * mc) >> 32],
+ *             rank r = (wv * n_k) >> 32, v = the r-th voxel of class k in ascending linear index (z * h + y) * w + x, and per axis
+ *             o = min(max(lb, v - P / 2), ub): the patch contains v.  mc == 0: the request is treated as free.
+ *   free      per axis o = lb + ((w_axis * (ub - lb + 1)) >> 32); wc and wv are not looked at.
+ * vs_patch_index  table: int32 [n_chunks + 1][n_class], n_chunks = ceil(d*h*w / VS_PATCH_CHUNK): row j holds the number of voxels of each class in
+ *             the chunks before chunk j (a chunk is VS_PATCH_CHUNK consecutive voxels of the linear index), the last row the totals.  Two launches:
+ *             workgroups count whole chunks with wave ballots and store one word per (chunk, class); one workgroup per class scans its column.
+ *             vs_patch_index_bytes: the table's size (0 for arguments vs_patch_index refuses); vs_patch_chunk: VS_PATCH_CHUNK.
+ * vs_patch_pick   words: uint32 [r][5], forced: int32 [r], both in DEVICE memory; the class list by value: n_sel <= 8 strictly ascending classes, class
+ *             i in bits [3 i, 3 i + 3) of `classes`.  picks: int32 [r][8] = (oz, oy, ox, k, vz, vy, vx, 0) for a forced request, (oz, oy, ox, -1, -1,
+ *             -1, -1, 0) for a free one.  One wave per request: totals, binary search of the chunk in the class's column, a walk through the chunk 64
+ *             voxels at a time (ballot, popcount) to the r-th match.  label and table are those of vs_patch_index; a table that does not belong to the
+ *             label cannot send a read out of bounds (the request then falls to a free origin).
+ * vs_patch_gather n_src <= 4 fp32 volumes (d, h, w), the pointers and a cval per source by value; out: fp32 (n_src, r, qd, qh, qw) with q = p + 2 margin
+ *             per axis, out[s][i][z][y][x] = src_s[o_i - margin + (z, y, x)] where that lies inside the volume and cval_s elsewhere; o_i = picks[i][0..2]
+ *             read from DEVICE memory — any integers, negative ones and ones past the volume included.  A thread owns four x of an output row.
+ * No atomics, no memset, nothing allocated, synchronised or read back; every call can be captured in a HIP graph and gives the same bits eagerly, under
+ * replay and in both builds.  A null pointer, n_class outside [1, 8], a class list that is not strictly ascending inside [0, n_class), r < 1, a patch
+ * side < 1, margin < 0, n_src outside [1, 4], a NaN cval, out equal to a source: VS_EINVAL; an unknown label type: VS_EDTYPE; an empty volume, one of
+ * 2^31 voxels or more, an output block of 2^31 voxels or more: VS_ESHAPE; an fp32 / int32 buffer not 4-byte, picks, sources or out not 16-byte aligned:
+ * VS_EALIGN; all answered on the host before any launch. */
+#define VS_PATCH_CHUNK 4096
+enum { VS_PATCH_F32 = 0, VS_PATCH_U8 = 1 };
+int vs_patch_chunk(void);
+size_t vs_patch_index_bytes(int d, int h, int w, int n_class);
+int vs_patch_index(const void* label, int dtype, int d, int h, int w, int n_class, int* table, void* stream);
+int vs_patch_pick(const void* label, int dtype, const int* table, int n_class, int n_sel, int classes, const unsigned int* words, const int* forced,
+                  int r, int d, int h, int w, int pd, int ph, int pw, int* picks, void* stream);
+int vs_patch_gather(const float* src0, const float* src1, const float* src2, const float* src3, float cval0, float cval1, float cval2, float cval3,
+                    int n_src, const int* picks, int r, int d, int h, int w, int pd, int ph, int pw, int margin, float* out, void* stream);
+
 /* ---- sliding-window prediction of a whole volume (csrc/window.hip; no counterpart in the reference) -------------------------------
  * A volume (C, D, H, W) is tiled with overlapping cubic windows of side `patch`, a network maps batches (B, C, P, P, P) of them to planar
  * probabilities (B, K, P, P, P), and the windows are blended: prob[k][v] = sum_i w_i(v) p_i[k](v) / sum_i w_i(v) over the windows i that cover

@@ -10,6 +10,8 @@ same names, constructor arguments and dict-in / dict-out protocol, operating on 
                               onto a Nyul-Udupa standard scale) before everything else, exact order statistics found on the device
     IntensityAugment          no counterpart in the reference's loaders: the batchgenerators / nnU-Net intensity transforms it inherits and leaves off
                               (noise, blur, brightness, contrast, simulated low resolution, gamma, mirror), applied after CenterIntensities; intensity_augment is its functional form
+    PatchSampler, train_patch no counterpart in the reference, which trains on CropResize'd crops only: nnU-Net's patch sampling — windows of the unscaled case, a share of
+                              each batch forced onto a random foreground voxel — cut on the device in place of CropResize, nothing read back (train_patch is train_sample's companion)
 
 The reference runs this chain on 16 CPU workers per loader (skimage resize + scipy map_coordinates of 128^3 volumes: seconds per
 sample); here a sample costs a handful of kernel launches.  One host synchronisation per sample remains: the crop cube's side depends
@@ -812,3 +814,84 @@ def train_sample(merge, patch_size, mask_index=None, transform=None, params=None
                              % (intensity.data_key, intensity.label_key, field, field + "_pancreas"))
         d = intensity(d, params=None if intensity_params is None else [intensity_params])
     return d[field], d[field + "_pancreas"]
+
+
+# ---- patch training: foreground-oversampled windows of the unscaled volume (csrc/patch.hip; DESIGN 3.19 holds the rule) -------------------------------
+class PatchSampler:
+    """nnU-Net's patch sampling on the device: a batch is made of windows of `patch` voxels (a side or (D, H, W)) of the unscaled volume, and the last
+    samples of every batch — sample j of B iff j >= floor(B (1 - oversample_foreground) + 0.5) — are forced to contain a uniformly chosen voxel of a
+    uniformly chosen class of `classes` that is present (None: 1 .. n_class - 1).  The rule is integer throughout (ops.patch_pick).
+    draw(batch_index, batch_size) -> (five words, forced): exactly one rng.randint(0, 2**32, size=5, dtype=np.uint64) per sample, forced or not, so the
+    stream does not depend on the data.  `rng`: a numpy RandomState (default: the global one).
+    __call__(image, label, n_class, requests) -> (image blocks (R, 1, Q, Q, Q), label blocks (R, 1, Q, Q, Q), picks int32 (R, 8)) with Q = patch +
+    2 margin per axis: index, pick and gather, four launches and one small upload, nothing synchronised or read back.  Outside the volume the image reads
+    `cval` and the label 0."""
+
+    def __init__(self, patch, oversample_foreground=0.33, classes=None, margin=0, rng=None, cval=-1024.0):
+        self.patch = volume._patch_sides(patch, "PatchSampler")
+        p = float(oversample_foreground)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("PatchSampler: oversample_foreground is a share in [0, 1], got %r" % (oversample_foreground,))
+        if not isinstance(margin, (int, np.integer)) or margin < 0:
+            raise ValueError("PatchSampler: margin is a non-negative integer, got %r" % (margin,))
+        if classes is not None:
+            classes = tuple(int(c) for c in classes)
+            if len(set(classes)) != len(classes) or any(not 0 <= c < volume.PATCH_MAX_CLASSES for c in classes):
+                raise ValueError("PatchSampler: classes are distinct integers in [0, %d), got %r" % (volume.PATCH_MAX_CLASSES, classes))
+        self.p, self.classes, self.margin, self.cval = p, classes, int(margin), float(cval)
+        self.rng = rng if rng is not None else np.random
+
+    def n_free(self, batch_size):
+        """the samples of a batch before the first forced one"""
+        return int(np.floor(int(batch_size) * (1.0 - self.p) + 0.5))
+
+    def draw(self, batch_index, batch_size):
+        if not 0 <= int(batch_index) < int(batch_size):
+            raise ValueError("PatchSampler.draw: sample %r of a batch of %r" % (batch_index, batch_size))
+        words = self.rng.randint(0, 2 ** 32, size=5, dtype=np.uint64)
+        return words, bool(int(batch_index) >= self.n_free(batch_size))
+
+    def __call__(self, image, label, n_class, requests):
+        _vol(image)
+        classes = tuple(range(1, int(n_class))) if self.classes is None else self.classes
+        words = torch.from_numpy(np.stack([np.asarray(w, dtype=np.uint64) for w, _ in requests]).astype(np.int64)).to(label.device, non_blocking=True)
+        forced = torch.tensor([int(bool(f)) for _, f in requests], dtype=torch.int32).to(label.device, non_blocking=True)
+        index = volume.patch_index(label, int(n_class))
+        picks = volume.patch_pick(label, index, classes, words, forced, self.patch)
+        lab = label if label.dtype == torch.float32 else label.float()
+        img_p, lab_p = volume.patch_gather((image, lab), (self.cval, 0.0), picks, self.patch, self.margin)
+        return img_p, lab_p, picks
+
+
+def train_patch(merge, patch_size, sampler, n_class, j, batch_size, mask_index=None, transform=None, params=None, field="venous", intensity=None,
+                intensity_params=None, request=None):
+    """train_sample's companion for patch training: sample `j` of a batch of `batch_size` cut from the UNSCALED case by `sampler` (a PatchSampler over
+    patch_size) in place of CropResize -> (image (1, 1, P, P, P), label (1, 1, P, P, P), picks int32 (1, 8)).  `request`: the sample's (words, forced)
+    instead of sampler.draw(j, batch_size).  `transform`: a MySpatialTransform(patch_size, random_crop=False): it resamples the gathered block of side
+    P + 2 margin about its centre down to P^3, so rotation and scale read real voxels of the margin, not cval (None: no augmentation; the sampler's
+    margin must then be 0).  Clip, CenterIntensities and `intensity` follow as in train_sample."""
+    patch = volume._patch_sides(patch_size, "train_patch")
+    if patch != sampler.patch:
+        raise ValueError("train_patch: the sampler cuts %s, the sample is %s" % (sampler.patch, patch))
+    if transform is None and sampler.margin:
+        raise ValueError("train_patch: a margin of %d needs a spatial transform that resamples the block down to the patch" % sampler.margin)
+    if transform is not None and (transform.random_crop or tuple(transform.patch_size) != patch):
+        raise ValueError("train_patch: the spatial transform must be built with random_crop=False and patch_size %s" % (patch,))
+    img = merge[..., 0].contiguous()
+    lab = merge[..., 1].contiguous()
+    if mask_index is not None:
+        lab = relabel(lab, mask_index)
+    if request is None:
+        request = sampler.draw(j, batch_size)
+    img_p, lab_p, picks = sampler(img, lab, n_class, [request])
+    d = {field: img_p, field + "_pancreas": lab_p}
+    if transform is not None:
+        d = transform(d, params=None if params is None else [params])
+    d = Clip([field], new_min=-200, new_max=400)(d)
+    d = CenterIntensities([field], subtrahend=100, divisor=300)(d)
+    if intensity is not None:
+        if (intensity.data_key, intensity.label_key) != (field, field + "_pancreas"):
+            raise ValueError("train_patch: the intensity transform reads %r / %r, the sample is under %r / %r"
+                             % (intensity.data_key, intensity.label_key, field, field + "_pancreas"))
+        d = intensity(d, params=None if intensity_params is None else [intensity_params])
+    return d[field], d[field + "_pancreas"], picks

@@ -88,7 +88,8 @@ def mask_index_of(args):
 class DeviceCaseLoader:
     """What BaseDataset + the transform stack + DataLoader deliver in the reference (main_source.py:186-243), with the transforms on the
     device: np.load of each case's merge array is the only host work; relabel / CropResize / MySpatialTransform / Clip / CenterIntensities
-    run as vs_data_* kernels (data_gpu.py).  Yields {IMG_KEY, LABEL_KEY: (B, 1, S, S, S) CUDA tensors}."""
+    run as vs_data_* kernels (data_gpu.py).  Yields {IMG_KEY, LABEL_KEY: (B, 1, S, S, S) CUDA tensors}.  With --train_patches a training loader cuts
+    S^3 windows of the unscaled case (data_gpu.PatchSampler / train_patch) in place of CropResize; validation loaders never do."""
 
     def __init__(self, names, root, args, batch_size, train, shuffle, rank=0, world=1, seed=0):
         from . import data_gpu
@@ -99,12 +100,15 @@ class DeviceCaseLoader:
         self.patch, self.mask_index, self.epoch, self.seed = (args.size,) * 3, mask_index_of(args), 0, seed + rank
         self.drop_last = train
         self.shift = int(getattr(args, "shift", 0)) if train else 0           # main_target.py:204 (training crops only; validation: CropResize default)
+        # --train_patches: a training loader cuts windows of the unscaled case in place of CropResize (self.sampler, below).  The sampler has then already
+        # chosen where the patch lies, and the spatial transform resamples the gathered block about its centre: random_crop=False
+        patches = bool(train and getattr(args, "train_patches", False))
         self.transform = None
         if train and not getattr(args, "no_aug", False):                       # main_source.py:195-205
             p_el = float(getattr(args, "aug_elastic", 0.0) or 0.0)            # --aug_elastic: the stage main_source.py:198 leaves one flag away from on
             elastic = {"noise": "philox", "seed": seed + 1000 * rank} if p_el > 0 else {}
             self.transform = data_gpu.MySpatialTransform(
-                self.patch, [d // 2 - 5 for d in self.patch], random_crop=True, scale=(0.85, 1.15), do_elastic_deform=p_el > 0, alpha=(0, 500),
+                self.patch, [d // 2 - 5 for d in self.patch], random_crop=not patches, scale=(0.85, 1.15), do_elastic_deform=p_el > 0, alpha=(0, 500),
                 do_rotation=True, sigma=(10, 30.), angle_x=(-0.2, 0.2), angle_y=(-0.2, 0.2), angle_z=(-0.2, 0.2), border_mode_data="constant",
                 border_cval_data=-1024, data_key=IMG_KEY, p_el_per_sample=p_el, label_key=LABEL_KEY, p_scale_per_sample=1, p_rot_per_sample=1,
                 rng=np.random.RandomState(seed + 1000 * rank), **elastic)
@@ -121,6 +125,12 @@ class DeviceCaseLoader:
             from . import evaluation
             self.standardize = data_gpu.IntensityStandardizer(tuple(args.standardize), target=evaluation.INTENSITY_CLIP,
                                                               above=getattr(args, "standardize_above", None))
+        self.sampler = None
+        if patches:
+            # the sampler has a generator of its own, so the spatial and intensity draws keep their streams; without augmentation nothing resamples a margin away
+            self.n_class = n_class_of(args)
+            self.sampler = data_gpu.PatchSampler(self.patch, float(getattr(args, "patch_fg", 0.33)), rng=np.random.RandomState(seed + 1000 * rank + 900),
+                                                 margin=int(getattr(args, "patch_margin", 16)) if self.transform is not None else 0)
         self._dg = data_gpu
 
     def _load(self, name):
@@ -148,10 +158,14 @@ class DeviceCaseLoader:
             np.random.RandomState(self.seed + self.epoch).shuffle(order)
         for b in range(len(self)):
             imgs, labs = [], []
-            for i in order[b * self.bs:(b + 1) * self.bs]:
+            for j, i in enumerate(order[b * self.bs:(b + 1) * self.bs]):
                 merge = self._load(self.names[i])
                 extra = {} if self.intensity is None else {"intensity": self.intensity}
-                img, lab = self._dg.train_sample(merge, self.patch, self.mask_index, self.transform, field=IMG_KEY, shift=self.shift, **extra)
+                if self.sampler is not None:
+                    img, lab, _ = self._dg.train_patch(merge, self.patch, self.sampler, self.n_class, j, self.bs, self.mask_index, self.transform, field=IMG_KEY,
+                                                       **extra)
+                else:
+                    img, lab = self._dg.train_sample(merge, self.patch, self.mask_index, self.transform, field=IMG_KEY, shift=self.shift, **extra)
                 imgs.append(img); labs.append(lab)
             yield {IMG_KEY: torch.cat(imgs), LABEL_KEY: torch.cat(labs)}
 
@@ -998,6 +1012,17 @@ def _probability(text):
     return v
 
 
+def _margin(text):
+    import argparse
+    try:
+        v = int(text)
+    except ValueError:
+        v = -1
+    if v < 0:
+        raise argparse.ArgumentTypeError("a non-negative number of voxels, got %r" % text)
+    return v
+
+
 def _percentile_pair(text):
     import argparse
     try:
@@ -1021,6 +1046,10 @@ def check_aug_flags(parser, a):
         parser.error("--standardize reads the percentiles of merge.npy cases: it needs --real_data")
     if getattr(a, "standardize_above", None) is not None and getattr(a, "standardize", None) is None:
         parser.error("--standardize_above selects the voxels --standardize reads: it needs --standardize")
+    if getattr(a, "train_patches", False) and not getattr(a, "real_data", False):
+        parser.error("--train_patches cuts its windows from merge.npy cases: it needs --real_data")
+    if getattr(a, "train_patches", False) and len(str(a.pan_index).split(",")) + 1 > 8:
+        parser.error("--train_patches indexes at most 8 classes, the background included")
     return a
 
 
@@ -1044,6 +1073,13 @@ def add_native_flags(parser):
                    "Hounsfield; training, validation and pseudo-label loaders alike; off: the reference's setting")
     g.add_argument("--standardize_above", type=float, default=None, metavar="T", help="with --standardize: the percentiles are those of the voxels above T "
                    "(strictly), e.g. to leave the air around the body out")
+    g.add_argument("--train_patches", action="store_true", help="with --real_data: patch training — every training sample is a --size window of the UNSCALED "
+                   "case in place of the label-centred, rescaled crop of CropResize (nnU-Net's loader: the windows --val_whole_volume predicts on), the "
+                   "last samples of each batch forced onto a random foreground voxel, cut on the device (data_gpu.PatchSampler); validation is unchanged")
+    g.add_argument("--patch_fg", type=_probability, default=0.33, metavar="P", help="with --train_patches: the share of a batch forced to contain foreground — "
+                   "sample j of B iff j >= floor(B (1 - P) + 0.5) (nnU-Net: 0.33)")
+    g.add_argument("--patch_margin", type=_margin, default=16, metavar="M", help="with --train_patches: voxels cut around each window for rotation and scale to "
+                   "read in place of the border value; 0 under --no_aug")
     g.add_argument("--latent_noise", default="torch", choices=["torch", "philox"], help="vae_train / embed_train / refine_vae: where the VAE's latent noise "
                    "comes from — torch: torch.randn per call, the step launched eagerly (the reference's draw); philox: a stated Philox4x32-10 stream per "
                    "rank (ops.LatentStream, seed 1000 rank + 700) drawn inside the forward launch from a counter in device memory, so the step is captured "

@@ -21,6 +21,8 @@ from . import _lib
 from ._lib import (VS_BF16, VS_CONV_K2S2, VS_CONV_K3, VS_CONV_UP, VS_F16, VS_F32, VS_PACK_ROWS_D0, VS_PACK_ROWS_D1_FLIP,
                    VS_PACK_SCATTER_D1, _contig, _p, _require_cuda, _stream, check, lib)
 from .volume import *  # noqa: F401,F403
+from .volume import (PATCH_CHUNK, PATCH_LABEL_DTYPES, PATCH_MAX_CLASSES, PATCH_MAX_SOURCES, patch_gather, patch_index,  # noqa: F401  (volume.PATCH_NAMES)
+                     patch_pick)
 
 _DT_TORCH = {VS_F32: torch.float32, VS_BF16: torch.bfloat16, VS_F16: torch.float16}
 _DT_VS = {v: k for k, v in _DT_TORCH.items()}

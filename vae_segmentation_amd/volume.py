@@ -904,3 +904,125 @@ def intensity_map(x, src, dst, extrapolate="linear", out=None):
     check(lib.vs_intensity_map(x.data_ptr(), src.data_ptr(), dst.data_ptr(), nl, int(extrapolate == "clamp"), out.data_ptr(), planes, d, h, w, _stream()),
           "intensity_map")
     return out
+
+
+# ---- training patches: foreground-oversampled windows cut on the device (csrc/patch.hip) ------------------------------------------------
+# __all__ above is the list of names that moved here from ops.py, which tests/test_host.py pins; this section's public names are PATCH_NAMES, and ops
+# imports them by name.
+PATCH_NAMES = ("PATCH_CHUNK", "PATCH_MAX_CLASSES", "PATCH_MAX_SOURCES", "PATCH_LABEL_DTYPES", "patch_index", "patch_pick", "patch_gather")
+PATCH_CHUNK = int(lib.vs_patch_chunk())     # VS_PATCH_CHUNK: the voxels of the linear index one row of patch_index's table stands for
+PATCH_MAX_CLASSES = 8
+PATCH_MAX_SOURCES = 4
+PATCH_LABEL_DTYPES = {torch.float32: _lib.VS_PATCH_F32, torch.uint8: _lib.VS_PATCH_U8}
+
+
+def _patch_label(label, what):
+    if not isinstance(label, torch.Tensor) or label.dtype not in PATCH_LABEL_DTYPES:
+        raise TypeError("%s: label is a float32 or uint8 tensor (D, H, W), got %s" % (what, getattr(label, "dtype", type(label))))
+    if label.dim() != 3 or label.numel() == 0 or label.numel() >= 2 ** 31:
+        raise ValueError("%s: label is a non-empty (D, H, W) volume of fewer than 2^31 voxels, got shape %s" % (what, tuple(label.shape)))
+    if not label.is_contiguous():
+        raise ValueError("%s: label must be contiguous" % what)
+    _require_cuda(label)
+    return tuple(int(v) for v in label.shape)
+
+
+def _patch_n_class(n_class, what):
+    if not isinstance(n_class, _numbers.Integral) or not 1 <= n_class <= PATCH_MAX_CLASSES:
+        raise ValueError("%s: n_class is an integer in [1, %d], got %r" % (what, PATCH_MAX_CLASSES, n_class))
+    return int(n_class)
+
+
+def _patch_sides(patch, what):
+    try:
+        sides = tuple(int(p) for p in ((patch,) * 3 if isinstance(patch, _numbers.Integral) else patch))
+        exact = isinstance(patch, _numbers.Integral) or all(s == p for s, p in zip(sides, patch))
+    except (TypeError, ValueError):
+        sides, exact = (), False
+    if not exact or len(sides) != 3 or min(sides) < 1:
+        raise ValueError("%s: patch is a positive side or three of them (D, H, W), got %r" % (what, patch))
+    return sides
+
+
+def patch_index(label, n_class):
+    """The position index of a label (D, H, W), float32 or uint8 on the device: int32 (n_chunks + 1, n_class), row j = the voxels of each class in the
+    first j chunks of PATCH_CHUNK consecutive voxels of the linear index (z H + y) W + x, the last row the totals.  A voxel belongs to class k iff its
+    value is the integer k in [0, n_class), n_class <= 8; NaN, fractions and larger values are counted nowhere.  Two launches, no atomics, nothing
+    synchronised or read back (vs_patch_index)."""
+    d, h, w = _patch_label(label, "patch_index")
+    nc = _patch_n_class(n_class, "patch_index")
+    table = torch.empty(((d * h * w + PATCH_CHUNK - 1) // PATCH_CHUNK + 1, nc), dtype=torch.int32, device=label.device)
+    assert table.numel() * 4 == lib.vs_patch_index_bytes(d, h, w, nc)
+    check(lib.vs_patch_index(label.data_ptr(), PATCH_LABEL_DTYPES[label.dtype], d, h, w, nc, table.data_ptr(), _stream()), "patch_index")
+    return table
+
+
+def patch_pick(label, index, classes, words, forced, patch):
+    """The origins of R patch requests: words uint32-valued (R, 5) = (wc, wv, wz, wy, wx) as an int64 or int32 tensor on the device (int64
+    values in [0, 2^32); int32 is taken as the same 32 bits), forced int32 (R,), classes the sampler's class list (distinct integers in [0, n_class), any
+    order), patch a side or (D, H, W) sides, index = patch_index(label, n_class).  A forced request whose list has a class present takes class
+    present[(wc mc) >> 32], its voxel of rank (wv n_k) >> 32 in ascending linear index, and the origin min(max(lb, v - P // 2), ub) per axis; any other
+    request the free origin lb + ((w_axis (ub - lb + 1)) >> 32).  -> picks int32 (R, 8) = (oz, oy, ox, class or -1, vz, vy, vx or -1, 0), on the device.
+    One launch of a wave per request; nothing synchronised or read back (vs_patch_pick)."""
+    d, h, w = _patch_label(label, "patch_pick")
+    sides = _patch_sides(patch, "patch_pick")
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 2 or not index.is_contiguous() or index.device != label.device or \
+            index.shape[0] != (d * h * w + PATCH_CHUNK - 1) // PATCH_CHUNK + 1 or not 1 <= index.shape[1] <= PATCH_MAX_CLASSES:
+        raise ValueError("patch_pick: index is patch_index(label, n_class), a contiguous int32 (n_chunks + 1, n_class) tensor on the label's device")
+    nc = int(index.shape[1])
+    try:
+        cls = [int(c) for c in classes]
+        exact = all(c == k for c, k in zip(cls, classes))
+    except (TypeError, ValueError):
+        cls, exact = [], False
+    if not exact or len(set(cls)) != len(cls) or any(c < 0 or c >= nc for c in cls):
+        raise ValueError("patch_pick: classes are distinct integers in [0, %d), got %r" % (nc, classes))
+    cls.sort()
+    if not isinstance(words, torch.Tensor) or words.dtype not in (torch.int64, torch.int32) or words.dim() != 2 or words.shape[1] != 5 or words.shape[0] < 1:
+        raise ValueError("patch_pick: words is an int64 or int32 tensor (R, 5) with R >= 1")
+    if not isinstance(forced, torch.Tensor) or forced.dtype != torch.int32 or tuple(forced.shape) != (words.shape[0],) or not forced.is_contiguous():
+        raise ValueError("patch_pick: forced is a contiguous int32 tensor (R,) for words (R, 5)")
+    _require_cuda(words, forced)
+    w32 = _contig(words.to(torch.int32)) if words.dtype == torch.int64 else _contig(words)        # int64 -> int32 keeps the low 32 bits
+    r = int(w32.shape[0])
+    picks = torch.empty((r, 8), dtype=torch.int32, device=label.device)
+    check(lib.vs_patch_pick(label.data_ptr(), PATCH_LABEL_DTYPES[label.dtype], index.data_ptr(), nc, len(cls), sum(c << (3 * i) for i, c in enumerate(cls)),
+                            w32.data_ptr(), forced.data_ptr(), r, d, h, w, sides[0], sides[1], sides[2], picks.data_ptr(), _stream()), "patch_pick")
+    return picks
+
+
+def patch_gather(sources, cvals, picks, patch, margin=0):
+    """The blocks of R requests cut from 1 to 4 float32 volumes of one shape (D, H, W): block i of source s is rows [o - margin, o - margin + Q) per axis,
+    Q = patch + 2 margin, o = picks[i, :3] read on the device (any integers); positions outside the volume read cvals[s].  -> a tuple of (R, 1, Qd, Qh, Qw)
+    tensors, one per source, views of one (n_src, R, Qd, Qh, Qw) block.  One launch, nothing synchronised or read back (vs_patch_gather)."""
+    try:
+        srcs = list(sources)
+        cv = [float(c) for c in cvals]
+    except (TypeError, ValueError):
+        raise ValueError("patch_gather: sources is a sequence of volumes and cvals one number for each") from None
+    if not 1 <= len(srcs) <= PATCH_MAX_SOURCES or len(cv) != len(srcs) or any(math.isnan(c) for c in cv):
+        raise ValueError("patch_gather: 1 to %d sources and one cval (not NaN) for each, got %d and %r" % (PATCH_MAX_SOURCES, len(srcs), cvals))
+    for t in srcs:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError("patch_gather: a source is a float32 tensor (D, H, W), got %s" % getattr(t, "dtype", type(t)))
+        if t.dim() != 3 or t.numel() == 0 or t.numel() >= 2 ** 31 or t.shape != srcs[0].shape or t.device != srcs[0].device:
+            raise ValueError("patch_gather: the sources are non-empty (D, H, W) volumes of one shape on one device, got %s" % [tuple(s.shape) for s in srcs])
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError("patch_gather: a source must be contiguous and 16-byte aligned")
+    _require_cuda(*srcs)
+    sides = _patch_sides(patch, "patch_gather")
+    if not isinstance(margin, _numbers.Integral) or margin < 0:
+        raise ValueError("patch_gather: margin is a non-negative integer, got %r" % (margin,))
+    if not isinstance(picks, torch.Tensor) or picks.dtype != torch.int32 or picks.dim() != 2 or picks.shape[1] != 8 or picks.shape[0] < 1 or \
+            not picks.is_contiguous() or picks.device != srcs[0].device or picks.data_ptr() % 16:
+        raise ValueError("patch_gather: picks is patch_pick's contiguous int32 (R, 8) tensor on the sources' device")
+    r, q = int(picks.shape[0]), tuple(s + 2 * int(margin) for s in sides)
+    if q[0] * q[1] * q[2] >= 2 ** 31:
+        raise ValueError("patch_gather: a block of 2^31 voxels or more, %s" % (q,))
+    out = torch.empty((len(srcs), r) + q, dtype=torch.float32, device=srcs[0].device)
+    ptrs = [t.data_ptr() for t in srcs] + [None] * (PATCH_MAX_SOURCES - len(srcs))
+    cv = cv + [0.0] * (PATCH_MAX_SOURCES - len(cv))
+    d, h, w = (int(v) for v in srcs[0].shape)
+    check(lib.vs_patch_gather(ptrs[0], ptrs[1], ptrs[2], ptrs[3], cv[0], cv[1], cv[2], cv[3], len(srcs), picks.data_ptr(), r, d, h, w, sides[0], sides[1],
+                              sides[2], int(margin), out.data_ptr(), _stream()), "patch_gather")
+    return tuple(out[s].unsqueeze(1) for s in range(len(srcs)))
