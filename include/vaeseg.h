@@ -922,6 +922,30 @@ int vs_dice_loss_multi_labels_fwd(const float* s, const float* const* t, const f
 int vs_dice_loss_multi_labels_bwd(const float* s, const float* const* t, const float* const* labels, const float* w, int k,
                                   const double* scratch, const float* gout, float* gs, float* const* gt, int batch, int channels,
                                   long long voxels, int bot, int top, float eps, void* stream);
+/* Compound segmentation loss of planar fp32 probabilities p [B][C][V] (1 <= C <= 8) against a LABEL volume [B][V] (csrc/segloss.hip):
+ * soft Dice over channels [bot, top) plus a class-weighted, optionally focal, voxel-wise cross-entropy.  The rule is this library's own; the reference has
+ * no counterpart.
+ *   A voxel is VALID iff label >= 0 and label < C (fp32 compares: NaN is not), its class is l = (int)label; every other voxel (-1 padding, 255, NaN) is
+ *   IGNORED: it adds to no sum — S included — and its gradient is 0 in every channel.  vs_dice_loss_multi_labels_* differs on purpose: there an
+ *   unmatched label still counts in S.
+ *   Over the valid voxels of a plane, in fp64:  S[b][c] = sum p_c,  I[b][c] = sum_{l=c} p_c,  T[b][c] = #{l = c}.
+ *   batch_dice == 0:  dice = mean_b mean_{c in [bot,top)} 2 I[b][c] / (S[b][c] + T[b][c] + eps)
+ *   batch_dice != 0:  dice = mean_c 2 sum_b I / (sum_b S + sum_b T + eps)                      dice_term = 1 - dice
+ *   f_v = -(1 - p_l)^gamma * max(ln p_l, -100)  (fp64 ln and pow; gamma == 0: plain cross-entropy);  ce_term = sum_v w[l_v] f_v / sum_v w[l_v], 0 when
+ *   the denominator is 0.   terms = (dice_term, ce_term), each rounded to fp32 once;  final = (dice_w * dice_term) + ce_w * ce_term  (fp32, that order).
+ * class_w: a HOST array of 8 floats >= 0 (entries >= C unused), copied into the kernel arguments.  scratch: vs_seg_loss_scratch_doubles() doubles, contents
+ * undefined on entry; the forward (two launches: per-block partials, a one-workgroup finish that adds them in a fixed order) leaves S, I, T, sum w f, sum w
+ * in its first batch * (3 * channels + 2) entries, which the backward (one launch) reads.  The backward writes every plane of
+ *   gp[b][c][v] = gout[0] * (dice_w * d dice_term / d p + [c == l_v] * ce_w * d ce_term / d p_l)
+ * — the exact derivative of the rule above (where the clamp is active the ln factor's derivative is 0), both parts formed in fp64 and rounded to fp32 once;
+ * gout is read on the device.  No atomics, no memset, nothing allocated, synchronised or read back: the same bits eagerly, under graph replay and in both
+ * builds.  V not a multiple of 4 or a pointer not 16-byte aligned: VS_EALIGN; a null pointer, C outside [1, 8], bot / top out of order, a negative
+ * (or NaN) weight, gamma or eps: VS_EINVAL; batch > 64 or V >= 2^31: VS_ESHAPE; all answered on the host before any launch. */
+size_t vs_seg_loss_scratch_doubles(int batch, int channels);
+int vs_seg_loss_fwd(const float* p, const float* label, const float* class_w, double* scratch, float* terms, float* final_out, int batch, int channels,
+                    long long voxels, int bot, int top, float eps, float dice_w, float ce_w, int batch_dice, float gamma, void* stream);
+int vs_seg_loss_bwd(const float* p, const float* label, const float* class_w, const double* scratch, const float* gout, float* gp, int batch, int channels,
+                    long long voxels, int bot, int top, float eps, float dice_w, float ce_w, int batch_dice, float gamma, void* stream);
 /* nn.BCELoss() mean reduction (utils/evaluation.py:29-39), log clamped at -100 like torch */
 int vs_bce_fwd(const float* p, const float* t, float* out, double* scratch, long long count, void* stream);
 int vs_bce_bwd(const float* p, const float* t, const float* gout, float* gp, long long count, void* stream);

@@ -70,7 +70,7 @@ def parse(argv=None):
     p.add_argument("--generate_bounding_boxes", action="store_true", help="accepted (main_target.py:80,169: asserted, never used)")
     p.add_argument("--shift", type=int, default=0, help="CropResize(shift=...) of the training crops (main_target.py:81,204)")
     driver.add_native_flags(p)
-    a = driver.check_aug_flags(p, p.parse_args(argv))
+    a = driver.check_aug_flags(p, p.parse_args(argv), seg_loss_methods=())       # the compound loss belongs to main_source.py's seg_train / joint_train
     driver.check_target_flags(a)
     return a
 

@@ -745,13 +745,15 @@ def run(args, side="source"):
         else:
             use_graph = False
 
+    seg_loss = seg_loss_of(args)                                            # --seg_loss dice_ce: ops.seg_loss's arguments; None: the reference's Dice
+
     def loss_fn():
         if method == "vae_train":
             return T.vae_train_losses(model, lab_buf, scale=0.35, noise=latent, eps=eps, n_class=nc)
         if method == "seg_train":
-            return T.seg_train_losses(model, img_buf, lab_buf, eps=eps, n_class=nc)
+            return T.seg_train_losses(model, img_buf, lab_buf, eps=eps, n_class=nc, loss=seg_loss)
         if method == "joint_train":
-            return T.joint_train_losses(model, img_buf, lab_buf, lambda_vae=lambda_vae, eps=eps, n_class=nc)
+            return T.joint_train_losses(model, img_buf, lab_buf, lambda_vae=lambda_vae, eps=eps, n_class=nc, loss=seg_loss)
         if method == "sep_joint_train":
             return T.sep_joint_train_losses(model, teacher, img_buf, lab_buf, eps=eps, n_class=nc)
         if method == "embed_train":
@@ -1034,8 +1036,61 @@ def _percentile_pair(text):
     return lo, hi
 
 
-def check_aug_flags(parser, a):
-    """--aug_elastic and --aug_intensity act on the augmented training samples: with --no_aug there are none; --standardize reads real cases"""
+def _nonnegative(text):
+    import argparse
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 <= v < float("inf"):
+        raise argparse.ArgumentTypeError("a finite number >= 0, got %r" % text)
+    return v
+
+
+def _class_weights(text):
+    import argparse
+    try:
+        ws = [_nonnegative(t) for t in text.split(",")]
+    except argparse.ArgumentTypeError:
+        raise argparse.ArgumentTypeError("comma-separated finite numbers >= 0, got %r" % text)
+    return ws
+
+
+SEG_LOSS_METHODS = ("seg_train", "joint_train")
+
+
+def check_seg_loss_flags(parser, a, methods=SEG_LOSS_METHODS):
+    """--seg_loss and the flags that shape the compound loss belong to the methods whose loss is a Dice against the label: seg_train and joint_train
+    of main_source.py (main_target.py passes methods=())"""
+    given = [n for n, default in (("seg_loss", "dice"), ("ce_weight", 1.0), ("batch_dice", False), ("focal_gamma", 0.0), ("class_weights", None))
+             if getattr(a, n, default) != default]
+    if not given:
+        return a
+    if a.method not in methods:
+        parser.error("%s: the compound segmentation loss belongs to --method seg_train and joint_train of main_source.py, not to --method %s"
+                     % (", ".join("--" + n for n in given), a.method))
+    if a.seg_loss != "dice_ce":
+        parser.error("%s shape(s) the compound loss: add --seg_loss dice_ce" % ", ".join("--" + n for n in given))
+    nc = n_class_of(a)
+    if nc > 8:
+        parser.error("--seg_loss dice_ce handles at most 8 classes, the background included")
+    if a.class_weights is not None and len(a.class_weights) != nc:
+        parser.error("--class_weights takes exactly %d numbers (one per class, the background included), got %d" % (nc, len(a.class_weights)))
+    return a
+
+
+def seg_loss_of(args):
+    """the `loss` argument of train.seg_train_losses / joint_train_losses from the flags; None for --seg_loss dice (the default): the reference's Dice"""
+    if getattr(args, "seg_loss", "dice") != "dice_ce":
+        return None
+    return {"dice_weight": 1.0, "ce_weight": args.ce_weight, "batch_dice": bool(args.batch_dice), "class_weights": args.class_weights,
+            "gamma": args.focal_gamma}
+
+
+def check_aug_flags(parser, a, seg_loss_methods=SEG_LOSS_METHODS):
+    """--aug_elastic and --aug_intensity act on the augmented training samples: with --no_aug there are none; --standardize reads real cases;
+    the compound-loss flags belong to seg_loss_methods (check_seg_loss_flags)"""
+    check_seg_loss_flags(parser, a, seg_loss_methods)
     if getattr(a, "aug_elastic", 0.0) > 0 and getattr(a, "no_aug", False):
         parser.error("--aug_elastic deforms the augmented training samples: it cannot be combined with --no_aug")
     if getattr(a, "aug_intensity", False) and getattr(a, "no_aug", False):
@@ -1080,6 +1135,16 @@ def add_native_flags(parser):
                    "sample j of B iff j >= floor(B (1 - P) + 0.5) (nnU-Net: 0.33)")
     g.add_argument("--patch_margin", type=_margin, default=16, metavar="M", help="with --train_patches: voxels cut around each window for rotation and scale to "
                    "read in place of the border value; 0 under --no_aug")
+    g.add_argument("--seg_loss", default="dice", choices=["dice", "dice_ce"], help="seg_train / joint_train: the loss against the label — dice: the "
+                   "reference's per-sample soft Dice, whose gradient is zero on a sample without foreground; dice_ce: Dice plus a voxel-wise cross-entropy, "
+                   "fused on the device (ops.seg_loss, DESIGN 3.20)")
+    g.add_argument("--ce_weight", type=_nonnegative, default=1.0, metavar="W", help="with --seg_loss dice_ce: the weight of the cross-entropy term")
+    g.add_argument("--batch_dice", action="store_true", help="with --seg_loss dice_ce: pool the Dice sums over the rank's batch (nnU-Net's batch Dice), so "
+                   "a sample without foreground still receives a Dice gradient")
+    g.add_argument("--focal_gamma", type=_nonnegative, default=0.0, metavar="G", help="with --seg_loss dice_ce: the focal exponent of the cross-entropy, "
+                   "-(1 - p)^G ln p; 0 = plain cross-entropy")
+    g.add_argument("--class_weights", type=_class_weights, default=None, metavar="W0,W1,...", help="with --seg_loss dice_ce: one cross-entropy weight "
+                   ">= 0 per class, the background first — exactly n_class numbers (torch's weighted mean); default all 1")
     g.add_argument("--latent_noise", default="torch", choices=["torch", "philox"], help="vae_train / embed_train / refine_vae: where the VAE's latent noise "
                    "comes from — torch: torch.randn per call, the step launched eagerly (the reference's draw); philox: a stated Philox4x32-10 stream per "
                    "rank (ops.LatentStream, seed 1000 rank + 700) drawn inside the forward launch from a counter in device memory, so the step is captured "

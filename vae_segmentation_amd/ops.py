@@ -2377,6 +2377,67 @@ def dice_loss_sum(source, targets_and_weights, botindex=0, topindex=2, eps=1e-6)
     return final, list(terms.unbind(0))
 
 
+class SegLoss(torch.autograd.Function):
+    """final = dice_weight * (1 - Dice) + ce_weight * CE of planar fp32 probabilities p (B, C, ...) against a LABEL volume (B, 1, ...): soft Dice over
+    channels [bot, top), per sample or pooled over the batch, plus a class-weighted, optionally focal, voxel-wise cross-entropy (csrc/segloss.hip,
+    DESIGN 3.20) — TWO forward launches and ONE backward launch, p and the label read once for every term, no atomics.  A label outside [0, C) — the
+    -1 of the quad padding, 255, NaN — is ignored by every term.  -> (final, terms[2] = (dice_term, ce_term)); terms are not differentiable, and the
+    only gradient is p's."""
+
+    @staticmethod
+    def forward(ctx, p, label, bot, top, eps, dice_weight, ce_weight, batch_dice, class_weights, gamma):
+        _require_cuda(p, label)
+        p, label = _contig(p.float()), _contig(label.float())
+        b, c = p.shape[0], p.shape[1]
+        voxels = p.numel() // (b * c)
+        if label.numel() != b * voxels:
+            raise ValueError("label target: expected %d x %d labels, got %s" % (b, voxels, tuple(label.shape)))
+        ctx.shape = tuple(p.shape)
+        p, label = _pad_quads(p, b, c, 0.0), _pad_quads(label, b, 1, -1.0)
+        voxels = p.numel() // (b * c)
+        scratch = torch.empty(max(1, lib.vs_seg_loss_scratch_doubles(b, c)), dtype=torch.float64, device=p.device)
+        terms = torch.empty(2, dtype=torch.float32, device=p.device)
+        final = torch.empty((), dtype=torch.float32, device=p.device)
+        cfg = (b, c, voxels, int(bot), int(top), float(eps), float(dice_weight), float(ce_weight), 1 if batch_dice else 0, float(gamma))
+        wp = (_ctypes.c_float * 8)(*([float(w) for w in class_weights] + [0.0] * 8)[:8])
+        check(lib.vs_seg_loss_fwd(p.data_ptr(), label.data_ptr(), _ctypes.addressof(wp), scratch.data_ptr(), terms.data_ptr(), final.data_ptr(), *cfg,
+                                  _stream()), "seg_loss_fwd")
+        ctx.save_for_backward(p, label, scratch)
+        ctx.cfg, ctx.class_weights = cfg, [float(w) for w in class_weights]
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)      # no zero-fill launch for the terms' gradient
+        return final, terms
+
+    @staticmethod
+    def backward(ctx, g, _gterms):
+        p, label, scratch = ctx.saved_tensors
+        gp = None
+        if g is not None and ctx.needs_input_grad[0]:
+            g = _contig(g.float())
+            gp = torch.empty_like(p)
+            wp = (_ctypes.c_float * 8)(*(ctx.class_weights + [0.0] * 8)[:8])
+            check(lib.vs_seg_loss_bwd(p.data_ptr(), label.data_ptr(), _ctypes.addressof(wp), scratch.data_ptr(), g.data_ptr(), gp.data_ptr(), *ctx.cfg,
+                                      _stream()), "seg_loss_bwd")
+        return (_unpad_quads(gp, ctx.shape),) + (None,) * 9
+
+
+def seg_loss(p, target, dice_weight=1.0, ce_weight=1.0, batch_dice=False, class_weights=None, gamma=0.0, botindex=0, topindex=2, eps=1e-6):
+    """dice_weight * (1 - Dice(p, target)) + ce_weight * CE(p, target) -> (final, (dice_term, ce_term)) for the softmax output p (B, C, ...), 1 <= C <= 8,
+    and an ops.LabelTarget; the rule is SegLoss's (DESIGN 3.20).  Channel selection as dice_loss_sum; batch_dice pools the Dice sums over the batch;
+    class_weights: C numbers >= 0 (default all 1) weighting the cross-entropy as torch's weighted mean does; gamma >= 0: the focal exponent."""
+    if not isinstance(target, LabelTarget):
+        raise TypeError("seg_loss takes its target as an ops.LabelTarget (a label volume); for a tensor target use dice_loss_sum")
+    channels = p.shape[1]
+    bot, top = (botindex, min(topindex, channels)) if channels > 1 else (0, 1)
+    if class_weights is None:
+        class_weights = [1.0] * channels
+    class_weights = [float(w) for w in class_weights]
+    if len(class_weights) != channels:
+        raise ValueError("seg_loss: %d class weights for %d channels" % (len(class_weights), channels))
+    final, terms = SegLoss.apply(p, target.label, bot, top, eps, dice_weight, ce_weight, bool(batch_dice), class_weights, gamma)
+    return final, tuple(terms.unbind(0))
+
+
 class BCE(torch.autograd.Function):
     """nn.BCELoss() (mean) — utils/evaluation.py:29-39."""
 

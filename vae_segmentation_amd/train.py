@@ -31,8 +31,25 @@ def _gt(batch, label, n_class):
     return batch["gt"]
 
 
-def joint_train_losses(joint, img, label, lambda_vae=0.1, eps=EPS_MAIN_SOURCE, n_class=2):
+def _seg_loss_args(loss):
+    """`loss` of seg_train_losses / joint_train_losses: a dict or namedtuple of ops.seg_loss's keyword arguments (dice_weight, ce_weight, batch_dice,
+    class_weights, gamma) -> the dict"""
+    kw = dict(loss._asdict() if hasattr(loss, "_asdict") else loss)
+    unknown = set(kw) - {"dice_weight", "ce_weight", "batch_dice", "class_weights", "gamma"}
+    if unknown:
+        raise TypeError("loss: unknown argument(s) %s" % ", ".join(sorted(unknown)))
+    return kw
+
+
+def joint_train_losses(joint, img, label, lambda_vae=0.1, eps=EPS_MAIN_SOURCE, n_class=2, loss=None):
     batch = {"img": img}
+    if loss is not None:
+        # the compound loss (ops.seg_loss, DESIGN 3.20) against the label volume in place of the ground-truth Dice term; the VAE term stays a Dice
+        batch["label"] = label
+        batch = joint(batch, "img", "pred", "recon")
+        vae_part, (recon_loss,) = ops.dice_loss_sum(batch["pred"], [(batch["recon"], lambda_vae)], botindex=1, topindex=n_class, eps=eps)
+        seg_part, (dsc_loss, ce_loss) = ops.seg_loss(batch["pred"], ops.LabelTarget(label), botindex=1, topindex=n_class, eps=eps, **_seg_loss_args(loss))
+        return vae_part + seg_part, {"recon_loss": recon_loss, "dice_loss": dsc_loss, "ce_loss": ce_loss, "batch": batch}
     gt = _gt(batch, label, n_class)
     batch = joint(batch, "img", "pred", "recon")
     # final = lambda_vae * (1 - avg_dsc(pred, recon)) + (1 - avg_dsc(pred, gt))        (main_source.py:469-471), one launch each way
@@ -41,8 +58,13 @@ def joint_train_losses(joint, img, label, lambda_vae=0.1, eps=EPS_MAIN_SOURCE, n
     return final, {"recon_loss": recon_loss, "dice_loss": dsc_loss, "batch": batch}
 
 
-def seg_train_losses(seg, img, label, eps=EPS_MAIN_SOURCE, n_class=2):
+def seg_train_losses(seg, img, label, eps=EPS_MAIN_SOURCE, n_class=2, loss=None):
     batch = {"img": img}
+    if loss is not None:
+        batch["label"] = label
+        batch = seg(batch, "img", "pred")
+        final, (dsc_loss, ce_loss) = ops.seg_loss(batch["pred"], ops.LabelTarget(label), botindex=1, topindex=n_class, eps=eps, **_seg_loss_args(loss))
+        return final, {"dice_loss": dsc_loss, "ce_loss": ce_loss, "batch": batch}
     gt = _gt(batch, label, n_class)
     batch = seg(batch, "img", "pred")
     final, (dsc_loss,) = ops.dice_loss_sum(batch["pred"], [(gt, 1.0)], botindex=1, topindex=n_class, eps=eps)
