@@ -4,6 +4,8 @@ host by tests/test_host_exact.py).  CPU only, fp64, no import of the package.
 Why it works: every kernel multiplies stored operands and accumulates in fp32.  Small integers are exact in bf16, fp16 and fp32 (and have a single non-zero
 limb in the three-limb fp32 kernels); while every partial sum of an output stays below 2^24 in magnitude, fp32 accumulation is exact in ANY order — any
 tile walk, split-K, slab reduction or atomics order.  The result must then EQUAL the fp64 reference (after one round-to-nearest-even where it is stored in 16 bits).
+Operands with two and three non-zero limbs — what the fp32 kernels' limb planes 1 and 2, the limb fragments of the packed weights and the second
+accumulator carry — are the last section (LimbCase).
 
 Lazy (InstanceNorm + ReLU fused) inputs: every (n, c) plane of the raw tensor gets mean exactly 0 and variance exactly 4 (unit_planes), so
 relu((x - mean) * rstd) is one of {0, 0.5, 1, 2}.  Such operands are integer multiples of `unit` = 0.5; everything below is stated in units, i.e. the bound on
@@ -375,3 +377,185 @@ class T2Case(_Case):
     gx = functools.cached_property(lambda self: conv_transpose3d_k2s2_bwd_data(self.gy, self.w))
     dw = functools.cached_property(lambda self: conv_transpose3d_k2s2_wgrad(self.a, self.gy)[0])
     db = functools.cached_property(lambda self: conv_transpose3d_k2s2_wgrad(self.a, self.gy)[1])
+
+
+# ------------------------------------------------------------------------------------------------ operands with several non-zero limbs (fp32 limb kernels)
+# The fp32 parity mode splits each fp32 operand into three bf16 limbs by round-to-nearest (csrc/common.h vs_limb_split4; pack.hip for the weights) and keeps six
+# of the nine limb products: x0 w0 + x0 w1 + x1 w0 + x0 w2 + x1 w1 + x2 w0.  The small integers above have one limb, so limb planes 1 and 2 carry zeros in those
+# cases.  Here the operands are integers with two or three non-zero limbs, paired so that the three DROPPED products (x1 w2, x2 w1, x2 w2) are identically zero:
+# a three-limb operand only ever meets a one-limb one, a two-limb operand a two-limb one.  The kept products are then all of x * w, every limb is an integer
+# (times the unit), and while sum |x_l| |w_l'| over an output's products and kept limb pairs stays below 2^24 every partial sum of any accumulator arrangement —
+# one accumulator or two, any tile walk, split-K, slabs, atomics — is an exact integer: the result must EQUAL the plain fp64 convolution, which stays the reference.
+# That sum is taken over the limbs: with the dropped products zero it equals (sum_l |x_l|) * (sum_l' |w_l'|) summed over the products, and limbs of mixed sign
+# make it slightly larger than sum |x| |w|.
+ROLES = ("x3", "w3", "g3", "22")
+THREE_BITS, TWO_BITS = (17, 19), (9, 10)
+REDRAW_ROUNDS = 50
+
+
+def bf16_rne(x):
+    """round-to-nearest-even to bf16, as v_cvt_pk_bf16_f32 does it; x must be exact in fp32"""
+    f = x.float()
+    assert torch.equal(f.double(), x), "not exact in fp32"
+    return f.to(torch.bfloat16).double()
+
+
+def limbs_of(x):
+    """the three bf16 limbs of an fp64 tensor of fp32 values, as common.h forms them: l0 = rne(x), l1 = rne(x - l0), l2 = rne(x - l0 - l1)"""
+    l0 = bf16_rne(x)
+    l1 = bf16_rne(x - l0)
+    l2 = bf16_rne(x - l0 - l1)
+    assert torch.equal(l0 + l1 + l2, x), "three bf16 limbs do not hold the value"
+    return l0, l1, l2
+
+
+def limb_abs(x):
+    """sum_l |x_l|: what an entry can contribute to a partial sum, per unit of the other operand's limbs"""
+    l0, l1, l2 = limbs_of(x)
+    return l0.abs() + l1.abs() + l2.abs()
+
+
+def limb_class_ok(v, limbs):
+    """per entry: does v have exactly `limbs` (2 or 3) non-zero limbs — limb 1 non-zero, limb 2 non-zero (three) or zero (two)"""
+    _, l1, l2 = limbs_of(v)
+    return (l1 != 0) & ((l2 != 0) if limbs == 3 else (l2 == 0))
+
+
+def limb_ints(shape, limbs, seed, density=1.0):
+    """fp64 integers with exactly `limbs` non-zero limbs in EVERY non-zero entry: 3 -> 17 to 19 bits, 2 -> 9 to 10 bits, random sign.  Entries that miss the
+    condition are drawn again (REDRAW_ROUNDS at the most: it is a condition, not a share); density < 1 zeroes the rest."""
+    g = _gen(seed)
+    shape = tuple(shape)
+    lo, hi = THREE_BITS if limbs == 3 else TWO_BITS
+
+    def draw(count):
+        return (torch.randint(2 ** (lo - 1), 2 ** hi, (count,), generator=g) * (torch.randint(0, 2, (count,), generator=g) * 2 - 1)).to(F64)
+    keep = (torch.rand(shape, generator=g) < density).reshape(-1).nonzero().view(-1) if density < 1.0 else torch.arange(math.prod(shape))
+    vals = draw(keep.numel())
+    bad = (~limb_class_ok(vals, limbs)).nonzero().view(-1)
+    for _ in range(REDRAW_ROUNDS):
+        if bad.numel() == 0:
+            break
+        new = draw(bad.numel())
+        vals[bad] = new
+        bad = bad[~limb_class_ok(new, limbs)]
+    assert bool(limb_class_ok(vals, limbs).all()), "%d redraw rounds left entries without %d non-zero limbs" % (REDRAW_ROUNDS, limbs)
+    v = torch.zeros(math.prod(shape), dtype=F64)
+    v[keep] = vals
+    return v.view(shape)
+
+
+def _k2_wgrad(x, gy):
+    return conv3d_k2s2_wgrad(x, gy)[0]
+
+
+def _t2_wgrad(x, gy):
+    return conv_transpose3d_k2s2_wgrad(x, gy)[0]
+
+
+# kind -> (forward, backward data, weight gradient) on planar fp64 tensors; the bias is added apart
+_LIMB_REFS = {"k3": (conv3d_k3, lambda gy, w, fine: conv3d_k3_bwd_data(gy, w), conv3d_k3_wgrad),
+              "k2": (conv3d_k2s2, conv3d_k2s2_bwd_data, _k2_wgrad),
+              "t2": (conv_transpose3d_k2s2, lambda gy, w, fine: conv_transpose3d_k2s2_bwd_data(gy, w), _t2_wgrad)}
+
+
+def dot_bounds_limbs(kind, a, w, gy, b=None):
+    """For every output entry the sum over its products and over the kept limb pairs of |x_l| |w_l'|, exactly (not an upper bound): the convolution of the
+    operands' limb_abs.  -> dict y / gx / dw / db of the largest entry.  Holds for operand pairs whose dropped limb products are zero (LimbCase.check asserts it)."""
+    fwd, bwd, wgr = _LIMB_REFS[kind]
+    sa, sw, sg = limb_abs(a), limb_abs(w), limb_abs(gy)
+    out = {"y": float(fwd(sa, sw).max()) + (0.0 if b is None else float(limb_abs(b).max())), "gx": float(bwd(sg, sw, a.shape[2:]).max()), "dw": float(wgr(sa, sg).max())}
+    if b is not None:
+        out["db"] = float(sg.sum((0, 2, 3, 4)).max())
+    return out
+
+
+class LimbCase(_Case):
+    """One convolution (kind k3 / k2 / t2, case = (N, Cin, Cout, D, H, W) as K3Case / K2Case / T2Case take it) with operands of a ROLE:
+
+      role   x                         w                    gy                    limb products it exercises
+      x3     three-limb, dense         ternary, sparse      ternary, sparse       y: x1 w0, x2 w0;  dW: limbs 1, 2 of the activation planes
+      w3     ternary, sparse           three-limb, dense    ternary, sparse       y: x0 w1, x0 w2;  gx: the same in the flipped weight image
+             (lazy: unit planes)       (lazy: sparse)
+      g3     ternary, sparse           ternary, sparse      three-limb, dense     gx: limbs 1, 2 of the staged gradient;  dW: of the gradient planes
+             (lazy: unit planes)                            (lazy: sparse)
+      22     two-limb, dense           two-limb, sparse     two-limb, sparse      y, gx, dW: x1 w1 with the two middle products
+
+    A lazy case runs the same InstanceNorm + ReLU input as the one-limb cases (unit_planes: a in {0, 0.5, 1, 2}, one limb, dense).  The bias of the strided
+    kinds is ternary.  The densities are not chosen by hand: every sparse operand starts at START / (products of the output it is summed into) and whichever
+    operands feed an output whose limb bound (dot_bounds_limbs) reaches 2^24 are thinned (by THIN times 2^24 / bound) and drawn again until the precondition
+    holds; an operand the role leaves dense is thinned only when nothing else feeds the output (the bias gradient of a dense three-limb gy)."""
+    START = {"x3": 16.0, "w3": 16.0, "g3": 16.0, "22": 12.0}
+    THIN = 0.75
+    LAZY_ROLES = ("w3", "g3")
+
+    def __init__(self, kind, case, role, lazy=False, seed=0):
+        assert kind in _LIMB_REFS and role in ROLES and (not lazy or role in self.LAZY_ROLES)
+        n, cin, cout, d, h, w = case
+        self.kind, self.case, self.role, self.lazy, self.unit, self.seed = kind, case, role, lazy, (0.5 if lazy else 1.0), seed
+        self.transposed = kind == "t2"
+        self.name = "%s %s role %s %s" % ({"k3": "k3", "k2": "k2s2", "t2": "t2s2"}[kind], case, role, "lazy" if lazy else "materialised")
+        vol = (d, h, w)
+        out_vol = vol if kind == "k3" else (d // 2, h // 2, w // 2) if kind == "k2" else (2 * d, 2 * h, 2 * w)
+        taps = 27 if kind == "k3" else 8
+        per_dw = n * d * h * w if kind != "k2" else n * (d // 2) * (h // 2) * (w // 2)          # terms of a weight-gradient entry
+        per_y = cin if kind == "t2" else taps * cin
+        per_gx = taps * cout if kind != "k2" else cout
+        self.shapes = {"x": (n, cin) + vol, "w": ((cin, cout) if kind == "t2" else (cout, cin)) + ((3,) * 3 if kind == "k3" else (2,) * 3), "gy": (n, cout) + out_vol}
+        start = self.START[role]
+        # the class of each operand (limbs; 1 = ternary) and its starting density
+        cls = {"x3": (3, 1, 1), "w3": (1, 3, 1), "g3": (1, 1, 3), "22": (2, 2, 2)}[role]
+        self.limbs = dict(zip(("x", "w", "gy"), cls))
+        dens = {"x3": (1.0, start / per_y, start / per_dw), "w3": (start / per_y, 1.0, start / per_gx), "g3": (start / per_dw, start / per_gx, 1.0),
+                "22": (1.0, start / max(per_y, per_gx), start / per_dw)}[role]
+        self.density = {k: min(1.0, v) for k, v in zip(("x", "w", "gy"), dens)}
+        if lazy:                                  # the dense one-limb activation takes the place of x; the three-limb operand becomes the sparse one
+            self.density["x"] = 1.0
+            self.density["w" if role == "w3" else "gy"] = min(1.0, start / (4.0 * (per_y if role == "w3" else per_dw)))
+        self.b = None if kind == "k3" else ints((cout,), 1, seed + 4)
+        feeds = {"y": ("x", "w"), "gx": ("gy", "w"), "dw": ("x", "gy"), "db": ("gy",)}
+        for self.rounds in range(1, 41):
+            self._draw(n, cin, vol)
+            self.bounds = dot_bounds_limbs(kind, self.a, self.w, self.gy, self.b)
+            over = [k for k, v in self.bounds.items() if not v < LIMIT * self.unit and not (lazy and k == "gx")]
+            if not over:
+                break
+            for k in over:
+                ops_ = [o for o in feeds[k] if not (lazy and o == "x")]
+                sparse = [o for o in ops_ if self.density[o] < 1.0]
+                for o in (sparse or ops_[-1:]):
+                    self.density[o] *= self.THIN * min(1.0, LIMIT * self.unit / self.bounds[k])
+        else:
+            raise AssertionError("%s: no densities meet the precondition" % self.name)
+
+    def _draw(self, n, cin, vol):
+        def make(which, k):
+            shape, limbs, p = self.shapes[which], self.limbs[which], self.density[which]
+            return ints(shape, 1, self.seed + k, p) if limbs == 1 else limb_ints(shape, limbs, self.seed + k, p)
+        self.x = unit_planes(n, cin, vol, self.seed + 1) if self.lazy else make("x", 1)
+        self.a = in_relu_exact(self.x) if self.lazy else self.x
+        self.w, self.gy = make("w", 2), make("gy", 3)
+
+    def check(self):
+        """the precondition over limbs, the limb condition of every operand class, and that the dropped limb products are zero"""
+        dots = {k: v for k, v in self.bounds.items() if not (self.lazy and k == "gx")}              # the gradient through a lazy input is not integer arithmetic
+        assert_exact_precondition(self.name, dots, self.unit)
+        for which, t in (("x", self.a), ("w", self.w), ("gy", self.gy)):
+            nz = t[t != 0]
+            assert nz.numel() > 0, "%s: %s is all zero" % (self.name, which)
+            if self.limbs[which] > 1 and not (self.lazy and which == "x"):
+                assert bool(limb_class_ok(nz, self.limbs[which]).all()), "%s: %s has entries without %d non-zero limbs" % (self.name, which, self.limbs[which])
+            else:
+                l0, l1, l2 = limbs_of(nz)
+                assert not bool(l1.any()) and not bool(l2.any()), "%s: %s is not a one-limb operand" % (self.name, which)
+        for p, q in (("x", "w"), ("gy", "w"), ("x", "gy")):                                       # x1 w2, x2 w1, x2 w2 vanish for every pair that is multiplied
+            assert 1 in (self.limbs[p], self.limbs[q]) or (self.limbs[p], self.limbs[q]) == (2, 2)
+        return self
+
+    def _biased(self, y):
+        return y if self.b is None else y + self.b.view(1, -1, 1, 1, 1)
+
+    y = functools.cached_property(lambda self: self._biased(_LIMB_REFS[self.kind][0](self.a, self.w)))
+    gx = functools.cached_property(lambda self: _LIMB_REFS[self.kind][1](self.gy, self.w, self.x.shape[2:]))
+    dw = functools.cached_property(lambda self: _LIMB_REFS[self.kind][2](self.a, self.gy))
+    db = functools.cached_property(lambda self: self.gy.sum((0, 2, 3, 4)))

@@ -1,8 +1,9 @@
 """The convolution and weight-gradient kernels against fp64 on inputs for which the right answer has NO rounding error: torch.equal, no tolerance.
 
-tests/exact_util.py explains the idea and makes the data: small integers (exact in bf16, fp16, fp32; one limb in the three-limb fp32 kernels), sized so that
+tests/exact_util.py explains the idea and makes the data: small integers (exact in bf16, fp16, fp32), sized so that
 every partial sum stays below 2^24, so fp32 accumulation is exact in any order — whatever the tile walk, split-K, slab reduction or atomics order, in both
-builds.  fp32 outputs (dW, db, the fp32 mode's y and gx, the statistics) equal the fp64 reference; 16-bit outputs equal it after one round-to-nearest-even
+builds.  The fp32 parity mode's kernels split every operand into three bf16 limbs; for them the small integers (one limb) are joined by integers with two and
+three non-zero limbs, paired so that the limb products the kernels drop are zero (exact_util.LimbCase; the table at the end of this text).  fp32 outputs (dW, db, the fp32 mode's y and gx, the statistics) equal the fp64 reference; 16-bit outputs equal it after one round-to-nearest-even
 (exact_util.stored).  Lazy inputs are planes with mean exactly 0 and variance exactly 4 (relu((x - mean) * rstd) in {0, 0.5, 1, 2}); the 16-bit kernels stage
 that value rounded to 16 bits, which absorbs eps = 1e-5; the fp32 kernels need rstd = 1/2 exactly, so the fp32 lazy cases run with ops.EPS_IN = 0 — and there the
 padded input channels (zero planes in the model: variance 0, rstd = inf at eps 0) are filled with such planes too; their weights are zero.
@@ -31,13 +32,42 @@ mode runs igemm_k3x.h / g3_body / g3x_body on the same shapes):
                         3 samples, 16 samples (128 of the kernel's 192 table pairs); the two real-size shapes are left to the tolerance test
 
 Not compared exactly, by design (not integer arithmetic; the tolerance tests keep them): the input gradient THROUGH a lazy input (InstanceNorm backward apply),
-the fused-apply forms, vs_conv_k3_softmax2_bwd_data, the composed Up block, the chain kernels."""
+the fused-apply forms, vs_conv_k3_softmax2_bwd_data, the composed Up block, the chain kernels.
+
+The fp32 limb kernels on operands with SEVERAL non-zero limbs (fp32 only, both builds; LIMB_* lists below, built for the purpose).  The kernels keep
+x0 w0 + x0 w1 + x1 w0 + x0 w2 + x1 w1 + x2 w0.  Every case runs in four roles, and a role pins these products (exact_util.LimbCase):
+  x3   x three-limb                y: x1 w0, x2 w0 (limb planes 1 and 2 of the staged activation); dW: limbs 1, 2 of the halo operand's planes
+  w3   w three-limb                y: x0 w1, x0 w2 (limb fragments 1 and 2 of the VS_F32X3 image); gx: the same in the flipped image
+  g3   gy three-limb               gx: limb planes 1, 2 of the staged gradient; dW: limbs 1, 2 of the row operand's planes (the halo operand's under the exchange)
+  22   x, w, gy two-limb           y, gx, dW: x1 w1 next to x0 w1 and x1 w0; the second accumulator carries all of them
+Which case reaches which instantiation (forward / backward data; tests/test_host_exact.py holds the list to the dispatch's rules, k3x_instantiation; every
+3x3x3 case asserts vs_conv_k3_f32_limbs == 1, none falls to k3s_kernel<float>).  vs_config.k3x_ck is 8 by default; 16 is the A/B setting:
+  LIMB_K3, k3x_ck = 8   (1, 8, 8, 5, 9, 33) ragged, (3, 8, 8, 7, 9, 37) three samples: k3xt / k3xt
+                        (1, 8, 16, 5, 6, 20): k3x<8,16> single chunk / MULTI with 4 x 1 x 16 tiles (YT = 1)
+                        (2, 8, 32, 16, 32, 64): k3x<8,32> single chunk (256 workgroups) / k3x<8,16,MULTI>
+                        (2, 16, 16, 12, 12, 12), (1, 32, 32, 7, 6, 6): the short-tile launches of <= 128 workgroups, YT = 1, two and four chunks
+                        (1, 16, 16, 9, 30, 33), (3, 64, 32, 9, 10, 21): YT = 2, ragged, two and eight chunks / YT = 2 and k3x<8,16,MULTI>
+                        (2, 16, 16, 20, 24, 40): k3x<8,16,MULTI>, a sample boundary in the walk; (1, 16, 32, 37, 30, 50): k3x<8,32,MULTI> / k3x<8,16,MULTI>, ragged
+  LIMB_K3, k3x_ck = 16  (1, 16, 16, 5, 9, 33): k3x<16,16>; (2, 16, 32, 16, 32, 64): k3x<16,32> / k3x<16,16,MULTI>; (1, 32, 64, 16, 32, 64): k3x<16,32,MULTI> /
+                        k3x<16,16,MULTI>; (3, 64, 32, 9, 10, 21): k3x<16,16,MULTI> both ways, four and two chunks, three samples, ragged
+  LIMB_K3_LAZY          roles w3 and g3 through the InstanceNorm + ReLU staging of a lazy input (k3xt, 8- and 16-channel chunks); the three-limb operand is
+                        the sparse one there, gx is not compared
+  every LIMB_K3 run     its weight gradient through g3x_group_kernel (one layer), 16- and 8-channel blocks
+  LIMB_K3_FALLBACK      two cases under f32_limbs = 0: k3_kernel<float> and g3_kernel<float>, where the same data are exact as well
+  LIMB_G1               g1_kernel<float, .., LIMB>: stride-2 gather and scatter, transposed scatter and gather at 8, 16, 32, 64, 128 channels, odd coarse grids
+                        (2, 3, 5), (3, 5, 7); 16- and 32-row tiles (two accumulators) by default, 64-row tiles (RB = 4: one accumulator) for the scatter launches
+                        under mt_min_wgs = 1; the 64-voxel split-chunk tiles at 64 and 128 channels; one case under g1_limbs = 0
+  LIMB_GROUP            eleven layers in one backward pass: g3x_group_kernel against g3x_kernel (per-layer launches) bit for bit and both against fp64; 16- and
+                        8-channel blocks; the operand exchange taken by the lazy layers with Cout <= Cin, and switched off (wgrad_swap = 0); wgrad_group_wgs = 6
+  FULL_CASES            not integer data: randn operands, every limb of both operands populated, against fp64 within FULL_K times torch's CPU fp32 error
+The epilogue statistics and fused InstanceNorm-backward sums of these data pass 2^24 and are not compared (with_stats = False); the one-limb cases keep them."""
 import ctypes
 import functools
 import zlib
 
 import pytest
 import torch
+import torch.nn.functional as F
 
 from tests import exact_util as X
 from tests.test_gpu_layers import FUSED_WGRAD_CASES
@@ -325,3 +355,202 @@ def test_k3_bwd_data_with_fused_weight_gradient_exact(case, dtype, lib_mode):
         check(lib.vs_conv_wgrad_multi(ctypes.addressof(arr), 1, ws.data_ptr(), nbytes, dt, ops.EPS_IN, st), "wgrad_multi (slabs)")
         torch.cuda.synchronize()
         _same(dw.cpu().double(), c.dw[:m_real, :c_real].reshape(m_real, c_real, 27), "%s: dW from %d slabs, %d x %d real channels" % (c.name, nslabs, m_real, c_real))
+
+
+# ------------------------------------------------------------------------------------------------ fp32 limb kernels: operands with two and three non-zero limbs
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def k3x_instantiation(n, c, m, d, h, w, k3x_ck=8):
+    """Which kernel csrc/conv_api.hip k3_tiles + csrc/igemm_k3x.hip g1_dispatch_k3_x3 give a plain (EPI_RAW, no fused apply) fp32 3x3x3 launch with c stored
+    input and m stored output channels under the default vs_config but for k3x_ck — restated here so that the case lists below can say, and
+    tests/test_host_exact.py can hold them to, which instantiation each case is there for.  A backward-data launch is the same with c and m exchanged."""
+    assert c in (8, 16, 32, 64) and m in (8, 16, 32, 64)
+    if c % 32 == 0 and (d + 2) * (h + 2) * (w + 2) <= 512:
+        return "k3s<float>"                                                # vs_conv_k3_f32_limbs == 0: not a limb kernel
+    ck = min(c, k3x_ck)
+    nch, rows16 = c // ck, _cdiv(m, 16) * 16
+    tiles = n * _cdiv(d, 4) * _cdiv(h, 4) * _cdiv(w, 16)
+    mt = 32 if rows16 % 32 == 0 and tiles * (rows16 // 32) >= 256 and (ck == 8 or 2 * n * (c + m) * 4 <= 3000) else 16
+    rt = rows16 // mt
+    if ck == 8 and c == 8 and m == 8:
+        return "k3xt"
+    if ck == 8 and nch > 1 and mt == 16:                                   # k3_short_tiles = 2
+        zx = n * _cdiv(d, 4) * _cdiv(w, 16)
+        if tiles * rt <= 128 and zx * _cdiv(h, 2) * rt <= 256:
+            return "k3x<8,16,MULTI,YT=%d>" % (1 if zx * _cdiv(h, 2) * rt <= 128 and zx * h * rt <= 256 else 2)
+    return "k3x<%d,%d%s>" % (ck, mt, ",MULTI" if nch > 1 else "")
+
+
+# (k3x_ck, case, forward instantiation, backward-data instantiation): the smallest shapes that reach each instantiation of g1_dispatch_k3_x3
+LIMB_K3 = [
+    (8, (1, 8, 8, 5, 9, 33), "k3xt", "k3xt"),                                                # ragged in three axes
+    (8, (3, 8, 8, 7, 9, 37), "k3xt", "k3xt"),                                                # three samples
+    (8, (1, 8, 16, 5, 6, 20), "k3x<8,16>", "k3x<8,16,MULTI,YT=1>"),
+    (8, (2, 8, 32, 16, 32, 64), "k3x<8,32>", "k3x<8,16,MULTI>"),                             # 256 workgroups of 32 rows
+    (8, (2, 16, 16, 12, 12, 12), "k3x<8,16,MULTI,YT=1>", "k3x<8,16,MULTI,YT=1>"),            # the 12^3-class launches: 4 x 1 x 16 tiles
+    (8, (1, 16, 16, 9, 30, 33), "k3x<8,16,MULTI,YT=2>", "k3x<8,16,MULTI,YT=2>"),             # 4 x 2 x 16 tiles, ragged
+    (8, (2, 16, 16, 20, 24, 40), "k3x<8,16,MULTI>", "k3x<8,16,MULTI>"),                      # 180 tiles, a sample boundary in the walk
+    (8, (1, 16, 32, 37, 30, 50), "k3x<8,32,MULTI>", "k3x<8,16,MULTI>"),                      # ragged in three axes
+    (8, (1, 32, 32, 7, 6, 6), "k3x<8,16,MULTI,YT=1>", "k3x<8,16,MULTI,YT=1>"),               # four chunks; next to the small-volume kernel's limit
+    (8, (3, 64, 32, 9, 10, 21), "k3x<8,16,MULTI,YT=2>", "k3x<8,16,MULTI>"),                  # eight chunks, three samples, ragged
+    (16, (1, 16, 16, 5, 9, 33), "k3x<16,16>", "k3x<16,16>"),
+    (16, (2, 16, 32, 16, 32, 64), "k3x<16,32>", "k3x<16,16,MULTI>"),
+    (16, (1, 32, 64, 16, 32, 64), "k3x<16,32,MULTI>", "k3x<16,16,MULTI>"),
+    (16, (3, 64, 32, 9, 10, 21), "k3x<16,16,MULTI>", "k3x<16,16,MULTI>"),                    # four chunks, three samples, ragged
+]
+LIMB_K3_LAZY = [LIMB_K3[0][:2], LIMB_K3[5][:2], LIMB_K3[9][:2], LIMB_K3[10][:2]]             # the staging of a lazy input: k3xt, 8- and 16-channel chunks
+LIMB_K3_RUNS = [(ck, case, role, False) for ck, case, _, _ in LIMB_K3 for role in X.ROLES] + \
+               [(ck, case, role, True) for ck, case in LIMB_K3_LAZY for role in X.LimbCase.LAZY_ROLES]
+# the A/B configuration vs_config.f32_limbs = 0 (exact-f32 MFMA kernels): the same data are exact there too
+LIMB_K3_FALLBACK = [(ck, case, role) for ck, case in (LIMB_K3[0][:2], LIMB_K3[5][:2]) for role in X.ROLES]
+# g1_kernel<float, ..., LIMB>: (kind, case, vs_config switches).  mt_min_wgs = 1 gives the widest row tile the rows allow — 64 rows (RB = 4: ONE accumulator)
+# for the scatter launches (8 C rows: backward data of the stride-2 conv, forward of the transposed one) and 32 rows for a 32-channel gather; the default
+# gives 16-row tiles (RB = 1: two accumulators) at these sizes.  64 and 128 channels at <= 64 workgroups: the 64-voxel split-chunk tiles (splitw).
+LIMB_G1 = [("k2", (2, 8, 8, 8, 8, 16), {}), ("k2", (2, 8, 8, 8, 8, 16), dict(mt_min_wgs=1)), ("k2", (1, 16, 16, 4, 6, 10), dict(mt_min_wgs=1)),
+           ("k2", (1, 32, 32, 4, 4, 4), dict(mt_min_wgs=1)), ("k2", (1, 64, 64, 2, 2, 6), {}), ("k2", (1, 128, 128, 2, 2, 2), {}),
+           ("t2", (2, 16, 16, 4, 4, 8), {}), ("t2", (1, 32, 32, 3, 5, 7), dict(mt_min_wgs=1)), ("t2", (1, 128, 128, 3, 3, 3), {}),
+           ("t2", (1, 128, 128, 3, 3, 3), dict(mt_min_wgs=1)),
+           ("t2", (1, 64, 64, 16, 16, 17), dict(mt_min_wgs=1))]      # 68 row-block tiles, more than the split-chunk form takes: its backward data is a 64-row GATHER tile
+LIMB_G1_RUNS = [(kind, case, cfg, role) for kind, case, cfg in LIMB_G1 for role in X.ROLES]
+LIMB_G1_FALLBACK = ("k2", (1, 32, 32, 4, 4, 4))
+# g3x weight gradients, one backward pass: (case, role, lazy) — 16- and 8-channel blocks; the operand exchange takes the lazy layers with Cout <= Cin
+LIMB_GROUP = [((2, 16, 16, 12, 12, 20), "g3", True), ((2, 16, 8, 9, 16, 33), "g3", True), ((2, 8, 16, 7, 9, 18), "g3", True), ((2, 8, 8, 7, 9, 21), "g3", True),
+              ((2, 8, 8, 7, 9, 21), "x3", False), ((2, 16, 16, 5, 5, 5), "x3", False), ((1, 32, 32, 7, 6, 6), "22", False), ((1, 32, 8, 5, 7, 19), "g3", False),
+              ((2, 16, 32, 8, 8, 8), "22", False), ((2, 8, 16, 5, 6, 20), "x3", False), ((2, 16, 16, 6, 5, 7), "w3", True)]
+LIMB_GROUP_CFGS = [{}, dict(wgrad_swap=0), dict(wgrad_group_wgs=6)]
+
+
+@functools.lru_cache(maxsize=4)
+def _limb_case(kind, case, role, lazy=False):
+    return X.LimbCase(kind, case, role, lazy, seed=_seed("limbs", kind, case, role, lazy)).check()
+
+
+@functools.lru_cache(maxsize=1)
+def _limb_group_cases():
+    return [_limb_case.__wrapped__("k3", case, role, lazy) for case, role, lazy in LIMB_GROUP]
+
+
+def _assert_limb_launches(ops, case, want):
+    from vae_segmentation_amd._lib import lib
+    n, cin, cout, d, h, w = case
+    assert lib.vs_conv_k3_f32_limbs(d, h, w, ops.cpad(cin)) == want and lib.vs_conv_k3_f32_limbs(d, h, w, ops.cpad(cout)) == want, \
+        "%s: not the kernel family this case is there for" % (case,)
+
+
+@both
+@pytest.mark.parametrize("k3x_ck,case,role,lazy", LIMB_K3_RUNS)
+def test_conv_k3_limbs_exact(k3x_ck, case, role, lazy, lib_mode, monkeypatch):
+    """k3xt / k3x_kernel (forward, backward data) and the g3x weight gradient on operands with two and three non-zero limbs (exact_util.LimbCase): y, dW and
+    (materialised) gx equal the plain fp64 convolution.  Neither a tolerance nor a restatement of the limb arithmetic: a limb-1 or limb-2 plane staged from the
+    wrong tap or channel, a wrong limb fragment of the VS_F32X3 image, a mis-paired x1 w1 or a lost second accumulator changes most entries."""
+    ops = _ops()
+    with ops.config(k3x_ck=k3x_ck):
+        _assert_limb_launches(ops, case, 1)
+        _k3_exact(_limb_case("k3", case, role, lazy), torch.float32, monkeypatch)
+
+
+@both
+@pytest.mark.parametrize("k3x_ck,case,role", LIMB_K3_FALLBACK)
+def test_conv_k3_limb_data_exact_without_limbs(k3x_ck, case, role, lib_mode, monkeypatch):
+    """the same data under vs_config.f32_limbs = 0: the exact-f32 MFMA kernels (igemm_k3.h, g3_kernel<float>) — the A/B configuration, kept correct"""
+    ops = _ops()
+    with ops.config(k3x_ck=k3x_ck, f32_limbs=0):
+        _assert_limb_launches(ops, case, 0)
+        _k3_exact(_limb_case("k3", case, role), torch.float32, monkeypatch)
+
+
+@both
+@pytest.mark.parametrize("kind,case,cfg,role", LIMB_G1_RUNS, ids=["%s-%s-%s-%s" % (k, "x".join(map(str, c)), "wide" if f else "default", r) for k, c, f, r in LIMB_G1_RUNS])
+def test_strided_limbs_exact(kind, case, cfg, role, lib_mode, monkeypatch):
+    """g1_kernel<float, ..., LIMB> (fragments split in registers, vs_limb_pair), gather and scatter forms, with two accumulators (16- and 32-row tiles) and
+    with one (64-row tiles): y, dW, db and gx equal the fp64 reference"""
+    ops = _ops()
+    with ops.config(**cfg):
+        assert ops.get_config()["f32_limbs"] == 1 and ops.get_config()["g1_limbs"] == 1
+        _strided(ops, kind, _limb_case(kind, case, role), torch.float32, monkeypatch)
+
+
+@both
+@pytest.mark.parametrize("role", X.ROLES)
+def test_strided_limb_data_exact_without_limbs(role, lib_mode, monkeypatch):
+    """one stride-2 case under vs_config.g1_limbs = 0 (g1_kernel<float, ..., LIMB = false>)"""
+    ops = _ops()
+    kind, case = LIMB_G1_FALLBACK
+    with ops.config(g1_limbs=0, mt_min_wgs=1):
+        _strided(ops, kind, _limb_case(kind, case, role), torch.float32, monkeypatch)
+
+
+@both
+@pytest.mark.parametrize("cfg", LIMB_GROUP_CFGS, ids=["default", "swap0", "group_wgs6"])
+def test_grouped_weight_gradients_limbs_exact(cfg, lib_mode, monkeypatch):
+    """g3x_group_kernel and g3x_kernel, 16- and 8-channel blocks, operand exchange on and off, on gradients and activations with three and two non-zero limbs:
+    LIMB_GROUP in one backward pass — grouped == per-layer bit for bit, and both equal the fp64 reference"""
+    ops = _ops()
+    cases = _limb_group_cases()
+    with ops.config(**cfg):
+        assert ops._GROUP["enabled"] and ops.get_config()["f32_limbs"] == 1
+        got = _layers_backward(ops, cases, ["k3"] * len(cases), torch.float32, monkeypatch)
+        ops.set_wgrad_grouping(False)
+        try:
+            single = _layers_backward(ops, cases, ["k3"] * len(cases), torch.float32, monkeypatch)
+        finally:
+            ops.set_wgrad_grouping(True)
+    for (gw, _), (sw, _), c in zip(got, single, cases):
+        _same(gw, sw, c.name + ": dW of the grouped launch against the per-layer launch")
+        _same(gw, c.dw, c.name + ": grouped dW")
+        _same(sw, c.dw, c.name + ": per-layer dW")
+
+
+# ------------------------------------------------------------------------------------------------ full-mantissa operands: every limb of both operands at once
+FULL_CASES = [(1, 16, 16, 24, 24, 24), (1, 8, 8, 5, 9, 33)]
+# Bound on (relative L2 error of the limb kernels against fp64) / (the same of torch's CPU fp32 convolution on the same operands): twice the largest ratio
+# measured over y, gx and dW of both cases in both builds, rounded up to a power of two (profiles/limb_exact_accuracy.txt: 0.95 the largest, gx at 24^3); the
+# factor of two is for another compiler's instruction order.  tests/test_host_exact.py shows that losing any one of the three smallest kept products puts the
+# error at 9 or more times the comparator, so this bound sees such a loss as well.
+FULL_K = 2.0
+
+
+def _rel_l2(a, ref):
+    return float((a.double() - ref).norm() / ref.norm())
+
+
+@functools.lru_cache(maxsize=2)
+def full_mantissa_case(case):
+    """randn operands in fp32 (weights scaled to unit output variance) -> dict: the operands, the fp64 results y / gx / dw of F.conv3d autograd, and `cpu32`, the
+    relative L2 error of the same autograd pass in fp32 on the CPU — the comparator"""
+    n, cin, cout, d, h, w = case
+    g = X._gen(_seed("full", case))
+    x = torch.randn(n, cin, d, h, w, generator=g)
+    wt = torch.randn(cout, cin, 3, 3, 3, generator=g) * (27 * cin) ** -0.5
+    gy = torch.randn(n, cout, d, h, w, generator=g)
+    out = {}
+    for dt in (torch.float64, torch.float32):
+        xr, wr = x.to(dt, copy=True).requires_grad_(True), wt.to(dt, copy=True).requires_grad_(True)
+        y = F.conv3d(xr, wr, None, padding=1)
+        (y * gy.to(dt)).sum().backward()
+        out[dt] = dict(y=y.detach(), gx=xr.grad, dw=wr.grad)
+    ref = out[torch.float64]
+    return dict(x=x, w=wt, gy=gy, cpu32={k: _rel_l2(out[torch.float32][k], ref[k]) for k in ref}, **ref)
+
+
+@both
+@pytest.mark.parametrize("case", FULL_CASES)
+def test_conv_k3_limbs_full_mantissa(case, lib_mode):
+    """ordinary random fp32 operands — all limbs of both operands populated at once, the dropped products not zero: forward, backward data and weight gradient
+    of the limb kernels are within FULL_K times the error torch's CPU fp32 convolution makes on the same operands (both against fp64)"""
+    ops = _ops()
+    n, cin, cout = case[:3]
+    _assert_limb_launches(ops, case, 1)
+    c = full_mantissa_case(case)
+    x_cl = _to_cl(c["x"].double(), ops.cpad(cin), torch.float32).requires_grad_(True)
+    w_gpu = c["w"].cuda().requires_grad_(True)
+    y, _ = ops.ConvK3.apply(x_cl, None, w_gpu, None)
+    y.backward(_to_cl(c["gy"].double(), ops.cpad(cout), torch.float32))
+    torch.cuda.synchronize()
+    got = dict(y=_from_cl(y.detach(), cout), gx=_from_cl(x_cl.grad, cin), dw=w_gpu.grad.cpu())
+    errs = {k: _rel_l2(got[k], c[k]) for k in got}
+    print("\nlimbs full mantissa %s %s: %s" % (case, lib_mode, ", ".join("%s %.3e / cpu fp32 %.3e = %.2f" % (k, errs[k], c["cpu32"][k], errs[k] / c["cpu32"][k]) for k in errs)))
+    for k in errs:
+        assert errs[k] <= FULL_K * c["cpu32"][k], "%s %s: %.3e against %g x %.3e" % (case, k, errs[k], FULL_K, c["cpu32"][k])
