@@ -28,6 +28,9 @@ mode runs igemm_k3x.h / g3_body / g3x_body on the same shapes):
                         the largest; under GROUP_SETTINGS the M-packed 8-channel form (g3b_body) on / off, the uber kernel or one grid per bucket, operand swap,
                         the big-tile kernel g3c_body for every layer, the transposed conv's bias gradient folded in or separate; wgrad_group_wgs = 6: every
                         workgroup walks several ragged tiles.  Grouped == per-layer launches (vs_conv_wgrad) bit for bit.
+  MANY_BATCHES          58 tiny layers, 18 of them with biases, in one backward pass: more than one batch through every batching loop of vs_conv_wgrad_multi's host
+                        side (G3_GROUP_MAX 24 layers per grid, G3_RED_MAX 56 reductions, G3_BIAS_MAX 16 biases per launch); bf16 in one grid, bf16 with one grid
+                        per bucket, bf16 with the transposed convs' biases kept out of their layers' launches, fp32
   FUSED_WGRAD_CASES     vs_conv_k3_bwd_data_wgrad (igemm_k3tw.h): backward-data result and its slabs reduced through a VS_WGRAD_SLABS descriptor — ragged,
                         3 samples, 16 samples (128 of the kernel's 192 table pairs); the two real-size shapes are left to the tolerance test
 
@@ -281,6 +284,45 @@ def test_grouped_weight_gradients_exact(cfg, dtype, lib_mode, monkeypatch):
     fp64 reference, and the grouped launches equal the per-layer ones bit for bit."""
     ops = _ops()
     cases, kinds = _group_cases(), [g[0] for g in GROUP_LAYERS]
+    with ops.config(**cfg):
+        assert ops._GROUP["enabled"]
+        got = _layers_backward(ops, cases, kinds, dtype, monkeypatch)
+        ops.set_wgrad_grouping(False)
+        try:
+            single = _layers_backward(ops, cases, kinds, dtype, monkeypatch)
+        finally:
+            ops.set_wgrad_grouping(True)
+    for (gw, gb), (sw, sb), c in zip(got, single, cases):
+        _same(gw, sw, c.name + ": dW of the grouped launch against the per-layer launch")
+        _same(gw, c.dw, c.name + ": grouped dW")
+        _same(sw, c.dw, c.name + ": per-layer dW")
+        if gb is not None:
+            _same(gb, sb, c.name + ": db of the grouped launch against the per-layer launch")
+            _same(gb, c.db, c.name + ": grouped db")
+            _same(sb, c.db, c.name + ": per-layer db")
+
+
+# More layers than one batch of any grouped launch holds (csrc/wgrad.hip: G3_GROUP_MAX = 24, G3_RED_MAX = 56, G3_BIAS_MAX = 16), all tiny: 40 3x3x3 layers 8 -> 8 on
+# a (1, 4, 4, 16) grid and 18 stride-2 / transposed layers 8 -> 8 with biases on a (2, 2, 2) coarse grid, alternating.  58 weight + 18 bias reductions (two
+# reduce launches), 18 biases (two bias launches where they do not ride in the all-buckets grid), 58 + 18 = 76 entries in the all-buckets grid (four G3Groups) with
+# the transposed convs' biases kept out of their layers' launches, 58 + 9 = 67 (three) by default.
+MANY_BATCHES = [("k3", 1, 8, 8, 4, 4, 16)] * 40 + [("k2", 1, 8, 8, 4, 4, 4) if i % 2 == 0 else ("t2", 1, 8, 8, 2, 2, 2) for i in range(18)]
+MANY_BATCHES_RUNS = [(torch.bfloat16, {}), (torch.bfloat16, dict(wgrad_uber=0)), (torch.float32, {}), (torch.bfloat16, dict(wgrad_bias_fold=0))]
+
+
+@functools.lru_cache(maxsize=1)
+def _many_batches_cases():
+    return [_KINDS[kind](tuple(case), True, seed=_seed("many", i)).check() for i, (kind, *case) in enumerate(MANY_BATCHES)]
+
+
+@both
+@pytest.mark.parametrize("dtype,cfg", MANY_BATCHES_RUNS, ids=["bf16", "bf16-uber0", "fp32", "bf16-fold0"])
+def test_grouped_weight_gradients_many_batches_exact(dtype, cfg, lib_mode, monkeypatch):
+    """MANY_BATCHES in one backward pass: every batching loop of vs_conv_wgrad_multi's host side (G3Group, G3RedGroup, G3BiasGroup fills) runs more than once —
+    bf16 in the all-buckets grid, bf16 with one grid per bucket (the bias partial sums in launches of their own), and fp32 (limb groups, exact-f32 stride-2
+    groups, the fp32 bias launches).  As test_grouped_weight_gradients_exact: grouped == per-layer bit for bit, and both equal the fp64 reference."""
+    ops = _ops()
+    cases, kinds = _many_batches_cases(), [g[0] for g in MANY_BATCHES]
     with ops.config(**cfg):
         assert ops._GROUP["enabled"]
         got = _layers_backward(ops, cases, kinds, dtype, monkeypatch)

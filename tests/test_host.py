@@ -110,6 +110,32 @@ def test_conv_plan_answers_are_pinned():
     assert [int((a[k, :, :6] != a[0, :, :6]).any(axis=1).sum()) for k in range(1, len(P.CONFIGS))] == [387, 14, 178, 32, 598, 502, 96, 3167, 192, 0]
 
 
+def test_wgrad_plan_answers_are_pinned():
+    """The host answers of the grouped weight-gradient path (csrc/wgrad.hip; tools/wgrad_plan_table.py): vs_conv_wgrad_multi_workspace_bytes of 16 descriptor
+    lists under three storage types, the default vs_config and seven single changes of it, vs_conv_wgrad_workspace_bytes of their single layers, and the code
+    of 96 rejected vs_conv_wgrad_multi calls (each refused on the host before its first launch: fake addresses) equal tests/golden/wgrad_plan.npz, a table made
+    from the build BEFORE one planner served the size query and the launcher: every entry."""
+    import numpy as np
+    from vae_segmentation_amd._lib import lib
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    try:
+        import wgrad_plan_table as P
+    finally:
+        sys.path.pop(0)
+    want = np.load(os.path.join(REPO, "tests", "golden", "wgrad_plan.npz"), allow_pickle=False)
+    got = P.table(lib.loaded()[0])
+    assert sorted(want.files) == sorted(got) == ["multi_bytes", "rejected", "rejected_bf16_bytes", "single_bytes", "singles"]
+    assert want["multi_bytes"].shape == (len(P.CONFIGS), 16, 3) and want["rejected"].shape == (96,) and want["single_bytes"].shape == (len(P.CONFIGS), len(want["singles"]))
+    for name in want.files:
+        assert got[name].dtype == want[name].dtype and got[name].shape == want[name].shape and (got[name] == want[name]).all(), name
+    # the fixture itself: every accepted list has a size in 16-bit storage, the fp32 mode refuses exactly the three lists with slab descriptors, every
+    # configuration change moves some answer, and every rejected call was refused with one of the library's own codes
+    mb = want["multi_bytes"]
+    assert (mb[:, :, 1:] > 0).all() and (mb[:, :, 1] == mb[:, :, 2]).all() and [int((mb[k, :, 0] == 0).sum()) for k in range(len(P.CONFIGS))] == [3] * len(P.CONFIGS)
+    assert all(int((mb[k] != mb[0]).sum()) > 0 for k in range(1, len(P.CONFIGS)))
+    assert sorted(set(want["rejected"].tolist())) == [-4, -3, -2, -1]
+
+
 def test_grouped_weight_gradient_planning_without_gpu():
     """vs_conv_wgrad_multi's host side: descriptor layout (ctypes mirror == C struct), workspace planning and rejection of bad
     descriptors happen before any launch."""

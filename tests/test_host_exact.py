@@ -158,6 +158,9 @@ def test_every_gpu_case_meets_the_precondition(kind, runs):
 
 def test_grouped_and_slab_cases_meet_the_precondition():
     assert len(G._group_cases()) == len(G.GROUP_LAYERS)
+    many = G._many_batches_cases()                           # more layers than a batch of any grouped launch holds (csrc/wgrad.hip G3_RED_MAX 56, G3_BIAS_MAX 16, G3_GROUP_MAX 24)
+    assert len(many) == 58 and sum(c.b is not None for c in many) == 18 and 58 + 18 > 56 and 58 + 18 > 3 * 24
+    assert all(float(c.gy.abs().min()) >= 1 for c in many)
     assert set(G._several_cases()) == {"k3", "k2", "t2"}
     assert G.SLAB_CASES == [(2, 12, 16, 40), (1, 9, 11, 33), (3, 5, 9, 33), (1, 4, 8, 32), (16, 4, 8, 32)]
     for n, d, h, w in G.SLAB_CASES:

@@ -1097,6 +1097,26 @@ extern "C" size_t vs_conv_wgrad_workspace_bytes(int n, int dp, int hp, int wp, i
     return (size_t)ksplit * mbn * cbn * ncb * 256 * 4;
 }
 
+// Every grid of this file starts here: the dynamic-LDS attribute once per kernel instantiation (the static below is per (KERN, RULE)), launch, check.
+// Each kernel keeps its own rule for the attribute: always its LDS size (the limb and exact-f32 grouped kernels, which always pass 64 KiB), only above
+// 64 KiB (g3b / g3), or a fixed 96 KiB whatever the grid needs (the all-buckets kernel: its LDS size differs from grid to grid).
+enum { G3_ATTR_ALWAYS, G3_ATTR_ABOVE_64K, G3_ATTR_96K };
+template <auto KERN, int RULE, typename Arg>
+static int g3_launch(int grid_x, int grid_y, size_t lds, hipStream_t s, const Arg& arg) {
+    if (RULE != G3_ATTR_ABOVE_64K || lds > 64 * 1024) {
+        static const hipError_t attr_err =
+            hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, RULE == G3_ATTR_96K ? 96 * 1024 : (int)lds);
+        if (attr_err != hipSuccess) return (int)attr_err;
+    }
+    if (RULE == G3_ATTR_96K && lds > 96 * 1024) return VS_ESHAPE;
+    hipLaunchKernelGGL(KERN, dim3(grid_x, grid_y), dim3(256), lds, s, arg);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+template <int CB, int KIND> constexpr size_t g3b_lds() { return G3B_LDS_Q + (size_t)G3Geo<CB, KIND>::QV * CB * 2; }
+template <int CB, int KIND> constexpr size_t g3_lds() { return G3_LDS_Q + (size_t)G3Geo<CB, KIND>::QV * CB * 4; }
+template <int CB> constexpr size_t g3x_lds() { return G3X_LDS_Q + (size_t)3 * G3Geo<CB, G3_K3>::QV * CB * 2; }
+
 // reduce_slabs: how many slabs (starting at reduce_ws) the reduction that follows this layer's kernel sums; 0 = no reduction launch (a
 // later part of the same weight's gradient — a weight used several times in one backward pass — reduces all parts' slabs together)
 template <int CB, int KIND>
@@ -1108,46 +1128,23 @@ static int g3_reduce_launch(const float* reduce_ws, float* dw, int m_real, int c
     return VS_OK;
 }
 
+// one layer: its kernel, then (reduce_slabs > 0) its reduction
+template <auto KERN, int RULE, int CB, int KIND>
+static int g3_layer_run(size_t lds, const G3Params& p, float* dw, int m_real, int c_real, hipStream_t s, const float* reduce_ws, int reduce_slabs) {
+    const int rc = g3_launch<KERN, RULE>(p.mbn * p.cbn, p.ksplit, lds, s, p);
+    return rc || reduce_slabs <= 0 ? rc : g3_reduce_launch<CB, KIND>(reduce_ws, dw, m_real, c_real, p.mbn, p.cbn, reduce_slabs, s);
+}
 template <typename T, int CB, int KIND>
 static int g3b_run(const G3Params& p, float* dw, int m_real, int c_real, hipStream_t s, const float* reduce_ws, int reduce_slabs) {
-    using GEO = G3Geo<CB, KIND>;
-    constexpr size_t lds = G3B_LDS_Q + (size_t)GEO::QV * CB * 2;
-    auto kern = g3b_kernel<CB, KIND, T>;
-    if (lds > 64 * 1024) {
-        static const hipError_t attr_err =
-            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (attr_err != hipSuccess) return (int)attr_err;
-    }
-    hipLaunchKernelGGL(kern, dim3(p.mbn * p.cbn, p.ksplit), dim3(256), lds, s, p);
-    VS_CHECK_LAUNCH();
-    return reduce_slabs > 0 ? g3_reduce_launch<CB, KIND>(reduce_ws, dw, m_real, c_real, p.mbn, p.cbn, reduce_slabs, s) : VS_OK;
+    return g3_layer_run<g3b_kernel<CB, KIND, T>, G3_ATTR_ABOVE_64K, CB, KIND>(g3b_lds<CB, KIND>(), p, dw, m_real, c_real, s, reduce_ws, reduce_slabs);
 }
-
 template <typename T, int CB, int KIND>
 static int g3_run(const G3Params& p, float* dw, int m_real, int c_real, hipStream_t s, const float* reduce_ws, int reduce_slabs) {
-    using GEO = G3Geo<CB, KIND>;
-    constexpr size_t lds = G3_LDS_Q + (size_t)GEO::QV * CB * 4;
-    auto kern = g3_kernel<T, CB, KIND>;
-    if (lds > 64 * 1024) {
-        static const hipError_t attr_err =
-            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (attr_err != hipSuccess) return (int)attr_err;
-    }
-    hipLaunchKernelGGL(kern, dim3(p.mbn * p.cbn, p.ksplit), dim3(256), lds, s, p);
-    VS_CHECK_LAUNCH();
-    return reduce_slabs > 0 ? g3_reduce_launch<CB, KIND>(reduce_ws, dw, m_real, c_real, p.mbn, p.cbn, reduce_slabs, s) : VS_OK;
+    return g3_layer_run<g3_kernel<T, CB, KIND>, G3_ATTR_ABOVE_64K, CB, KIND>(g3_lds<CB, KIND>(), p, dw, m_real, c_real, s, reduce_ws, reduce_slabs);
 }
-
 template <int CB>
 static int g3x_run(const G3Params& p, float* dw, int m_real, int c_real, hipStream_t s, const float* reduce_ws, int reduce_slabs) {
-    using GEO = G3Geo<CB, G3_K3>;
-    constexpr size_t lds = G3X_LDS_Q + (size_t)3 * GEO::QV * CB * 2;
-    auto kern = g3x_kernel<CB>;
-    static const hipError_t attr_err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr_err != hipSuccess) return (int)attr_err;
-    hipLaunchKernelGGL(kern, dim3(p.mbn * p.cbn, p.ksplit), dim3(256), lds, s, p);
-    VS_CHECK_LAUNCH();
-    return reduce_slabs > 0 ? g3_reduce_launch<CB, G3_K3>(reduce_ws, dw, m_real, c_real, p.mbn, p.cbn, reduce_slabs, s) : VS_OK;
+    return g3_layer_run<g3x_kernel<CB>, G3_ATTR_ALWAYS, CB, G3_K3>(g3x_lds<CB>(), p, dw, m_real, c_real, s, reduce_ws, reduce_slabs);
 }
 
 // One layer's kernel into `workspace`.  prior_slabs >= 0: reduce (prior_slabs + this layer's) slabs starting prior_slabs slabs BEFORE
@@ -1214,7 +1211,15 @@ static int wgrad_single(const void* P, const double* p_stats, const void* Q, con
 
 
 // ---------------------------------------------------------------------------------------------------
-// Grouped path (vs_conv_wgrad_multi): see include/vaeseg.h.
+// Grouped path (vs_conv_wgrad_multi): see include/vaeseg.h; DESIGN.md 3.2a for the plan.
+//   kernels and their argument structs      G3RedGroup / g3_reduce_group_kernel, G3BiasGroup / bias_partial_group_kernel, g3b_uber_kernel (G3Group is above)
+//   multi_plan                              descriptors -> MultiPlan: per layer its G3Params, k-split and slab / bias regions (one grid's worth of planning)
+//   g3_group_fill / g3_groups_run, RedList, bias_partials_launch
+//                                           the one copy of each batching loop: G3_GROUP_MAX layers per grid, G3_RED_MAX reductions, G3_BIAS_MAX biases
+//   wgrad_plan                              (descs, count, dtype) -> WgradPlan: status, workspace bytes and every region; the ONLY layout — the size query
+//                                           returns its bytes, the launcher launches from it and computes no size or offset of its own
+//   launch_f32, launch_uber, launch_buckets, launch_16bit
+//                                           the launches of a planned call, one step each
 // ---------------------------------------------------------------------------------------------------
 #include <algorithm>
 #include <vector>
@@ -1497,9 +1502,20 @@ static int multi_validate(const vs_wgrad_desc& d) {
     return VS_OK;
 }
 
+// The uses of one weight in a pass: for every descriptor the index of the FIRST one with the same dw (its own index where it is the first).  The one scan of
+// this kind: multi_plan's MultiLayer::primary and the fp32 mode's serial region (wgrad_plan) both read it.
+static std::vector<int> dw_first_use(const vs_wgrad_desc* descs, int count) {
+    std::vector<int> first(count);
+    for (int i = 0; i < count; ++i) {
+        first[i] = i;
+        for (int j = 0; j < i; ++j) if (descs[j].dw == descs[i].dw) { first[i] = j; break; }
+    }
+    return first;
+}
+
 // bf16 plan: every layer gets its own slab region; k-splits are chosen per (CB, KIND) bucket so that the bucket's ONE grid has
-// about `target` workgroups of about equal tile counts.
-static int multi_plan(const vs_wgrad_desc* descs, int count, float eps, MultiPlan& plan, int target_wgs = 0, bool pack_m = false) {
+// about `target` workgroups of about equal tile counts.  G3Params.eps is left 0: the launch fills it in (g3_group_fill).
+static int multi_plan(const vs_wgrad_desc* descs, int count, MultiPlan& plan, int target_wgs = 0, bool pack_m = false) {
     // workgroups per bucket.  With one grid PER bucket 512 measured best of 384..2560 (two workgroups per CU are resident); inside the all-buckets grid the
     // buckets share the chip, every workgroup pays a prologue (statistics tables, first loads) and an epilogue (slab reduction through LDS, slab store, its
     // share of the reduction launch), and fewer, longer workgroups win: same-box A/B at 96^3 (profiles/r05_ab_wgrad_group_wgs.json)
@@ -1534,7 +1550,7 @@ static int multi_plan(const vs_wgrad_desc* descs, int count, float eps, MultiPla
         if (rc) return rc;
         vs_wgrad_desc& d = eff[i];
         MultiLayer& L = plan.layers[i];
-        L.swap = (d.kind == VS_CONV_K3 && d.reserved_ == -1) ? 1 : 0;        // exchanged by the caller already (fp32 path: f32_effective)
+        L.swap = (d.kind == VS_CONV_K3 && d.reserved_ == -1) ? 1 : 0;        // exchanged by the caller already (fp32 path: f32_exchange)
         if (!L.swap && swap_on && d.kind == VS_CONV_K3 && d.q_stats != nullptr && d.p_stats == nullptr && d.m_ch <= d.c_ch) {
             std::swap(d.p, d.q); std::swap(d.p_stats, d.q_stats); std::swap(d.m_ch, d.c_ch); std::swap(d.m_real, d.c_real);
             L.swap = 1;
@@ -1570,7 +1586,6 @@ static int multi_plan(const vs_wgrad_desc* descs, int count, float eps, MultiPla
                 g3_fastdiv(p);
             }
         }
-        p.eps = eps;
         p.inv_cnt_p = 1.0 / ((double)d.dp * d.hp * d.wp);
         p.inv_cnt_q = 1.0 / ((double)p.Dq * p.Hq * p.Wq);
         if ((long long)d.n * d.dp * d.hp * d.wp * d.m_ch * 2 >= 2147483648ll || (long long)d.n * p.Dq * p.Hq * p.Wq * d.c_ch * 2 >= 2147483648ll) return VS_ESHAPE;
@@ -1578,17 +1593,17 @@ static int multi_plan(const vs_wgrad_desc* descs, int count, float eps, MultiPla
         bucket_work[bucket_of(L)] += (long long)p.mbn * p.cbn * p.total_tiles;
     }
     // descriptors that share dw (db): parts of one gradient
+    const std::vector<int> first = dw_first_use(descs, count);
     for (int i = 0; i < count; ++i) {
         MultiLayer& L = plan.layers[i];
-        L.primary = i; L.bias_primary = i;
+        L.primary = first[i]; L.bias_primary = i;
+        if (L.primary != i) {
+            const MultiLayer& F = plan.layers[L.primary];
+            if (F.cbsz != L.cbsz || F.kind != L.kind || F.p.mbn != L.p.mbn || F.p.cbn != L.p.cbn || F.m_real != L.m_real || F.c_real != L.c_real || F.p.mp != L.p.mp || F.swap != L.swap
+                || (F.big != 0) != (L.big != 0))
+                return VS_EINVAL;                     // same destination, different layer geometry
+        }
         for (int j = 0; j < i; ++j) {
-            if (descs[j].dw == descs[i].dw && L.primary == i) {
-                const MultiLayer& F = plan.layers[j];
-                if (F.cbsz != L.cbsz || F.kind != L.kind || F.p.mbn != L.p.mbn || F.p.cbn != L.p.cbn || F.m_real != L.m_real || F.c_real != L.c_real || F.p.mp != L.p.mp || F.swap != L.swap
-                    || (F.big != 0) != (L.big != 0))
-                    return VS_EINVAL;                     // same destination, different layer geometry
-                L.primary = F.primary;
-            }
             if (descs[i].bias_g && descs[j].bias_g && descs[j].db == descs[i].db && L.bias_primary == i) {
                 if (descs[j].bias_c_real != descs[i].bias_c_real) return VS_EINVAL;
                 L.bias_primary = plan.layers[j].bias_primary;
@@ -1614,7 +1629,9 @@ static int multi_plan(const vs_wgrad_desc* descs, int count, float eps, MultiPla
         if (d.bias_g) {
             const int rpi = 256 / (d.bias_c_ch / 8);
             long long nb = (d.bias_rows + (long long)rpi * 32 - 1) / ((long long)rpi * 32);
-            L.bias_nblk = (int)std::min<long long>(std::max<long long>(nb, 1), target_wgs > 0 ? std::max(8, target_wgs / 2) : 256);     // <= 2 rounds of the reduce's 16 x 8 loads
+            // <= 2 rounds of the reduce's 16 x 8 loads.  (The clamp had a second arm for target_wgs > 0; the only callers that pass a target are the fp32
+            // mode's groups, whose descriptors carry no bias — f32_group_descs strips it — so it could not be reached and is gone.)
+            L.bias_nblk = (int)std::min<long long>(std::max<long long>(nb, 1), 256);
             // ConvTranspose3d's bias: the gradient rows are the fine tensor the stride-2 kernel stages as Q — summed there (all-buckets grid, 16-bit storage)
             if (fold_on && d.kind == VS_CONV_K2S2 && d.bias_g == d.q && d.bias_c_ch == d.c_ch && d.bias_c_real == d.c_ch &&
                 d.bias_rows == (long long)d.n * p.Dq * p.Hq * p.Wq) {
@@ -1653,22 +1670,6 @@ static int multi_plan(const vs_wgrad_desc* descs, int count, float eps, MultiPla
     return VS_OK;
 }
 
-template <typename T, int CB, int KIND, bool MP = false>
-static int g3b_group_run(const G3Group& grp, hipStream_t s) {
-    using GEO = G3Geo<CB, KIND>;
-    constexpr size_t lds = G3B_LDS_Q + (size_t)GEO::QV * CB * 2;
-    auto kern = g3b_group_kernel<CB, KIND, T, MP>;
-    if (lds > 64 * 1024) {
-        static const hipError_t attr_err =
-            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (attr_err != hipSuccess) return (int)attr_err;
-    }
-    hipLaunchKernelGGL(kern, dim3(grp.wg_start[grp.n]), dim3(256), lds, s, grp);
-    VS_CHECK_LAUNCH();
-    return VS_OK;
-}
-
-
 static int g3v_of(int cbsz, int kind, bool mp, int big = 0) {
     if (big) return big;
     if (kind == VS_CONV_UP) return G3V_UP_16;
@@ -1678,13 +1679,13 @@ static int g3v_of(int cbsz, int kind, bool mp, int big = 0) {
 }
 static size_t g3v_lds(int variant) {
     switch (variant) {
-        case G3V_K3_16: case G3V_K3_16_MP: return G3B_LDS_Q + (size_t)G3Geo<16, G3_K3>::QV * 16 * 2;
-        case G3V_K3_8: case G3V_K3_8_MP:   return G3B_LDS_Q + (size_t)G3Geo<8, G3_K3>::QV * 8 * 2;
-        case G3V_K2S2_16:                  return G3B_LDS_Q + (size_t)G3Geo<16, G3_K2S2>::QV * 16 * 2;
-        case G3V_K2S2_8:                   return G3B_LDS_Q + (size_t)G3Geo<8, G3_K2S2>::QV * 8 * 2;
+        case G3V_K3_16: case G3V_K3_16_MP: return g3b_lds<16, G3_K3>();
+        case G3V_K3_8: case G3V_K3_8_MP:   return g3b_lds<8, G3_K3>();
+        case G3V_K2S2_16:                  return g3b_lds<16, G3_K2S2>();
+        case G3V_K2S2_8:                   return g3b_lds<8, G3_K2S2>();
         case G3V_BIG_MP8:                  return G3CGeo<8, true, G3C_TZ, G3C_TY>::LDS;
         case G3V_BIG_A16H8:                return G3CGeo<8, false, G3C_TZ, G3C_TY>::LDS;
-        default:                           return G3B_LDS_Q + (size_t)G3Geo<16, G3_UP>::QV * 16 * 2;
+        default:                           return g3b_lds<16, G3_UP>();
     }
 }
 // relative duration of one tile of a variant's loop (sort key of the all-buckets launch: longest workgroups first)
@@ -1694,58 +1695,173 @@ static double g3v_tile_cost(int variant) {
         case G3V_K2S2_16: return 1.6; case G3V_K2S2_8: return 0.8; case G3V_BIG_MP8: return 3.2; case G3V_BIG_A16H8: return 4.5; default: return 2.0;
     }
 }
+
+// ---- the pieces every grouped launch is made of -------------------------------------------------------------------------------------------
+// One G3Group from a plan.  Entry idx[j] >= 0 is plan layer idx[j]; idx[j] < 0 (all-buckets grid only) the bias partial sums of layer -(idx[j] + 1), whose entry
+// re-uses G3Params (g3b_uber_kernel).  uber_lds non-null: the all-buckets grid — every entry gets its G3V_* variant, *uber_lds the largest variant's LDS bytes.
+static int g3_group_fill(G3Group& grp, const MultiPlan& plan, const vs_wgrad_desc* descs, char* ws, float eps, const int* idx, size_t n, size_t* uber_lds) {
+    grp.xcd = vs_cfg().wgrad_xcd;                        // >= 2: g3_xcd_rank (the channel-block pairs of a tile on one XCD)
+    grp.n = (int)n;
+    long long wg = 0;
+    size_t lds = 0;
+    for (int j = 0; j < grp.n; ++j) {
+        G3Params& q = grp.p[j];
+        grp.wg_start[j] = (int)wg;
+        if (idx[j] < 0) {
+            const int i = -idx[j] - 1;
+            const vs_wgrad_desc& d = descs[i];
+            q.P = d.bias_g; q.ws = (float*)(ws + plan.layers[i].bias_off);
+            q.total_tiles = (int)d.bias_rows; q.Mch = d.bias_c_ch; q.Cch = d.bias_c_real; q.ksplit = plan.layers[i].bias_nblk;
+            q.mbn = 1; q.cbn = 1; q.variant = G3V_BIAS;
+            lds = std::max(lds, (size_t)256 * 8 * sizeof(float));
+            wg += q.ksplit;
+            continue;
+        }
+        const MultiLayer& L = plan.layers[idx[j]];
+        if (L.kind == VS_CONV_UP && L.cbsz != 16) return VS_ESHAPE;      // (multi_validate refuses a VS_CONV_UP descriptor with fewer than 16 Q channels first)
+        q = L.p;
+        q.eps = eps;
+        q.ws = (float*)(ws + L.ws_off);
+        if (uber_lds) {
+            q.variant = g3v_of(L.cbsz, L.kind, L.p.mp != 0, L.big);
+            lds = std::max(lds, g3v_lds(q.variant));
+        }
+        wg += (long long)L.p.mbn * L.p.cbn * L.p.ksplit;
+    }
+    if (wg >= 2147483647ll) return VS_ESHAPE;
+    for (int j = grp.n; j <= G3_GROUP_MAX; ++j) grp.wg_start[j] = (int)wg;
+    if (uber_lds) *uber_lds = lds;
+    return VS_OK;
+}
+// the entries idx, G3_GROUP_MAX per grid, each grid through run(group, LDS bytes of the all-buckets grid or 0)
+template <typename Run>
+static int g3_groups_run(const MultiPlan& plan, const vs_wgrad_desc* descs, char* ws, float eps, const std::vector<int>& idx, bool uber, Run run) {
+    for (size_t at = 0; at < idx.size(); at += G3_GROUP_MAX) {
+        G3Group grp{};
+        size_t lds = 0;
+        int rc = g3_group_fill(grp, plan, descs, ws, eps, idx.data() + at, std::min<size_t>(G3_GROUP_MAX, idx.size() - at), uber ? &lds : nullptr);
+        if (!rc) rc = run(grp, lds);
+        if (rc) return rc;
+    }
+    return VS_OK;
+}
+static std::vector<int> layers_by_work(const MultiPlan& plan, std::vector<int> idx) {        // longest workgroups first
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return plan.layers[a].work > plan.layers[b].work; });
+    return idx;
+}
+
+// The entries of the grouped reduction (g3_reduce_group_kernel) and the blocks each takes.
+struct RedList {
+    std::vector<G3RedDesc> d;
+    std::vector<int> blocks;
+    // the slabs of one gradient: all its parts, summed by `parts` partitions in parallel
+    void add_slabs(const float* slabs, float* dw, int m_real, int c_real, int mbn, int cbn, int nslabs, int cb, int ntaps, int ncb, int swap, int parts = 0) {
+        // a partition sums up to 8 slabs in one round of independent loads: no more partitions (= threads, waves) than that needs
+        if (!parts) for (parts = 1; parts < G3_RED_ROWS && parts * 8 < nslabs;) parts *= 2;
+        const long long slab_elems = (long long)mbn * cbn * ncb * 256;
+        d.push_back(G3RedDesc{slabs, dw, m_real, c_real, mbn, cbn, nslabs, cb, ntaps, ncb, 0, parts, swap});
+        blocks.push_back(vs_ceil_div(slab_elems, 256 * (G3_RED_ROWS / parts)));
+    }
+    void add_layer(const MultiLayer& L, char* ws) {
+        add_slabs((const float*)(ws + L.ws_off), L.dw, L.m_real, L.c_real, L.p.mbn, L.p.cbn, L.total_slabs, L.cbsz | (L.p.mp ? 0x100 : 0), L.kind != VS_CONV_K2S2 ? 27 : 8, L.ncb, L.swap);
+    }
+    void add_bias(const void* partials, float* db, int c_real, int nparts) {       // double [nparts][c_real]
+        d.push_back(G3RedDesc{(const float*)partials, db, 0, c_real, 0, 0, nparts, 0, 0, 0, 1, G3_RED_ROWS, 0});
+        blocks.push_back(vs_ceil_div(c_real, 64));
+    }
+    // a VS_WGRAD_SLABS descriptor: 27 x 8 x 8 slabs a backward-data launch wrote (16 vectors of 4 elements per block: 1728 / 64 = 27 blocks) and the bias
+    // partials it may carry (vs_conv_k3_softmax2_bwd_data)
+    void add_slab_desc(const vs_wgrad_desc& sd) {
+        add_slabs((const float*)sd.p, sd.dw, sd.m_real, sd.c_real, 1, 1, sd.n, 0x208, 27, 27, 0, G3_RED_ROWS);
+        if (sd.bias_g) add_bias(sd.bias_g, sd.db, sd.bias_c_real, sd.n);
+    }
+    // the reductions of a planned list: per layer its weight (ws non-null) and its bias (bias_ws non-null: where the plan's bias offsets count from)
+    void add_plan(const MultiPlan& plan, const vs_wgrad_desc* descs, char* ws, char* bias_ws) {
+        for (size_t i = 0; i < plan.layers.size(); ++i) {
+            const MultiLayer& L = plan.layers[i];
+            if (ws && L.primary == (int)i) add_layer(L, ws);          // one reduction per gradient, over the slabs of all its parts
+            if (bias_ws && descs[i].bias_g && L.bias_primary == (int)i) add_bias(bias_ws + L.bias_off, descs[i].db, descs[i].bias_c_real, L.bias_total_blk);
+        }
+    }
+    // G3_RED_MAX entries per launch.  The 31-bit bound on a grid is tested for every caller; two of them cannot reach it with descriptors that were accepted:
+    // a list of slab descriptors alone gives at most 56 x 27 blocks per launch, the fp32 mode's bias entries 56 x 2048 / 64.
+    int launch(hipStream_t st) const {
+        for (size_t at = 0; at < d.size(); at += G3_RED_MAX) {
+            G3RedGroup grp{};
+            grp.n = (int)std::min<size_t>(G3_RED_MAX, d.size() - at);
+            long long blk = 0;
+            for (int j = 0; j < grp.n; ++j) { grp.d[j] = d[at + j]; grp.blk_start[j] = (int)blk; blk += blocks[at + j]; }
+            if (blk >= 2147483647ll) return VS_ESHAPE;
+            for (int j = grp.n; j <= G3_RED_MAX; ++j) grp.blk_start[j] = (int)blk;
+            hipLaunchKernelGGL(g3_reduce_group_kernel, dim3((unsigned)blk), dim3(64 * G3_RED_ROWS), 0, st, grp);
+            VS_CHECK_LAUNCH();
+        }
+        return VS_OK;
+    }
+};
+
+// the bias partial sums of the layers idx of a plan (bias_ws: where its bias offsets count from), G3_BIAS_MAX per launch; T: the storage type of the gradient rows
 template <typename T>
-static int g3b_uber_run(const G3Group& grp, size_t lds, hipStream_t s) {
-    auto kern = g3b_uber_kernel<T>;
-    static const hipError_t attr_err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (attr_err != hipSuccess) return (int)attr_err;
-    if (lds > 96 * 1024) return VS_ESHAPE;
-    hipLaunchKernelGGL(kern, dim3(grp.wg_start[grp.n]), dim3(256), lds, s, grp);
-    VS_CHECK_LAUNCH();
+static int bias_partials_launch(const MultiPlan& plan, const vs_wgrad_desc* descs, char* bias_ws, const std::vector<int>& idx, hipStream_t st) {
+    for (size_t at = 0; at < idx.size(); at += G3_BIAS_MAX) {
+        G3BiasGroup grp{};
+        grp.n = (int)std::min<size_t>(G3_BIAS_MAX, idx.size() - at);
+        int blk = 0;
+        for (int j = 0; j < grp.n; ++j) {
+            const int i = idx[at + j];
+            const vs_wgrad_desc& d = descs[i];
+            if (sizeof(T) == 4 && (d.bias_c_ch % 4 || 256 % (d.bias_c_ch / 4))) return VS_ESHAPE;      // fp32 rows: 4 channels per 16-byte fragment (2048 channels do not fit)
+            grp.d[j] = G3BiasDesc{d.bias_g, (double*)(bias_ws + plan.layers[i].bias_off), d.bias_rows, d.bias_c_ch,
+                                  d.bias_c_real, plan.layers[i].bias_nblk, 0};      // parts of one bias gradient: adjacent partial regions
+            grp.blk_start[j] = blk;
+            blk += plan.layers[i].bias_nblk;
+        }
+        for (int j = grp.n; j <= G3_BIAS_MAX; ++j) grp.blk_start[j] = blk;
+        hipLaunchKernelGGL(bias_partial_group_kernel<T>, dim3(blk), dim3(256), 0, st, grp);
+        VS_CHECK_LAUNCH();
+    }
     return VS_OK;
 }
 
-// ---- fp32 parity mode: the 3x3x3 layers of a pass as grouped limb launches (g3x_group_kernel), one grid per channel-block width ----------
+// ---- the plan of a call: one layout, read by vs_conv_wgrad_multi_workspace_bytes and by vs_conv_wgrad_multi -----------------
 static bool f32_limbs_on() {
     const int on = vs_cfg().f32_limbs;
     return on != 0;
 }
-// descriptors of the pass that take the limb path, bias requests stripped (the fp32 branch sums biases with vs_bias_grad_acc); cb: 16 / 8
-// the fp32 mode's grouped launches: 3x3x3 layers on the limb kernels, stride-2 layers on the exact-f32 MFMA body; 16- and 8-channel blocks each
+// the fp32 mode's grouped launches: 3x3x3 layers on the limb kernels (g3x_group_kernel; VS_F32_LIMBS=0: none, they run serially on g3_kernel), stride-2 layers on
+// the exact-f32 MFMA body (g3_group_kernel: their Q limb planes would not fit the LDS); 16- and 8-channel blocks each
 struct F32Grp { int kind, cb; };
 static const F32Grp F32_GROUPS[4] = {{VS_CONV_K3, 16}, {VS_CONV_K3, 8}, {VS_CONV_K2S2, 16}, {VS_CONV_K2S2, 8}};
 // fp32 parity mode: the operand exchange of multi_plan applied BEFORE the layers are sorted into channel-block groups (the exchange changes which operand's
 // width picks the group): a 16 -> 8 layer at full resolution becomes 16 full MFMA rows against 14 two-tap blocks of the 8-channel gradient instead of 8 of 16
 // rows against 27 blocks — 84 instead of 162 limb MFMAs per 32 voxels — and the halo operand is the stored gradient (no normalise before the limb split).
 // Marked with reserved_ = -1 (a field only VS_CONV_UP descriptors use).  VS_WGRAD_SWAP=0 switches it off.
-static std::vector<vs_wgrad_desc> f32_effective(const vs_wgrad_desc* descs, int count) {
-    std::vector<vs_wgrad_desc> eff(descs, descs + count);
-    if (vs_cfg().wgrad_swap == 0 || !f32_limbs_on()) return eff;      // only the grouped limb launches write the exchanged form back (G3RedDesc.swap)
-    for (vs_wgrad_desc& d : eff) {
+static void f32_exchange(std::vector<vs_wgrad_desc>& descs) {
+    if (vs_cfg().wgrad_swap == 0 || !f32_limbs_on()) return;          // only the grouped limb launches write the exchanged form back (G3RedDesc.swap)
+    for (vs_wgrad_desc& d : descs) {
         if (d.kind == VS_CONV_K3 && d.q_stats != nullptr && d.p_stats == nullptr && d.m_ch <= d.c_ch && d.p && d.q) {
             std::swap(d.p, d.q); std::swap(d.p_stats, d.q_stats); std::swap(d.m_ch, d.c_ch); std::swap(d.m_real, d.c_real);
             d.reserved_ = -1;
         }
     }
-    return eff;
 }
 static bool f32_grouped_kind(int kind) { return kind == VS_CONV_K2S2 || (kind == VS_CONV_K3 && f32_limbs_on()); }
-static std::vector<vs_wgrad_desc> f32_limb_subset(const vs_wgrad_desc* descs, int count, int cb, int kind = VS_CONV_K3) {
+// the descriptors of one group, bias requests stripped (the fp32 mode's bias gradients have a region and launches of their own)
+static std::vector<vs_wgrad_desc> f32_group_descs(const std::vector<vs_wgrad_desc>& descs, const F32Grp& gk) {
     std::vector<vs_wgrad_desc> out;
-    if (!f32_grouped_kind(kind)) return out;
-    for (int i = 0; i < count; ++i) {
-        if (descs[i].kind != kind || (descs[i].c_ch >= 16 ? 16 : 8) != cb) continue;
-        vs_wgrad_desc d = descs[i];
+    if (!f32_grouped_kind(gk.kind)) return out;
+    for (const vs_wgrad_desc& src : descs) {
+        if (src.kind != gk.kind || (src.c_ch >= 16 ? 16 : 8) != gk.cb) continue;
+        vs_wgrad_desc d = src;
         d.bias_g = nullptr; d.db = nullptr; d.bias_rows = 0; d.bias_c_ch = 0; d.bias_c_real = 0;
         out.push_back(d);
     }
     return out;
 }
-static inline int f32_limb_target(int cb) { return cb == 16 ? 256 : 512; }       // resident workgroups: one per CU (16-channel blocks: 90 KB of LDS), two (8)
-// stride-2 layers (exact-f32 MFMA, fp32 accumulators): as many workgroups as keep a workgroup at <= 8 tiles — the bound on an accumulator's chain the
-// per-layer plan keeps (g3_plan: VS_WGRAD_F32_TILES)
-static int f32_group_target(const std::vector<vs_wgrad_desc>& sub, int cb, int kind) {
-    if (kind == VS_CONV_K3) return f32_limb_target(cb);
+// workgroups of a group's grid.  Limb kernels: the resident ones, one per CU (16-channel blocks: 90 KB of LDS) or two (8).  Stride-2 layers (exact-f32 MFMA, fp32
+// accumulators): as many as keep a workgroup at <= 8 tiles — the bound on an accumulator's chain the per-layer plan keeps (g3_plan: VS_WGRAD_F32_TILES)
+static int f32_group_target(const std::vector<vs_wgrad_desc>& sub, const F32Grp& gk) {
+    if (gk.kind == VS_CONV_K3) return gk.cb == 16 ? 256 : 512;
     long long work = 0;
     for (const vs_wgrad_desc& d : sub) {
         int cbsz, mbn, cbn, ncb, tps, tyn, txn, ks;
@@ -1754,486 +1870,256 @@ static int f32_group_target(const std::vector<vs_wgrad_desc>& sub, int cb, int k
     }
     return (int)std::min<long long>(std::max<long long>(256, (work + 7) / 8), 1 << 20);
 }
-template <int CB, int KIND>
-static int g3_group_run(const G3Group& grp, hipStream_t s) {
-    using GEO = G3Geo<CB, KIND>;
-    constexpr size_t lds = G3_LDS_Q + (size_t)GEO::QV * CB * 4;
-    auto kern = g3_group_kernel<CB, KIND>;
-    static const hipError_t attr_err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr_err != hipSuccess) return (int)attr_err;
-    hipLaunchKernelGGL(kern, dim3(grp.wg_start[grp.n]), dim3(256), lds, s, grp);
-    VS_CHECK_LAUNCH();
-    return VS_OK;
-}
 
-template <int CB>
-static int g3x_group_run(const G3Group& grp, hipStream_t s) {
-    using GEO = G3Geo<CB, G3_K3>;
-    constexpr size_t lds = G3X_LDS_Q + (size_t)3 * GEO::QV * CB * 2;
-    auto kern = g3x_group_kernel<CB>;
-    static const hipError_t attr_err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr_err != hipSuccess) return (int)attr_err;
-    hipLaunchKernelGGL(kern, dim3(grp.wg_start[grp.n]), dim3(256), lds, s, grp);
-    VS_CHECK_LAUNCH();
-    return VS_OK;
-}
-
-static int f32_limb_group_launch(const std::vector<vs_wgrad_desc>& sub, int cb, float eps, char* ws, size_t ws_bytes, hipStream_t st, int kind = VS_CONV_K3) {
-    if (sub.empty()) return VS_OK;
-    MultiPlan plan;
-    int rc = multi_plan(sub.data(), (int)sub.size(), eps, plan, f32_group_target(sub, cb, kind));
-    if (rc) return rc;
-    if (ws_bytes < plan.bytes) return VS_EWORKSPACE;
-    const int count = (int)sub.size();
-    for (int i = 0; i < count; ++i) {                    // fp32 operands: 4-byte elements under the 32-bit buffer offsets
-        const vs_wgrad_desc& d = sub[i];
-        const long long qv = kind == VS_CONV_K2S2 ? 8 : 1;          // Q grid: the fine one for the stride-2 kinds
-        if ((long long)d.n * d.dp * d.hp * d.wp * d.m_ch * 4 >= 2147483648ll || (long long)d.n * d.dp * d.hp * d.wp * qv * d.c_ch * 4 >= 2147483648ll) return VS_ESHAPE;
-    }
-    std::vector<int> idx(count);
-    for (int i = 0; i < count; ++i) idx[i] = i;
-    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return plan.layers[a].work > plan.layers[b].work; });
-    for (size_t at = 0; at < idx.size(); at += G3_GROUP_MAX) {
-        G3Group grp{};
-        grp.xcd = vs_cfg().wgrad_xcd;                    // >= 2: g3_xcd_rank (the channel-block pairs of a tile on one XCD)
-        grp.n = (int)std::min<size_t>(G3_GROUP_MAX, idx.size() - at);
-        long long wg = 0;
-        for (int j = 0; j < grp.n; ++j) {
-            MultiLayer& L = plan.layers[idx[at + j]];
-            grp.p[j] = L.p;
-            grp.p[j].ws = (float*)(ws + L.ws_off);
-            grp.wg_start[j] = (int)wg;
-            wg += (long long)L.p.mbn * L.p.cbn * L.p.ksplit;
-        }
-        if (wg >= 2147483647ll) return VS_ESHAPE;
-        for (int j = grp.n; j <= G3_GROUP_MAX; ++j) grp.wg_start[j] = (int)wg;
-        if (kind == VS_CONV_K2S2) rc = cb == 16 ? g3_group_run<16, G3_K2S2>(grp, st) : g3_group_run<8, G3_K2S2>(grp, st);
-        else rc = cb == 16 ? g3x_group_run<16>(grp, st) : g3x_group_run<8>(grp, st);
-        if (rc) return rc;
-    }
-    std::vector<G3RedDesc> red;
-    std::vector<int> blocks;
-    for (int i = 0; i < count; ++i) {
-        const MultiLayer& L = plan.layers[i];
-        if (L.primary != i) continue;
-        const long long slab_elems = (long long)L.p.mbn * L.p.cbn * L.ncb * 256;
-        int parts = 1;
-        while (parts < G3_RED_ROWS && parts * 8 < L.total_slabs) parts *= 2;
-        red.push_back(G3RedDesc{(const float*)(ws + L.ws_off), L.dw, L.m_real, L.c_real, L.p.mbn, L.p.cbn, L.total_slabs, L.cbsz, kind == VS_CONV_K2S2 ? 8 : 27, L.ncb, 0, parts, L.swap});
-        blocks.push_back(vs_ceil_div(slab_elems, 256 * (G3_RED_ROWS / parts)));
-    }
-    for (size_t at = 0; at < red.size(); at += G3_RED_MAX) {
-        G3RedGroup grp{};
-        grp.n = (int)std::min<size_t>(G3_RED_MAX, red.size() - at);
-        long long blk = 0;
-        for (int j = 0; j < grp.n; ++j) { grp.d[j] = red[at + j]; grp.blk_start[j] = (int)blk; blk += blocks[at + j]; }
-        if (blk >= 2147483647ll) return VS_ESHAPE;
-        for (int j = grp.n; j <= G3_RED_MAX; ++j) grp.blk_start[j] = (int)blk;
-        hipLaunchKernelGGL(g3_reduce_group_kernel, dim3((unsigned)blk), dim3(64 * G3_RED_ROWS), 0, st, grp);
-        VS_CHECK_LAUNCH();
-    }
-    return VS_OK;
-}
-static size_t f32_limb_group_bytes(const std::vector<vs_wgrad_desc>& sub, int cb, int kind = VS_CONV_K3) {
-    if (sub.empty()) return 0;
-    MultiPlan plan;
-    if (multi_plan(sub.data(), (int)sub.size(), 0.f, plan, f32_group_target(sub, cb, kind))) return 0;
-    return (plan.bytes + 255) / 256 * 256;
-}
-}  // namespace
-
-// the grouped launches with a caller-chosen grid width (target_workgroups; 0 = the default, 512: two per CU).  Internal since round 5: the
-// early, throttled branch it was exported for (round 4) measured slower at every width (profiles/r04_ab_wgrad_early.json).
-static size_t wgrad_multi_workspace_bytes_impl(const vs_wgrad_desc* descs, int count, int dtype, int target_workgroups);
-static int wgrad_multi_impl(const vs_wgrad_desc* descs, int count, void* workspace, size_t workspace_bytes, int dtype,
-                            float eps, int target_workgroups, void* stream);
-extern "C" size_t vs_conv_wgrad_multi_workspace_bytes(const vs_wgrad_desc* descs, int count, int dtype) {
-    return wgrad_multi_workspace_bytes_impl(descs, count, dtype, 0);
-}
-extern "C" int vs_conv_wgrad_multi(const vs_wgrad_desc* descs, int count, void* workspace, size_t workspace_bytes, int dtype,
-                                   float eps, void* stream) {
-    return wgrad_multi_impl(descs, count, workspace, workspace_bytes, dtype, eps, 0, stream);
-}
-
-// fp32 mode: the bias gradients of a pass as the 16-bit path computes them (grouped partial sums, one fixed-order reduction) instead of a zero fill and a float-atomic
-// launch per layer.  The plan is multi_plan's; its bias regions follow its slab regions, so they are rebased to the start of the first one.
-static size_t f32_bias_base(const vs_wgrad_desc* descs, int count, const MultiPlan& plan) {
-    size_t base = (size_t)-1;
-    for (int i = 0; i < count; ++i) if (descs[i].bias_g) base = std::min(base, plan.layers[i].bias_off);
-    return base;
-}
-static size_t f32_bias_bytes(const vs_wgrad_desc* descs, int count, int target_workgroups) {
-    bool any = false;
-    for (int i = 0; i < count; ++i) any = any || descs[i].bias_g != nullptr;
-    if (!any) return 0;
-    MultiPlan plan;
-    if (multi_plan(descs, count, 0.f, plan, target_workgroups)) return 0;
-    return plan.bytes - f32_bias_base(descs, count, plan);
-}
-
-// VS_WGRAD_SLABS descriptors (slabs already computed by vs_conv_k3_bwd_data_wgrad): no grid work, no workspace, one entry of the grouped reduction each
-static std::vector<vs_wgrad_desc> without_slab_descs(const vs_wgrad_desc* descs, int count) {
-    std::vector<vs_wgrad_desc> reg;
-    for (int i = 0; i < count; ++i) if (descs[i].kind != VS_WGRAD_SLABS) reg.push_back(descs[i]);
-    return reg;
-}
 static int slab_desc_validate(const vs_wgrad_desc& d) {
     if (!d.p || !d.dw || d.n <= 0 || ((uintptr_t)d.p & 15)) return VS_EINVAL;
     if (d.bias_g && (!d.db || d.bias_c_real <= 0 || d.bias_c_real > 8 || d.bias_rows != d.n || ((uintptr_t)d.bias_g & 7))) return VS_EINVAL;    // double [n][bias_c_real] partials
     if (d.m_real <= 0 || d.m_real > 8 || d.c_real <= 0 || d.c_real > 8 || d.m_ch != 8 || d.c_ch != 8) return VS_ESHAPE;
     return VS_OK;
 }
-static void slab_red_entry(const vs_wgrad_desc& d, G3RedDesc& r, int& blocks) {
-    r = G3RedDesc{(const float*)d.p, d.dw, d.m_real, d.c_real, 1, 1, d.n, 0x208, 27, 27, 0, G3_RED_ROWS, 0};
-    blocks = 1728 / 64;                                  // 16 vectors of 4 elements per block (g3_reduce_group_kernel)
-}
-// the bias partials a slab descriptor may carry (vs_conv_k3_softmax2_bwd_data): one more entry of the bias kind
-static void slab_bias_entry(const vs_wgrad_desc& d, G3RedDesc& r, int& blocks) {
-    r = G3RedDesc{(const float*)d.bias_g, d.db, 0, d.bias_c_real, 0, 0, d.n, 0, 0, 0, 1, G3_RED_ROWS, 0};
-    blocks = vs_ceil_div(d.bias_c_real, 64);
-}
-static int slab_reduce_only(const std::vector<vs_wgrad_desc>& slabs, hipStream_t st) {
-    std::vector<G3RedDesc> ents;
-    std::vector<int> nbs;
-    for (const vs_wgrad_desc& sd : slabs) {
-        G3RedDesc r;
-        int nb = 0;
-        slab_red_entry(sd, r, nb);
-        ents.push_back(r); nbs.push_back(nb);
-        if (sd.bias_g) { slab_bias_entry(sd, r, nb); ents.push_back(r); nbs.push_back(nb); }
+
+// What a call's descriptors come to, for the size query and the launcher alike.  16-bit storage: one MultiPlan (`multi`), bytes = its bytes.  fp32: four grouped
+// regions (F32_GROUPS, each a MultiPlan of its own), then the serial region the per-layer launches of the other layers share, then the bias region.
+struct WgradPlan {
+    int status = VS_OK;                      // what the descriptors earn before anything is launched; then nothing below is to be used
+    size_t bytes = 0;                        // the workspace
+    std::vector<vs_wgrad_desc> descs;        // the layers: slab descriptors taken out, fp32: operands exchanged (f32_exchange)
+    std::vector<vs_wgrad_desc> slabs;        // the VS_WGRAD_SLABS descriptors: no grid work, no workspace, entries of the grouped reduction
+    MultiPlan multi;                         // 16-bit storage
+    struct Group {                           // fp32: one grouped region
+        std::vector<vs_wgrad_desc> descs;
+        MultiPlan plan;
+        int status = VS_OK;                  // the plan's, or VS_ESHAPE for operands past the 32-bit byte offsets in 4-byte elements
+        size_t off = 0, bytes = 0;           // bytes: 0 for an empty group and for one whose plan failed
+    } group[4];
+    struct SerialUse {                       // fp32: one per-layer launch (vs_conv_wgrad's kernels), in launch order
+        int desc;
+        size_t off;                          // of its slabs inside the serial region: the uses of one weight lie side by side, weights share the region
+        bool first, last;                    // of the uses of its weight; the last one's launch reduces them all
+        bool mismatch;                       // not the geometry of the weight's first use: VS_EINVAL when the launches get here
+    };
+    std::vector<SerialUse> serial;
+    size_t serial_off = 0, serial_bytes = 0;
+    bool any_bias = false;                   // fp32: the bias gradients as the 16-bit path computes them (grouped partial sums, one fixed-order reduction)
+    MultiPlan bias;                          //   multi_plan's bias regions of ALL layers; they follow its slab regions, so they are rebased to the first one's start
+    int bias_status = VS_OK;
+    size_t bias_off = 0, bias_base = 0;      // the region's offset in the workspace; the plan's offset of its first bias region
+
+    int first_status() const {               // any refusal the plan knows of, in the launcher's order
+        if (status) return status;
+        for (const Group& g : group) if (g.status) return g.status;
+        for (const SerialUse& u : serial) if (u.mismatch) return VS_EINVAL;
+        return bias_status;
     }
-    for (size_t at = 0; at < ents.size(); at += G3_RED_MAX) {
-        G3RedGroup grp{};
-        grp.n = (int)std::min<size_t>(G3_RED_MAX, ents.size() - at);
-        long long blk = 0;
-        for (int j = 0; j < grp.n; ++j) {
-            grp.d[j] = ents[at + j];
-            grp.blk_start[j] = (int)blk;
-            blk += nbs[at + j];
+};
+
+static void wgrad_plan_f32(WgradPlan& plan) {
+    for (const vs_wgrad_desc& d : plan.descs) if ((plan.status = multi_validate(d))) return;
+    f32_exchange(plan.descs);
+    const vs_wgrad_desc* descs = plan.descs.data();
+    const int count = (int)plan.descs.size();
+    size_t off = 0;
+    for (int g = 0; g < 4; ++g) {
+        WgradPlan::Group& G = plan.group[g];
+        G.descs = f32_group_descs(plan.descs, F32_GROUPS[g]);
+        G.off = off;
+        if (G.descs.empty()) continue;
+        G.status = multi_plan(G.descs.data(), (int)G.descs.size(), G.plan, f32_group_target(G.descs, F32_GROUPS[g]));
+        if (G.status) continue;
+        G.bytes = (G.plan.bytes + 255) / 256 * 256;
+        off += G.bytes;
+        const long long qv = F32_GROUPS[g].kind == VS_CONV_K2S2 ? 8 : 1;          // Q grid: the fine one for the stride-2 kinds
+        for (const vs_wgrad_desc& d : G.descs)                                    // fp32 operands: 4-byte elements under the 32-bit buffer offsets
+            if ((long long)d.n * d.dp * d.hp * d.wp * d.m_ch * 4 >= 2147483648ll || (long long)d.n * d.dp * d.hp * d.wp * qv * d.c_ch * 4 >= 2147483648ll) G.status = VS_ESHAPE;
+    }
+    // the other layers: serial per-layer launches share one region; the uses of one weight need theirs side by side
+    plan.serial_off = off;
+    const std::vector<int> first = dw_first_use(descs, count);
+    for (int i = 0; i < count; ++i) {
+        if (f32_grouped_kind(descs[i].kind) || first[i] != i) continue;
+        int last = i;
+        for (int j = i + 1; j < count; ++j) if (first[j] == i) last = j;
+        size_t sum = 0;
+        for (int j = i; j <= last; ++j) {
+            const vs_wgrad_desc& d = descs[j];
+            if (first[j] != i) continue;
+            const bool mismatch = d.m_ch != descs[i].m_ch || d.c_ch != descs[i].c_ch || d.kind != descs[i].kind || d.m_real != descs[i].m_real || d.c_real != descs[i].c_real;
+            plan.serial.push_back(WgradPlan::SerialUse{j, sum, j == i, j == last, mismatch});
+            // slabs of the next part start right behind this part's: its plan is the fp32 plan vs_conv_wgrad_workspace_bytes sizes
+            sum += vs_conv_wgrad_workspace_bytes(d.n, d.dp, d.hp, d.wp, d.m_ch, d.c_ch, d.kind);
         }
-        for (int j = grp.n; j <= G3_RED_MAX; ++j) grp.blk_start[j] = (int)blk;
-        hipLaunchKernelGGL(g3_reduce_group_kernel, dim3((unsigned)blk), dim3(64 * G3_RED_ROWS), 0, st, grp);
-        VS_CHECK_LAUNCH();
+        plan.serial_bytes = std::max(plan.serial_bytes, sum);
+    }
+    plan.serial_bytes = (plan.serial_bytes + 255) / 256 * 256;
+    plan.bias_off = plan.serial_off + plan.serial_bytes;
+    plan.bytes = plan.bias_off;
+    for (int i = 0; i < count; ++i) plan.any_bias = plan.any_bias || descs[i].bias_g != nullptr;
+    if (!plan.any_bias || (plan.bias_status = multi_plan(descs, count, plan.bias))) return;
+    plan.bias_base = (size_t)-1;
+    for (int i = 0; i < count; ++i) if (descs[i].bias_g) plan.bias_base = std::min(plan.bias_base, plan.bias.layers[i].bias_off);
+    plan.bytes += plan.bias.bytes - plan.bias_base;
+}
+
+static WgradPlan wgrad_plan(const vs_wgrad_desc* descs, int count, int dtype) {
+    WgradPlan plan;
+    if (!descs || count <= 0) { plan.status = VS_EINVAL; return plan; }
+    plan.descs.reserve(count);
+    for (int i = 0; i < count && !plan.status; ++i) {                // the one place slab descriptors are told from layers
+        if (descs[i].kind != VS_WGRAD_SLABS) { plan.descs.push_back(descs[i]); continue; }
+        if (dtype == VS_F32) plan.status = VS_EINVAL;
+        else plan.status = slab_desc_validate(descs[i]);
+        for (int j = 0; j < count && !plan.status; ++j) if (j != i && descs[j].dw == descs[i].dw) plan.status = VS_EINVAL;      // a slab descriptor is the only contribution to its gradient
+        plan.slabs.push_back(descs[i]);
+    }
+    if (plan.status) return plan;
+    if (plan.descs.empty()) { plan.bytes = 256; return plan; }      // nothing but reductions: a token workspace (the caller passes a non-null pointer)
+    if (dtype == VS_F32) wgrad_plan_f32(plan);
+    else if (!(plan.status = multi_plan(plan.descs.data(), (int)plan.descs.size(), plan.multi, 0, true))) plan.bytes = plan.multi.bytes;
+    return plan;
+}
+
+// ---- the launches of a planned call, step by step -------------------------------------------------------------------------------------------
+// fp32 parity mode.  The 3x3x3 layers: grouped limb launches on the bf16 matrix cores — with per-layer launches the 16 small layers of a step cost 30-47 us each
+// (one tile per workgroup under fixed prologue / slab costs); the stride-2 kinds likewise on the exact-f32 body; each group reduces its own slabs.
+static int launch_f32_group(const WgradPlan::Group& G, const F32Grp& gk, char* ws, float eps, hipStream_t st) {
+    std::vector<int> idx(G.descs.size());
+    for (size_t i = 0; i < idx.size(); ++i) idx[i] = (int)i;
+    int rc = g3_groups_run(G.plan, G.descs.data(), ws, eps, layers_by_work(G.plan, idx), false, [&](const G3Group& grp, size_t) {
+        const int wgs = grp.wg_start[grp.n];
+        if (gk.kind == VS_CONV_K2S2)
+            return gk.cb == 16 ? g3_launch<g3_group_kernel<16, G3_K2S2>, G3_ATTR_ALWAYS>(wgs, 1, g3_lds<16, G3_K2S2>(), st, grp)
+                               : g3_launch<g3_group_kernel<8, G3_K2S2>, G3_ATTR_ALWAYS>(wgs, 1, g3_lds<8, G3_K2S2>(), st, grp);
+        return gk.cb == 16 ? g3_launch<g3x_group_kernel<16>, G3_ATTR_ALWAYS>(wgs, 1, g3x_lds<16>(), st, grp)
+                           : g3_launch<g3x_group_kernel<8>, G3_ATTR_ALWAYS>(wgs, 1, g3x_lds<8>(), st, grp);
+    });
+    if (rc) return rc;
+    RedList red;
+    red.add_plan(G.plan, G.descs.data(), ws, nullptr);
+    return red.launch(st);
+}
+static int launch_f32(const WgradPlan& plan, char* ws, size_t ws_bytes, float eps, hipStream_t st) {
+    for (int g = 0; g < 4; ++g) {
+        const WgradPlan::Group& G = plan.group[g];
+        if (ws_bytes < G.off + G.bytes) return VS_EWORKSPACE;
+        if (G.status) return G.status;
+        if (G.descs.empty()) continue;
+        int rc = launch_f32_group(G, F32_GROUPS[g], ws + G.off, eps, st);
+        if (rc) return rc;
+    }
+    // the layers outside the groups, one launch each; the last use of a weight reduces the slabs of all its uses
+    int prior = 0;
+    for (const WgradPlan::SerialUse& u : plan.serial) {
+        const vs_wgrad_desc& d = plan.descs[u.desc];
+        if (u.mismatch) return VS_EINVAL;
+        if (u.first) prior = 0;
+        int slabs = 0;
+        int rc = wgrad_single(d.p, d.p_stats, d.q, d.q_stats, d.dw, ws + plan.serial_off + u.off, ws_bytes - plan.serial_off - u.off, d.n, d.dp, d.hp, d.wp,
+                              d.m_ch, d.c_ch, d.m_real, d.c_real, d.kind, VS_F32, eps, st, u.last ? prior : -1, &slabs);
+        if (rc) return rc;
+        prior += slabs;
+    }
+    if (!plan.any_bias) return VS_OK;
+    if (plan.bias_status) return plan.bias_status;
+    if (ws_bytes < plan.bytes) return VS_EWORKSPACE;
+    char* bias_ws = ws + plan.bias_off - plan.bias_base;
+    std::vector<int> idx;
+    for (size_t i = 0; i < plan.descs.size(); ++i) if (plan.descs[i].bias_g) idx.push_back((int)i);
+    int rc = bias_partials_launch<float>(plan.bias, plan.descs.data(), bias_ws, idx, st);
+    if (rc) return rc;
+    RedList red;
+    red.add_plan(plan.bias, plan.descs.data(), nullptr, bias_ws);
+    return red.launch(st);
+}
+
+// 16-bit storage, every bucket in one grid (G3_GROUP_MAX entries per grid, longest workgroups first); the bias gradients' partial sums ride behind the weight
+// layers (short workgroups) unless a layer's own launch folds them in or their row count passes the 31 bits of a G3Params field
+static int launch_uber(const WgradPlan& plan, char* ws, float eps, bool f16, hipStream_t st) {
+    const MultiPlan& mp = plan.multi;
+    const int count = (int)plan.descs.size();
+    std::vector<int> idx(count);
+    for (int i = 0; i < count; ++i) idx[i] = i;
+    auto key = [&](int a) { const MultiLayer& L = mp.layers[a]; return (double)L.work * g3v_tile_cost(g3v_of(L.cbsz, L.kind, L.p.mp != 0, L.big)); };
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return key(a) > key(b); });
+    for (int i = 0; i < count; ++i)
+        if (plan.descs[i].bias_g && plan.descs[i].bias_rows < 2147483647ll && !mp.layers[i].bias_fold) idx.push_back(-(i + 1));
+    return g3_groups_run(mp, plan.descs.data(), ws, eps, idx, true, [&](const G3Group& grp, size_t lds) {
+        return f16 ? g3_launch<g3b_uber_kernel<vs_half>, G3_ATTR_96K>(grp.wg_start[grp.n], 1, lds, st, grp)
+                   : g3_launch<g3b_uber_kernel<unsigned short>, G3_ATTR_96K>(grp.wg_start[grp.n], 1, lds, st, grp);
+    });
+}
+// VS_WGRAD_UBER=0: one grid per bucket.  The instantiations of g3b_group_kernel, listed in the order the object file has always carried them (the compiler numbers
+// its labels by it, and tools/isa_diff.py compares the device code of two trees text for text); launch_buckets looks its kernel up.
+struct G3Bucket {
+    int kind, cb;
+    bool mp, f16;
+    int (*launch)(int, int, size_t, hipStream_t, const G3Group&);
+    size_t lds;
+};
+#define G3_BUCKET(T, CB, KIND, MP) \
+    {KIND == G3_UP ? VS_CONV_UP : KIND, CB, MP, std::is_same<T, vs_half>::value, g3_launch<g3b_group_kernel<CB, KIND, T, MP>, G3_ATTR_ABOVE_64K, G3Group>, g3b_lds<CB, KIND>()}
+static const G3Bucket G3_BUCKETS[] = {
+    G3_BUCKET(vs_half, 16, G3_UP, false),          G3_BUCKET(unsigned short, 16, G3_UP, false),          // the composed Up block: 16-channel Q blocks only
+    G3_BUCKET(vs_half, 16, G3_K3, true),           G3_BUCKET(vs_half, 8, G3_K3, true),                   // the M-packed 3x3x3 layers (8 stored P channels)
+    G3_BUCKET(unsigned short, 16, G3_K3, true),    G3_BUCKET(unsigned short, 8, G3_K3, true),
+    G3_BUCKET(vs_half, 16, G3_K3, false),          G3_BUCKET(vs_half, 8, G3_K3, false),
+    G3_BUCKET(vs_half, 16, G3_K2S2, false),        G3_BUCKET(vs_half, 8, G3_K2S2, false),
+    G3_BUCKET(unsigned short, 16, G3_K3, false),   G3_BUCKET(unsigned short, 8, G3_K3, false),
+    G3_BUCKET(unsigned short, 16, G3_K2S2, false), G3_BUCKET(unsigned short, 8, G3_K2S2, false),
+};
+#undef G3_BUCKET
+static int launch_buckets(const WgradPlan& plan, char* ws, float eps, bool f16, hipStream_t st) {
+    const MultiPlan& mp = plan.multi;
+    for (int bucket = 0; bucket < 8; ++bucket) {         // (16 | 8 channel blocks) x (3x3x3, stride 2, composed Up, 3x3x3 M-packed), launched in this order
+        const int cbsz = (bucket & 1) ? 8 : 16, kind = bucket < 2 || bucket >= 6 ? VS_CONV_K3 : (bucket < 4 ? VS_CONV_K2S2 : VS_CONV_UP);
+        const bool mpb = bucket >= 6;
+        const G3Bucket* kern = nullptr;
+        for (const G3Bucket& b : G3_BUCKETS) if (b.kind == kind && b.cb == cbsz && b.mp == mpb && b.f16 == f16) kern = &b;
+        std::vector<int> idx;
+        for (size_t i = 0; i < mp.layers.size(); ++i)
+            if (mp.layers[i].cbsz == cbsz && mp.layers[i].kind == kind && (mp.layers[i].p.mp != 0) == mpb) idx.push_back((int)i);
+        int rc = g3_groups_run(mp, plan.descs.data(), ws, eps, layers_by_work(mp, idx), false, [&](const G3Group& grp, size_t) {
+            return kern ? kern->launch(grp.wg_start[grp.n], 1, kern->lds, st, grp) : (int)VS_ESHAPE;
+        });
+        if (rc) return rc;
     }
     return VS_OK;
 }
+// 16-bit storage: the grids, the bias partial sums that did not ride in them, then every reduction of the call in one grid
+static int launch_16bit(const WgradPlan& plan, char* ws, float eps, bool f16, hipStream_t st) {
+    const int uber = vs_cfg().wgrad_uber;       // read per call (the tests run both forms)
+    int rc = uber ? launch_uber(plan, ws, eps, f16, st) : launch_buckets(plan, ws, eps, f16, st);
+    if (rc) return rc;
+    std::vector<int> idx;
+    for (size_t i = 0; i < plan.descs.size(); ++i)
+        if (plan.descs[i].bias_g && !plan.multi.layers[i].bias_fold && (!uber || plan.descs[i].bias_rows >= 2147483647ll)) idx.push_back((int)i);
+    rc = f16 ? bias_partials_launch<vs_half>(plan.multi, plan.descs.data(), ws, idx, st) : bias_partials_launch<unsigned short>(plan.multi, plan.descs.data(), ws, idx, st);
+    if (rc) return rc;
+    RedList red;
+    red.add_plan(plan.multi, plan.descs.data(), ws, ws);
+    for (const vs_wgrad_desc& sd : plan.slabs) red.add_slab_desc(sd);      // the layers whose slabs a backward-data launch wrote
+    return red.launch(st);
+}
+}  // namespace
 
-static size_t wgrad_multi_workspace_bytes_impl(const vs_wgrad_desc* descs, int count, int dtype, int target_workgroups) {
-    if (!descs || count <= 0 || target_workgroups < 0) return 0;
-    std::vector<vs_wgrad_desc> reg_only;
-    {
-        bool any = false;
-        for (int i = 0; i < count; ++i) any = any || descs[i].kind == VS_WGRAD_SLABS;
-        if (any) {
-            if (dtype == VS_F32) return 0;
-            reg_only = without_slab_descs(descs, count);
-            if (reg_only.empty()) return 256;               // nothing but reductions: a token workspace (the caller passes a non-null pointer)
-            descs = reg_only.data(); count = (int)reg_only.size();
-        }
-    }
-    std::vector<vs_wgrad_desc> eff32;
-    if (dtype == VS_F32) {                        // serial per-layer launches share one region; the uses of one weight need theirs side by side
-        eff32 = f32_effective(descs, count);
-        descs = eff32.data();
-        // the 3x3x3 layers of the limb path come first: two grouped regions (16- / 8-channel blocks); the serial region of the other layers follows
-        size_t limb_bytes = 0;
-        for (const F32Grp& gk : F32_GROUPS) limb_bytes += f32_limb_group_bytes(f32_limb_subset(descs, count, gk.cb, gk.kind), gk.cb, gk.kind);
-        size_t mx = 0;
-        for (int i = 0; i < count; ++i) {
-            if (f32_grouped_kind(descs[i].kind)) continue;
-            bool first = true;
-            for (int j = 0; j < i; ++j) first = first && descs[j].dw != descs[i].dw;
-            if (!first) continue;
-            size_t sum = 0;
-            for (int j = i; j < count; ++j)
-                if (descs[j].dw == descs[i].dw)
-                    sum += vs_conv_wgrad_workspace_bytes(descs[j].n, descs[j].dp, descs[j].hp, descs[j].wp, descs[j].m_ch, descs[j].c_ch, descs[j].kind);
-            mx = std::max(mx, sum);
-        }
-        return limb_bytes + (mx + 255) / 256 * 256 + f32_bias_bytes(descs, count, target_workgroups);
-    }
-    MultiPlan plan;
-    if (multi_plan(descs, count, 0.f, plan, target_workgroups, true)) return 0;
-    return plan.bytes;
+extern "C" size_t vs_conv_wgrad_multi_workspace_bytes(const vs_wgrad_desc* descs, int count, int dtype) {
+    const WgradPlan plan = wgrad_plan(descs, count, dtype);
+    return plan.first_status() ? 0 : plan.bytes;
 }
 
-static int wgrad_multi_impl(const vs_wgrad_desc* descs, int count, void* workspace, size_t workspace_bytes, int dtype,
-                            float eps, int target_workgroups, void* stream) {
-    if (!descs || count <= 0 || !workspace || target_workgroups < 0) return VS_EINVAL;
+extern "C" int vs_conv_wgrad_multi(const vs_wgrad_desc* descs, int count, void* workspace, size_t workspace_bytes, int dtype,
+                                   float eps, void* stream) {
+    if (!descs || count <= 0 || !workspace) return VS_EINVAL;
     if (!vs_dtype_ok(dtype)) return VS_EDTYPE;
-    const bool f16 = dtype == VS_F16;
     hipStream_t st = (hipStream_t)stream;
-    std::vector<vs_wgrad_desc> reg_only, slab_descs;
-    for (int i = 0; i < count; ++i)
-        if (descs[i].kind == VS_WGRAD_SLABS) {
-            if (dtype == VS_F32) return VS_EINVAL;
-            int rc = slab_desc_validate(descs[i]);
-            if (rc) return rc;
-            for (int j = 0; j < count; ++j) if (j != i && descs[j].dw == descs[i].dw) return VS_EINVAL;      // a slab descriptor is the only contribution to its gradient
-            slab_descs.push_back(descs[i]);
-        }
-    if (!slab_descs.empty()) {
-        reg_only = without_slab_descs(descs, count);
-        if (reg_only.empty()) return slab_reduce_only(slab_descs, st);
-        descs = reg_only.data(); count = (int)reg_only.size();
+    const WgradPlan plan = wgrad_plan(descs, count, dtype);
+    if (plan.status) return plan.status;
+    if (plan.descs.empty()) {                                      // slab descriptors alone
+        RedList red;
+        for (const vs_wgrad_desc& sd : plan.slabs) red.add_slab_desc(sd);
+        return red.launch(st);
     }
-    std::vector<vs_wgrad_desc> eff32;
-    if (dtype == VS_F32) {
-        for (int i = 0; i < count; ++i) {
-            int rc = multi_validate(descs[i]);
-            if (rc) return rc;
-        }
-        eff32 = f32_effective(descs, count);
-        descs = eff32.data();
-        // the 3x3x3 layers: grouped limb launches on the bf16 matrix cores (g3x_group_kernel) — with per-layer launches the 16 small layers of a
-        // step cost 30-47 us each (one tile per workgroup under fixed prologue / slab costs); the stride-2 kinds: per-layer exact-f32 kernels
-        {
-            char* wsp = (char*)workspace;
-            size_t left = workspace_bytes;
-            for (const F32Grp& gk : F32_GROUPS) {
-                const std::vector<vs_wgrad_desc> sub = f32_limb_subset(descs, count, gk.cb, gk.kind);
-                const size_t need = f32_limb_group_bytes(sub, gk.cb, gk.kind);
-                if (need > left) return VS_EWORKSPACE;
-                int rc = f32_limb_group_launch(sub, gk.cb, eps, wsp, left, st, gk.kind);
-                if (rc) return rc;
-                wsp += need; left -= need;
-            }
-            workspace = wsp; workspace_bytes = left;
-        }
-        for (int i = 0; i < count; ++i) {
-            if (f32_grouped_kind(descs[i].kind)) continue;
-            bool first = true;
-            for (int j = 0; j < i; ++j) first = first && descs[j].dw != descs[i].dw;
-            if (!first) continue;
-            int last = i;
-            for (int j = i + 1; j < count; ++j) if (descs[j].dw == descs[i].dw) last = j;
-            // the uses of this weight, slabs side by side; the last one's launch reduces them all
-            size_t off = 0;
-            int prior = 0;
-            for (int j = i; j <= last; ++j) {
-                const vs_wgrad_desc& d = descs[j];
-                if (d.dw != descs[i].dw) continue;
-                if (d.m_ch != descs[i].m_ch || d.c_ch != descs[i].c_ch || d.kind != descs[i].kind || d.m_real != descs[i].m_real || d.c_real != descs[i].c_real)
-                    return VS_EINVAL;
-                int slabs = 0;
-                int rc = wgrad_single(d.p, d.p_stats, d.q, d.q_stats, d.dw, (char*)workspace + off, workspace_bytes - off, d.n, d.dp, d.hp, d.wp,
-                                      d.m_ch, d.c_ch, d.m_real, d.c_real, d.kind, dtype, eps, stream, j == last ? prior : -1, &slabs);
-                if (rc) return rc;
-                off += vs_conv_wgrad_workspace_bytes(d.n, d.dp, d.hp, d.wp, d.m_ch, d.c_ch, d.kind) / 1;
-                // slabs of the next part start right behind this part's: its plan is the fp32 plan vs_conv_wgrad_workspace_bytes sizes
-                prior += slabs;
-            }
-        }
-        bool any_bias = false;
-        for (int i = 0; i < count; ++i) any_bias = any_bias || descs[i].bias_g != nullptr;
-        if (any_bias) {
-            size_t mx = 0;                               // the serial region's size, as the workspace query counts it
-            for (int i = 0; i < count; ++i) {
-                if (f32_grouped_kind(descs[i].kind)) continue;
-                bool first = true;
-                for (int j = 0; j < i; ++j) first = first && descs[j].dw != descs[i].dw;
-                if (!first) continue;
-                size_t sum = 0;
-                for (int j = i; j < count; ++j)
-                    if (descs[j].dw == descs[i].dw)
-                        sum += vs_conv_wgrad_workspace_bytes(descs[j].n, descs[j].dp, descs[j].hp, descs[j].wp, descs[j].m_ch, descs[j].c_ch, descs[j].kind);
-                mx = std::max(mx, sum);
-            }
-            mx = (mx + 255) / 256 * 256;
-            MultiPlan plan;
-            int rc = multi_plan(descs, count, eps, plan, target_workgroups);
-            if (rc) return rc;
-            const size_t base = f32_bias_base(descs, count, plan);
-            if (workspace_bytes < mx + (plan.bytes - base)) return VS_EWORKSPACE;
-            char* bws = (char*)workspace + mx;
-            std::vector<int> idx;
-            for (int i = 0; i < count; ++i) if (descs[i].bias_g) idx.push_back(i);
-            for (size_t at = 0; at < idx.size(); at += G3_BIAS_MAX) {
-                G3BiasGroup grp{};
-                grp.n = (int)std::min<size_t>(G3_BIAS_MAX, idx.size() - at);
-                int blk = 0;
-                for (int j = 0; j < grp.n; ++j) {
-                    const int i = idx[at + j];
-                    const vs_wgrad_desc& d = descs[i];
-                    if (d.bias_c_ch % 4 || 256 % (d.bias_c_ch / 4)) return VS_ESHAPE;
-                    grp.d[j] = G3BiasDesc{d.bias_g, (double*)(bws + (plan.layers[i].bias_off - base)), d.bias_rows, d.bias_c_ch, d.bias_c_real, plan.layers[i].bias_nblk, 0};
-                    grp.blk_start[j] = blk;
-                    blk += plan.layers[i].bias_nblk;
-                }
-                for (int j = grp.n; j <= G3_BIAS_MAX; ++j) grp.blk_start[j] = blk;
-                hipLaunchKernelGGL(bias_partial_group_kernel<float>, dim3(blk), dim3(256), 0, st, grp);
-                VS_CHECK_LAUNCH();
-            }
-            std::vector<G3RedDesc> red;
-            for (int i = 0; i < count; ++i)
-                if (descs[i].bias_g && plan.layers[i].bias_primary == i)
-                    red.push_back(G3RedDesc{(const float*)(bws + (plan.layers[i].bias_off - base)), descs[i].db, 0, descs[i].bias_c_real, 0, 0, plan.layers[i].bias_total_blk, 0, 0, 0, 1, G3_RED_ROWS});
-            for (size_t at = 0; at < red.size(); at += G3_RED_MAX) {
-                G3RedGroup grp{};
-                grp.n = (int)std::min<size_t>(G3_RED_MAX, red.size() - at);
-                long long blk = 0;
-                for (int j = 0; j < grp.n; ++j) { grp.d[j] = red[at + j]; grp.blk_start[j] = (int)blk; blk += vs_ceil_div(red[at + j].c_real, 64); }
-                for (int j = grp.n; j <= G3_RED_MAX; ++j) grp.blk_start[j] = (int)blk;
-                hipLaunchKernelGGL(g3_reduce_group_kernel, dim3((unsigned)blk), dim3(64 * G3_RED_ROWS), 0, st, grp);
-                VS_CHECK_LAUNCH();
-            }
-        }
-        return VS_OK;
-    }
-    MultiPlan plan;
-    int rc = multi_plan(descs, count, eps, plan, target_workgroups, true);
-    if (rc) return rc;
+    if (dtype == VS_F32) return launch_f32(plan, (char*)workspace, workspace_bytes, eps, st);
     if (workspace_bytes < plan.bytes) return VS_EWORKSPACE;
     if ((uintptr_t)workspace % 16) return VS_EINVAL;
-    char* ws = (char*)workspace;
-
-    // ---- every bucket in one grid (G3_GROUP_MAX layers per grid, longest workgroups first); VS_WGRAD_UBER=0: one grid per bucket ----
-    const int uber = vs_cfg().wgrad_uber;       // read per call (the tests run both forms)
-    if (uber) {
-        std::vector<int> idx(count);
-        for (int i = 0; i < count; ++i) idx[i] = i;
-        auto key = [&](int a) { const MultiLayer& L = plan.layers[a]; return (double)L.work * g3v_tile_cost(g3v_of(L.cbsz, L.kind, L.p.mp != 0, L.big)); };
-        std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return key(a) > key(b); });
-        for (int i = 0; i < count; ++i)                      // the bias gradients' partial sums: entries -(i + 1), behind the weight layers (short workgroups)
-            if (descs[i].bias_g && descs[i].bias_rows < 2147483647ll && !plan.layers[i].bias_fold) idx.push_back(-(i + 1));
-        for (size_t at = 0; at < idx.size(); at += G3_GROUP_MAX) {
-            G3Group grp{};
-            const int xcd_walk = vs_cfg().wgrad_xcd;
-            grp.xcd = xcd_walk;
-            grp.n = (int)std::min<size_t>(G3_GROUP_MAX, idx.size() - at);
-            long long wg = 0;
-            size_t lds = 0;
-            for (int j = 0; j < grp.n; ++j) {
-                if (idx[at + j] < 0) {
-                    const int i = -idx[at + j] - 1;
-                    const vs_wgrad_desc& d = descs[i];
-                    G3Params q{};
-                    q.P = d.bias_g; q.ws = (float*)(ws + plan.layers[i].bias_off);
-                    q.total_tiles = (int)d.bias_rows; q.Mch = d.bias_c_ch; q.Cch = d.bias_c_real; q.ksplit = plan.layers[i].bias_nblk;
-                    q.mbn = 1; q.cbn = 1; q.variant = G3V_BIAS;
-                    grp.p[j] = q;
-                    lds = std::max(lds, (size_t)256 * 8 * sizeof(float));
-                    grp.wg_start[j] = (int)wg;
-                    wg += q.ksplit;
-                    continue;
-                }
-                MultiLayer& L = plan.layers[idx[at + j]];
-                if (L.kind == VS_CONV_UP && L.cbsz != 16) return VS_ESHAPE;
-                grp.p[j] = L.p;
-                grp.p[j].ws = (float*)(ws + L.ws_off);
-                grp.p[j].variant = g3v_of(L.cbsz, L.kind, L.p.mp != 0, L.big);
-                lds = std::max(lds, g3v_lds(grp.p[j].variant));
-                grp.wg_start[j] = (int)wg;
-                wg += (long long)L.p.mbn * L.p.cbn * L.p.ksplit;
-            }
-            if (wg >= 2147483647ll) return VS_ESHAPE;
-            for (int j = grp.n; j <= G3_GROUP_MAX; ++j) grp.wg_start[j] = (int)wg;
-            rc = f16 ? g3b_uber_run<vs_half>(grp, lds, st) : g3b_uber_run<unsigned short>(grp, lds, st);
-            if (rc) return rc;
-        }
-    } else
-    for (int bucket = 0; bucket < 8; ++bucket) {
-        const int cbsz = (bucket & 1) ? 8 : 16, kind = bucket < 2 || bucket >= 6 ? VS_CONV_K3 : (bucket < 4 ? VS_CONV_K2S2 : VS_CONV_UP);
-        const bool mpb = bucket >= 6;                    // the M-packed 3x3x3 layers (8 stored P channels): kernel instantiations of their own
-        std::vector<int> idx;
-        for (int i = 0; i < count; ++i)
-            if (plan.layers[i].cbsz == cbsz && plan.layers[i].kind == kind && (plan.layers[i].p.mp != 0) == mpb) idx.push_back(i);
-        std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return plan.layers[a].work > plan.layers[b].work; });
-        for (size_t at = 0; at < idx.size(); at += G3_GROUP_MAX) {
-            G3Group grp{};
-            const int xcd_walk = vs_cfg().wgrad_xcd;
-            grp.xcd = xcd_walk;
-            grp.n = (int)std::min<size_t>(G3_GROUP_MAX, idx.size() - at);
-            long long wg = 0;
-            for (int j = 0; j < grp.n; ++j) {
-                MultiLayer& L = plan.layers[idx[at + j]];
-                grp.p[j] = L.p;
-                grp.p[j].ws = (float*)(ws + L.ws_off);
-                grp.wg_start[j] = (int)wg;
-                wg += (long long)L.p.mbn * L.p.cbn * L.p.ksplit;
-            }
-            if (wg >= 2147483647ll) return VS_ESHAPE;
-            for (int j = grp.n; j <= G3_GROUP_MAX; ++j) grp.wg_start[j] = (int)wg;
-            if (kind == VS_CONV_UP) {
-                if (cbsz != 16) return VS_ESHAPE;
-                rc = f16 ? g3b_group_run<vs_half, 16, G3_UP>(grp, st) : g3b_group_run<unsigned short, 16, G3_UP>(grp, st);
-            } else if (mpb) {
-                if (f16) rc = cbsz == 16 ? g3b_group_run<vs_half, 16, G3_K3, true>(grp, st) : g3b_group_run<vs_half, 8, G3_K3, true>(grp, st);
-                else rc = cbsz == 16 ? g3b_group_run<unsigned short, 16, G3_K3, true>(grp, st) : g3b_group_run<unsigned short, 8, G3_K3, true>(grp, st);
-            } else if (f16) {
-                if (kind == VS_CONV_K3) rc = cbsz == 16 ? g3b_group_run<vs_half, 16, G3_K3>(grp, st) : g3b_group_run<vs_half, 8, G3_K3>(grp, st);
-                else rc = cbsz == 16 ? g3b_group_run<vs_half, 16, G3_K2S2>(grp, st) : g3b_group_run<vs_half, 8, G3_K2S2>(grp, st);
-            } else {
-                if (kind == VS_CONV_K3) rc = cbsz == 16 ? g3b_group_run<unsigned short, 16, G3_K3>(grp, st) : g3b_group_run<unsigned short, 8, G3_K3>(grp, st);
-                else rc = cbsz == 16 ? g3b_group_run<unsigned short, 16, G3_K2S2>(grp, st) : g3b_group_run<unsigned short, 8, G3_K2S2>(grp, st);
-            }
-            if (rc) return rc;
-        }
-    }
-    // ---- bias partials (in the all-buckets grid above when it is on) ----
-    {
-        std::vector<int> idx;
-        for (int i = 0; i < count; ++i) if (descs[i].bias_g && !plan.layers[i].bias_fold && (!uber || descs[i].bias_rows >= 2147483647ll)) idx.push_back(i);
-        for (size_t at = 0; at < idx.size(); at += G3_BIAS_MAX) {
-            G3BiasGroup grp{};
-            grp.n = (int)std::min<size_t>(G3_BIAS_MAX, idx.size() - at);
-            int blk = 0;
-            for (int j = 0; j < grp.n; ++j) {
-                const int i = idx[at + j];
-                const vs_wgrad_desc& d = descs[i];
-                grp.d[j] = G3BiasDesc{d.bias_g, (double*)(ws + plan.layers[i].bias_off), d.bias_rows, d.bias_c_ch,
-                                      d.bias_c_real, plan.layers[i].bias_nblk, 0};      // parts of one bias gradient: adjacent partial regions
-                grp.blk_start[j] = blk;
-                blk += plan.layers[i].bias_nblk;
-            }
-            for (int j = grp.n; j <= G3_BIAS_MAX; ++j) grp.blk_start[j] = blk;
-            if (f16) hipLaunchKernelGGL(bias_partial_group_kernel<vs_half>, dim3(blk), dim3(256), 0, st, grp);
-            else hipLaunchKernelGGL(bias_partial_group_kernel<unsigned short>, dim3(blk), dim3(256), 0, st, grp);
-            VS_CHECK_LAUNCH();
-        }
-    }
-    // ---- every reduction in one grid (G3_RED_MAX entries per launch) ----
-    {
-        std::vector<G3RedDesc> red;
-        std::vector<int> blocks;
-        for (int i = 0; i < count; ++i) {
-            const MultiLayer& L = plan.layers[i];
-            if (L.primary == i) {                        // one reduction per gradient, over the slabs of all its parts
-                const long long slab_elems = (long long)L.p.mbn * L.p.cbn * L.ncb * 256;
-                // a partition sums up to 8 slabs in one round of independent loads: no more partitions (= threads, waves) than that needs
-                int parts = 1;
-                while (parts < G3_RED_ROWS && parts * 8 < L.total_slabs) parts *= 2;
-                red.push_back(G3RedDesc{(const float*)(ws + L.ws_off), L.dw, L.m_real, L.c_real, L.p.mbn, L.p.cbn, L.total_slabs, L.cbsz | (L.p.mp ? 0x100 : 0),
-                                        L.kind != VS_CONV_K2S2 ? 27 : 8, L.ncb, 0, parts, L.swap});
-                blocks.push_back(vs_ceil_div(slab_elems, 256 * (G3_RED_ROWS / parts)));
-            }
-            if (descs[i].bias_g && L.bias_primary == i) {
-                red.push_back(G3RedDesc{(const float*)(ws + L.bias_off), descs[i].db, 0, descs[i].bias_c_real, 0, 0, L.bias_total_blk, 0, 0, 0, 1, G3_RED_ROWS});
-                blocks.push_back(vs_ceil_div(descs[i].bias_c_real, 64));
-            }
-        }
-        for (const vs_wgrad_desc& sd : slab_descs) {      // the layers whose slabs a backward-data launch wrote
-            G3RedDesc r;
-            int nb = 0;
-            slab_red_entry(sd, r, nb);
-            red.push_back(r);
-            blocks.push_back(nb);
-            if (sd.bias_g) { slab_bias_entry(sd, r, nb); red.push_back(r); blocks.push_back(nb); }
-        }
-        for (size_t at = 0; at < red.size(); at += G3_RED_MAX) {
-            G3RedGroup grp{};
-            grp.n = (int)std::min<size_t>(G3_RED_MAX, red.size() - at);
-            long long blk = 0;
-            for (int j = 0; j < grp.n; ++j) {
-                grp.d[j] = red[at + j];
-                grp.blk_start[j] = (int)blk;
-                blk += blocks[at + j];
-            }
-            if (blk >= 2147483647ll) return VS_ESHAPE;
-            for (int j = grp.n; j <= G3_RED_MAX; ++j) grp.blk_start[j] = (int)blk;
-            hipLaunchKernelGGL(g3_reduce_group_kernel, dim3((unsigned)blk), dim3(64 * G3_RED_ROWS), 0, st, grp);
-            VS_CHECK_LAUNCH();
-        }
-    }
-    return VS_OK;
+    return launch_16bit(plan, (char*)workspace, eps, dtype == VS_F16, st);
 }
