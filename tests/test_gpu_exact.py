@@ -285,7 +285,7 @@ def test_grouped_weight_gradients_exact(cfg, dtype, lib_mode, monkeypatch):
     ops = _ops()
     cases, kinds = _group_cases(), [g[0] for g in GROUP_LAYERS]
     with ops.config(**cfg):
-        assert ops._GROUP["enabled"]
+        assert ops.wgrad_grouping()
         got = _layers_backward(ops, cases, kinds, dtype, monkeypatch)
         ops.set_wgrad_grouping(False)
         try:
@@ -324,7 +324,7 @@ def test_grouped_weight_gradients_many_batches_exact(dtype, cfg, lib_mode, monke
     ops = _ops()
     cases, kinds = _many_batches_cases(), [g[0] for g in MANY_BATCHES]
     with ops.config(**cfg):
-        assert ops._GROUP["enabled"]
+        assert ops.wgrad_grouping()
         got = _layers_backward(ops, cases, kinds, dtype, monkeypatch)
         ops.set_wgrad_grouping(False)
         try:
@@ -532,7 +532,7 @@ def test_grouped_weight_gradients_limbs_exact(cfg, lib_mode, monkeypatch):
     ops = _ops()
     cases = _limb_group_cases()
     with ops.config(**cfg):
-        assert ops._GROUP["enabled"] and ops.get_config()["f32_limbs"] == 1
+        assert ops.wgrad_grouping() and ops.get_config()["f32_limbs"] == 1
         got = _layers_backward(ops, cases, ["k3"] * len(cases), torch.float32, monkeypatch)
         ops.set_wgrad_grouping(False)
         try:

@@ -562,7 +562,7 @@ def test_grouped_weight_gradients_many_layers(dtype, mpack, uber, swap, big, fol
     # >= 400 k voxels (none of this list) get it.  Switched through the library's one configuration entry point (vs_set_config), restored afterwards.
     # fold 1 (default): a transposed conv's bias gradient is summed by its own weight-gradient workgroups (their Q operand is that tensor); 0: a pass of its own.
     with ops.config(**group_config(mpack, uber, swap, big, fold)):
-        assert ops._GROUP["enabled"]
+        assert ops.wgrad_grouping()
         got, refs = _group_layers_backward(ops, dtype)
         tol = TOL[dtype] * 4
         for (gw, gb), (rw, rb), case in zip(got, refs, GROUP_LAYERS):

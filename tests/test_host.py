@@ -544,30 +544,161 @@ def test_volume_imports_without_ops():
     assert run.returncode == 0 and run.stdout.decode().strip().endswith("ok"), run.stdout.decode()
 
 
-def test_on_backward_end():
-    """ops._on_backward_end: nothing is queued outside a backward pass; inside one, a registry's callback is queued once and runs once, after the pass"""
-    from vae_segmentation_amd import ops
-    reg, ran, seen = {"callback": False}, [], []
+# ---- ops._PENDING: what one backward pass owns, and its one end-of-pass callback (CPU tensors and a toy Function: no device) ----
+class _InPass(torch.autograd.Function):
+    """identity whose backward runs fn() — inside a backward pass of the autograd engine"""
 
-    def fn():
-        ran.append(1)
+    @staticmethod
+    def forward(ctx, x, fn):
+        ctx.fn = fn
+        return x * 2
 
-    assert ops._on_backward_end(reg, fn) is False and reg["callback"] is False and not ran
+    @staticmethod
+    def backward(ctx, g):
+        ctx.fn()
+        return g * 2, None
 
-    class Twice(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, x):
-            return x * 2
 
-        @staticmethod
-        def backward(ctx, g):
-            seen.append((ops._on_backward_end(reg, fn), ops._on_backward_end(reg, fn), reg["callback"], len(ran)))
-            return g * 2
-
+def _run_pass(fn):
     x = torch.ones(3, requires_grad=True)
-    y = Twice.apply(x).sum()
+    _InPass.apply(x, fn).sum().backward()
+    return x
+
+
+def _pass_is_empty(ops):
+    p = ops._PENDING
+    return not (p["grads"] or p["unapplied"] or p["slots"] or p["dead_biases"] or p["up_jobs"] or p["queued"])
+
+
+@pytest.fixture
+def pass_ops():
+    from vae_segmentation_amd import ops
+    ops.drop_stale_wgrads()
+    assert _pass_is_empty(ops) and ops.pending_wgrads() == 0
+    yield ops
+    ops._GROUP["descs"], ops._GROUP["keep"] = [], []
+    ops.drop_stale_wgrads()
+
+
+def _unapplied(ops, seed):
+    """register an un-applied gradient as a conv backward does -> g"""
+    g, x = torch.full((2, 3), float(seed)), torch.zeros(2, 3)
+    assert ops._finish(g, x, torch.zeros(4), torch.zeros(4), True) is g
+    return g
+
+
+def test_pass_state_nothing_queued_outside_a_pass(pass_ops):
+    ops = pass_ops
+    assert ops._PENDING.join() is False and ops._PENDING["queued"] is False
+    ops._park_gradient(torch.zeros(2), torch.ones(2))           # stored, but no callback: nothing will call back
+    assert len(ops._PENDING["grads"]) == 1 and ops._PENDING["queued"] is False
+    ops.drop_stale_wgrads()
+    assert _pass_is_empty(ops)
+
+
+def test_pass_state_callback_queued_once_runs_once_after_the_pass(pass_ops, monkeypatch):
+    """the callback is queued once per pass however many parts register, and runs once, after backward() returned from the last node"""
+    ops = pass_ops
+    ran, seen, done = [], [], ops._pass_done
+    monkeypatch.setattr(ops, "_pass_done", lambda: (ran.append(1), done())[1])
+    x0, held = torch.zeros(2), []
+
+    def parts():
+        first = ops._PENDING.join()
+        ops._park_gradient(x0, torch.ones(2))
+        held.append(_unapplied(ops, 1))
+        seen.append((first, ops._PENDING.join(), ops._PENDING["queued"], len(ran)))
+        assert ops._collect_gradient(x0) is not None and ops._take_lazy(held[0]) is not None
+
+    assert ops._PENDING.join() is False and ops._PENDING["queued"] is False and not ran
+    x = torch.ones(3, requires_grad=True)
+    y = _InPass.apply(x, parts).sum()
     assert not seen and not ran
     y.backward()
     assert seen == [(True, True, True, 0)]                   # queued by the first call alone, and not run before backward() returned
-    assert ran == [1] and reg["callback"] is True            # run once, after the pass; clearing the mark is the callback's own business
+    assert ran == [1] and _pass_is_empty(ops)                # run once, after the pass; it clears the mark with everything else
     assert torch.equal(x.grad, torch.full((3,), 2.0))
+
+
+def test_pass_state_parked_gradient(pass_ops):
+    ops = pass_ops
+    x0, g0 = torch.zeros(2), torch.ones(2)
+    _run_pass(lambda: (ops._park_gradient(x0, g0), ops._collect_gradient(x0)))
+    assert _pass_is_empty(ops)
+    with pytest.raises(RuntimeError, match=r"1 parked skip gradient\(s\) were never collected by the conv that shares their input: gradients lost"):
+        _run_pass(lambda: ops._park_gradient(x0, g0))
+    assert _pass_is_empty(ops)
+
+
+def test_pass_state_unapplied_gradient(pass_ops):
+    ops = pass_ops
+    taken = []
+    _run_pass(lambda: taken.append(ops._take_lazy(_unapplied(ops, 1))))
+    assert len(taken[0]) == 3 and _pass_is_empty(ops)
+    held = []
+    with pytest.raises(RuntimeError, match=r"1 un-applied gradient\(s\) \(deferred InstanceNorm-backward apply\) were not taken by the producing conv: gradients wrong$"):
+        _run_pass(lambda: held.append(_unapplied(ops, 2)))
+    assert _pass_is_empty(ops)
+
+
+def test_pass_state_both_kinds_left_over_one_error(pass_ops):
+    ops = pass_ops
+    held = []
+
+    def leave():
+        ops._park_gradient(torch.zeros(2), torch.ones(2))
+        held.extend([_unapplied(ops, 1), _unapplied(ops, 2)])
+
+    with pytest.raises(RuntimeError, match=r"^2 un-applied gradient\(s\) .* were not taken by the producing conv: gradients wrong \(and 1 parked skip gradient\(s\) were never collected\)$"):
+        _run_pass(leave)
+    assert _pass_is_empty(ops)
+
+
+def test_pass_state_dropped_after_a_pass_that_died(pass_ops):
+    ops = pass_ops
+    held, x0 = [], torch.zeros(2)
+
+    def die():
+        ops._park_gradient(x0, torch.ones(2))
+        held.append(_unapplied(ops, 1))
+        ops._PENDING["slots"][1] = ops._Slot(1, None, False)
+        ops._PENDING["dead_biases"].add(2)
+        ops._PENDING["up_jobs"][3] = {}
+        raise ValueError("midway")
+
+    with pytest.raises(ValueError, match="midway"):
+        _run_pass(die)
+    ops.drop_stale_wgrads()
+    assert _pass_is_empty(ops) and ops.pending_wgrads() == 0
+    e0 = ops._PENDING["epoch"]
+    _run_pass(lambda: (ops._park_gradient(x0, torch.ones(2)), ops._collect_gradient(x0)))       # the next pass works
+    assert _pass_is_empty(ops) and ops._PENDING["epoch"] == e0 + 1
+
+
+def test_queued_second_phase_survives_drop_stale(pass_ops):
+    """descriptors queued with no callback pending are the caller's second phase (set_wgrad_split), not leftovers of a pass that died"""
+    ops = pass_ops
+    entry = (ops.WgradDesc(), False, 0.0, 0.0, 0)
+    ops._GROUP["descs"].append(entry)
+    ops._PENDING["slots"][1] = ops._Slot(1, None, False)
+    ops.drop_stale_wgrads()
+    assert ops.pending_wgrads() == 1 and ops._GROUP["descs"][0] is entry and 1 in ops._PENDING["slots"]
+    ops._PENDING["queued"] = True                                  # the same queue behind a pass that died: stale
+    ops.drop_stale_wgrads()
+    assert ops.pending_wgrads() == 0 and _pass_is_empty(ops)
+
+
+def test_use_epoch_and_use_counts(pass_ops):
+    """the use epoch advances once per pass; a weight counted once in a forward is "not once" after a second forward, and once again in the next epoch"""
+    ops = pass_ops
+    e0, w = ops._PENDING["epoch"], torch.ones(1)
+    ops._count_use(w)
+    assert w._vs_use == [e0, 1]
+    ops._count_use(w)
+    assert w._vs_use != [e0, 1] and w._vs_use == [e0, 2]
+    x0 = torch.zeros(2)
+    for k in (1, 2):
+        _run_pass(lambda: (ops._PENDING.join(), ops._park_gradient(x0, torch.ones(2)), ops._PENDING.join(), ops._collect_gradient(x0)))
+        assert ops._PENDING["epoch"] == e0 + k
+    ops._count_use(w)
+    assert w._vs_use == [e0 + 2, 1]

@@ -140,7 +140,7 @@ class DoubleConv(nn.Module):
         for i in idx:
             a = _conv_norm_act(self.conv, i, a)
             if i < 6 and a.stats is not None:
-                ops.mark_defer_apply(a.raw, self.conv[i])      # consumed once, by the next 3x3x3 conv: its IN-backward apply can be fused (ops._LAZY_APPLY)
+                ops.mark_defer_apply(a.raw, self.conv[i])      # consumed once, by the next 3x3x3 conv: its IN-backward apply can be fused (ops._finish, ops._PENDING["unapplied"])
         return _as_tensor(a, self.out_ch) if wrapped else a
 
     def lazy_all(self):
@@ -230,7 +230,7 @@ def set_recompute(enabled=True):
     # recomputation is meant to free: in this mode each layer's weight gradient is launched where its backward runs; switching recomputation off
     # restores whatever grouping was in force before it was switched on
     if enabled:
-        _RECOMPUTE_SAVED_GROUPING[0] = bool(ops._GROUP["enabled"])
+        _RECOMPUTE_SAVED_GROUPING[0] = ops.wgrad_grouping()
         ops.set_wgrad_grouping(False)
     else:
         ops.set_wgrad_grouping(_RECOMPUTE_SAVED_GROUPING[0])
@@ -394,7 +394,7 @@ class Segmentation(nn.Module):
         u = _dropout(_run_block(self.up2, x5), dropout)
         u = _run_block(self.up3, u)
         # skips (joint_model.py:380,382).  x3 / x2 also feed down3 / down2's strided conv: their skip gradient is parked for that conv's
-        # backward to sum in (ops._park_gradient) instead of an add launch of autograd's
+        # backward to sum in (ops._park_gradient -> ops._PENDING["grads"]) instead of an add launch of autograd's
         u = _dropout(Act(ops.Materialize.apply(u.raw, u.stats, x3.raw, x3.stats, True), None), dropout)
         u = _run_block(self.up4, u)
         u = _dropout(Act(ops.Materialize.apply(u.raw, u.stats, x2.raw, x2.stats, True), None), dropout)

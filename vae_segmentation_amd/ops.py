@@ -11,6 +11,8 @@ total derivative (the InstanceNorm+ReLU backward is applied by the consumer's ba
 
 The forward-only utilities on planar volumes live in volume.py; its public names are re-exported here (``ops.cc_label`` is ``volume.cc_label``).
 """
+import collections as _collections
+import contextlib as _contextlib
 import ctypes as _ctypes
 import os
 import weakref as _weakref
@@ -156,7 +158,9 @@ PROFILE_SPIN = [None]          # set by profiling.py (the measurement aid lives 
 
 
 class _timed:
-    def __init__(self, kid, nbytes, flops, detail=""):
+    def __init__(self, kid, nbytes=None, flops=None, detail=""):
+        if PROFILE is not None and callable(kid):
+            kid, nbytes, flops = kid()              # a form's *_profile helper, evaluated only while a PROFILE list is installed
         self.rec = None if PROFILE is None else [kid, float(nbytes), float(flops), detail]
 
     def __enter__(self):
@@ -498,58 +502,82 @@ def conv_gather(x, xs, wp, bias, m_out, kind, want_stats, real_channels=None):
 def conv_scatter(x, xs, wp, bias, m_out):
     n, d, h, w, c = x.shape
     y = torch.empty((n, 2 * d, 2 * h, 2 * w, m_out), dtype=x.dtype, device=x.device)
-    kid = nb = fl = None
-    if PROFILE is not None:
-        tiles = n * ((d * h * w + 255) // 256)
-        rows16 = (8 * m_out + 15) // 16 * 16
-        kid = "g1_kernel<%s,%d,2,%d,2>" % (_tname(x), min(c, 32), _pick_mt(rows16, tiles))
-        nb = (x.numel() + y.numel()) * _esize(x) + 8 * c * m_out * _esize(x)
-        fl = 2.0 * (x.numel() // c) * 8 * c * m_out
-    with _timed(kid, nb, fl, "x%s->m%d" % (tuple(x.shape), m_out)):
+    profile = lambda: ("g1_kernel<%s,%d,2,%d,2>" % (_tname(x), min(c, 32), _pick_mt((8 * m_out + 15) // 16 * 16, n * ((d * h * w + 255) // 256))),
+                       (x.numel() + y.numel()) * _esize(x) + 8 * c * m_out * _esize(x), 2.0 * (x.numel() // c) * 8 * c * m_out)
+    with _timed(profile, detail="x%s->m%d" % (tuple(x.shape), m_out)):
         check(lib.vs_conv_scatter_fwd(x.data_ptr(), _p(xs), wp.data_ptr(), _p(bias), y.data_ptr(), n, d, h, w, c, m_out,
                                       vs_dtype(x), EPS_IN, _stream()), "conv_scatter_fwd")
     return y
 
 
+_Slot = _collections.namedtuple("_Slot", "gw_ptr gb_ptr from_slabs")
+
+
+class _PassState(dict):
+    """Everything that lives for ONE backward pass, by name.  A part that registers something calls join(), which has the autograd engine call _pass_done() when
+    the pass ends; _pass_done() and drop_stale_wgrads() (a pass that died) empty it with reset().  Only the use epoch survives: it counts the passes."""
+
+    def __init__(self):
+        self["epoch"] = 0           # advanced when a pass ends: the use counts of the next forward start over (_count_use)
+        self.reset()
+
+    def reset(self):
+        self.update(
+            grads={},               # (address, shape) of a raw tensor -> the skip's gradient of it, parked for the conv that shares the tensor (_park_gradient)
+            unapplied={},           # (address, shape) of an un-applied gradient g -> (x, stats, sums, g), waiting for x's producer (_finish, _take_lazy)
+            slots={},               # id(weight) -> _Slot: where the FIRST use of a weight in this pass has its deferred gradient written (_side_grads)
+            dead_biases=set(),      # id(bias) of the dead biases that got their (zero) gradient in this pass (_dead_bias_grad)
+            up_jobs={},             # id(w3) -> the chain-rule job of a trainable composed Up head (_up_weight_grads)
+            queued=False)           # _pass_done is queued with the engine
+
+    def join(self):
+        """-> True when _pass_done() is, or now was, queued for the running pass; False outside a backward pass, where nothing was queued and nothing will call back."""
+        if not self["queued"]:
+            try:
+                torch.autograd.Variable._execution_engine.queue_callback(_pass_done)
+                self["queued"] = True
+            except RuntimeError:
+                pass
+        return self["queued"]
+
+
+_PENDING = _PassState()
+
+
+def _pass_done():
+    """The one end-of-pass callback, in this order: advance the use epoch; issue the grouped weight gradients (under set_wgrad_split the first phase only; the Up
+    chain-rule jobs run when nothing is left for later); clear all pass state; raise if gradients were left behind.  The state is cleared before anything is raised,
+    so a failed pass cannot poison the next one."""
+    p = _PENDING
+    p["epoch"] += 1
+    parked, unapplied = len(p["grads"]), len(p["unapplied"])
+    try:
+        flush_wgrads(first_only=_GROUP["split"] is not None)
+    finally:
+        p.reset()
+    if unapplied:
+        raise RuntimeError("%d un-applied gradient(s) (deferred InstanceNorm-backward apply) were not taken by the producing conv: gradients wrong" % unapplied
+                           + (" (and %d parked skip gradient(s) were never collected)" % parked if parked else ""))
+    if parked:
+        raise RuntimeError("%d parked skip gradient(s) were never collected by the conv that shares their input: gradients lost" % parked)
+
+
 # An activation that feeds both the next encoder level (a lazy conv) and an additive U-Net skip (joint_model.py:380,382) receives two
-# gradients.  The skip's (Materialize.backward, which runs first: the decoder is differentiated before the encoder) is parked here, keyed
+# gradients.  The skip's (Materialize.backward, which runs first: the decoder is differentiated before the encoder) is parked in the pass state, keyed
 # by the raw tensor, and summed in by the apply pass of the conv's backward (vs_instnorm_relu_bwd_apply_add) instead of by an ATen add
-# launch of autograd's.  A gradient nobody collected by the end of the pass is an error (it would be lost), checked by an engine callback.
-_PENDING = {"grads": {}, "callback": False}
-
-
-def _on_backward_end(reg, fn):
-    """Have the autograd engine call fn() when the running backward pass ends, once per pass: reg["callback"] remembers that it is queued (fn clears it).
-    -> True when fn is, or now was, queued for this pass; False outside a backward pass, where nothing was queued and nothing will call back."""
-    if not reg["callback"]:
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(fn)
-            reg["callback"] = True
-        except RuntimeError:
-            pass
-    return reg["callback"]
-
-
+# launch of autograd's.  A gradient nobody collected by the end of the pass is an error (it would be lost): _pass_done raises.
 def _park_gradient(x, g):
     _PENDING["grads"][(x.data_ptr(), tuple(x.shape))] = g
-    _on_backward_end(_PENDING, _pending_done)
+    _PENDING.join()
 
 
 def _collect_gradient(x):
     return _PENDING["grads"].pop((x.data_ptr(), tuple(x.shape)), None)
 
 
-def _pending_done():
-    _PENDING["callback"] = False
-    left = len(_PENDING["grads"])
-    _PENDING["grads"].clear()
-    if left:
-        raise RuntimeError("%d parked skip gradient(s) were never collected by the conv that shares their input: gradients lost" % left)
-
-
 # Deferred IN-backward apply (the 8-channel full-resolution layers, igemm_k3t.h FA): where a lazy activation x is produced by an 8 -> 8 3x3x3
 # conv and consumed by exactly one 3x3x3 conv (the modules mark x: mark_defer_apply), the consumer's backward hands over the UN-applied
-# gradient g = dL/da together with (x, stats, sums) through this registry, and the producer's backward-data kernel applies
+# gradient g = dL/da together with (x, stats, sums) through the pass state (_PENDING["unapplied"]), and the producer's backward-data kernel applies
 # rstd * (g*mask - m1 - xhat*m2) while it stages its input — the standalone apply launch (3 tensor passes at 96^3) disappears.
 # An entry nobody took by the end of the pass means a consumer treated an un-applied gradient as applied: that is an error, not a fallback.
 FUSE_APPLY = os.environ.get("VS_FUSE_APPLY", "1") != "0"
@@ -562,7 +590,6 @@ EPILOGUE_APPLY_S2 = os.environ.get("VS_EPILOGUE_APPLY_S2", "1") != "0"      # ..
 _FA_CHANNELS = (8, 16)
 _FA_CHANNELS_F32 = (8, 16)       # 16: k3x_kernel<8, 16, .., FA> (the 16 -> 16 layers of the 48^3 level; the library has the last word)
 FUSE_APPLY_F32 = os.environ.get("VS_FUSE_APPLY_F32", "1") != "0"      # A/B switch of the parity mode's fused apply
-_LAZY_APPLY = {"grads": {}, "callback": False}
 
 
 def mark_defer_apply(x, producer):
@@ -576,29 +603,33 @@ def mark_defer_apply(x, producer):
     return x
 
 
-def _fa_supported(gy, x, lazy_input):
-    n, d, h, w, c = gy.shape
-    return bool(lib.vs_conv_k3_fused_apply_supported(n, d, h, w, c, x.shape[-1], 1 if lazy_input else 0, vs_dtype(gy)))
+def _wants_defer(x, xs):
+    """does the producer of the lazy activation (x, xs) want its gradient un-applied? (mark_defer_apply)"""
+    return bool(getattr(x, "_vs_defer_apply", False)) and xs is not None
 
 
-def _defer_register(g, x, xs, sums):
-    # g itself is kept in the entry: the key is its address, and a live reference is what guarantees that address cannot be recycled for another
-    # gradient of the same shape before the producing conv's backward takes the entry
-    _LAZY_APPLY["grads"][(g.data_ptr(), tuple(g.shape))] = (x, xs, sums, g)
-    _on_backward_end(_LAZY_APPLY, _lazy_apply_done)
+def _finish(g, x, xs, sums, defer):
+    """The end of a backward-data launch that left g = dL/da of a = relu(instnorm(x)) with its sums: hand g over un-applied to x's producer (defer), or apply the
+    InstanceNorm+ReLU backward in place, a parked skip gradient of the same tensor summed in.  A stored x (xs None) has nothing to apply.  -> g"""
+    if xs is None:
+        return g
+    if defer:
+        # g itself is kept in the entry: the key is its address, and a live reference is what guarantees that address cannot be recycled for another
+        # gradient of the same shape before the producing conv's backward takes the entry
+        _PENDING["unapplied"][(g.data_ptr(), tuple(g.shape))] = (x, xs, sums, g)
+        _PENDING.join()
+        return g
+    n, c = x.shape[0], x.shape[-1]
+    add = _collect_gradient(x)                 # the skip's gradient of the same tensor, if one was parked
+    with _timed("in_relu_bwd_apply_kernel<%s>" % _tname(x), (3 if add is None else 4) * x.numel() * _esize(x), 6.0 * x.numel(), str(tuple(x.shape))):
+        check(lib.vs_instnorm_relu_bwd_apply_add(g.data_ptr(), x.data_ptr(), xs.data_ptr(), sums.data_ptr(), _p(add), g.data_ptr(), n, x.numel() // (n * c),
+                                                 c, vs_dtype(x), EPS_IN, _stream()), "instnorm_relu_bwd_apply")
+    return g
 
 
 def _take_lazy(g):
-    ent = _LAZY_APPLY["grads"].pop((g.data_ptr(), tuple(g.shape)), None) if _LAZY_APPLY["grads"] else None
+    ent = _PENDING["unapplied"].pop((g.data_ptr(), tuple(g.shape)), None) if _PENDING["unapplied"] else None
     return None if ent is None else ent[:3]
-
-
-def _lazy_apply_done():
-    _LAZY_APPLY["callback"] = False
-    left = len(_LAZY_APPLY["grads"])
-    _LAZY_APPLY["grads"].clear()
-    if left:
-        raise RuntimeError("%d un-applied gradient(s) (deferred InstanceNorm-backward apply) were not taken by the producing conv: gradients wrong" % left)
 
 
 def apply_lazy(g, lazy):
@@ -618,133 +649,160 @@ def _ea_sync(n, device):
     return buf[off:off + cnt]
 
 
-def conv_bwd_data_lazy(gy, wpb, x, xs, kind, scatter=False, real_channels=None, defer=False, lazy=None, want_dx=False, fuse_wgrad=None):
+# The backward-data launch forms _conv_bwd_data picks from; the profiler's (kernel id, algorithmic bytes, flops) of a form is the *_profile helper before it.
+def _k3_tiles(shape):
+    n, d, h, w = shape[:4]
+    return n * ((d + 3) // 4) * ((h + 3) // 4) * ((w + 15) // 16)
+
+
+def _fused_wgrad_profile(gy, x, lazy):
+    c = x.shape[-1]
+    return ("k3tw_kernel<%s,%s>" % (_tname(x), "true" if lazy is not None else "false"),
+            ((3 if lazy is not None else 2) * gy.numel() + 2 * x.numel()) * _esize(x), 2.0 * 2.0 * (x.numel() // c) * 27 * gy.shape[-1] * c)
+
+
+def _bwd_fused_wgrad(gy, wpb, x, xs, lazy, weight, m_real, c_real):
+    """the 8 -> 8 launch that also forms the layer's weight gradient (see _wgrad_fusable), gy un-applied (lazy) or not -> (g, sums, gw)"""
+    sums, g = _new_stats(x.shape[0], x.shape[-1], x.device), torch.empty_like(x)
+    ax, axs, asums = lazy if lazy is not None else (None, None, None)
+    nslabs = lib.vs_conv_k3_bwd_data_wgrad_slabs(*gy.shape[:4])
+    slabs = torch.empty(nslabs * 1728, dtype=torch.float32, device=x.device)
+    with _timed(lambda: _fused_wgrad_profile(gy, x, lazy), detail="bwd+wgrad gy%s->m%d" % (tuple(gy.shape), x.shape[-1])):
+        check(lib.vs_conv_k3_bwd_data_wgrad(gy.data_ptr(), _p(ax), _p(axs), _p(asums), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(),
+                                            sums.data_ptr(), slabs.data_ptr(), *gy.shape, x.shape[-1], vs_dtype(x), EPS_IN, _stream()), "conv_k3_bwd_data_wgrad")
+    return g, sums, _group_submit_slabs(weight, slabs, nslabs, m_real, c_real, (gy, x, xs))[0]
+
+
+def _fused_apply_profile(gy, x, want_dx):
+    gc, c = gy.shape[-1], x.shape[-1]
+    kid = _k3_kid(_tname(x), min(gc, 32), _pick_mt((c + 15) // 16 * 16, _k3_tiles(gy.shape)), sums=True, geom=tuple(gy.shape[:4]), m=c) + "+apply"
+    return kid, (2 * gy.numel() + 2 * x.numel() + (gy.numel() if want_dx else 0)) * _esize(x) + gc * c * 27 * _esize(x), 2.0 * (x.numel() // c) * 27 * gc * c
+
+
+def _bwd_fused_apply(gy, wpb, x, xs, lazy, want_dx):
+    """gy is itself an un-applied gradient, lazy = (act_x, act_stats, act_sums) (see _finish): its apply is fused into this launch's staging
+    -> (g, sums, the applied gy or None [want_dx]).  A stored x (xs None: VAE.in_block on the prediction) has no sums to fuse; that launch is not timed."""
+    ax, axs, asums = lazy
+    sums = _new_stats(x.shape[0], x.shape[-1], x.device) if xs is not None else None
+    g = torch.empty_like(x)
+    dx = torch.empty_like(gy) if want_dx else None
+    with (_timed(lambda: _fused_apply_profile(gy, x, want_dx), detail="bwd+apply gy%s->m%d" % (tuple(gy.shape), x.shape[-1])) if xs is not None
+          else _contextlib.nullcontext()):
+        check(lib.vs_conv_k3_bwd_data_fused_apply(gy.data_ptr(), ax.data_ptr(), axs.data_ptr(), asums.data_ptr(), wpb.data_ptr(), g.data_ptr(),
+                                                  _p(x if xs is not None else None), _p(xs), _p(sums), _p(dx), *gy.shape, x.shape[-1], vs_dtype(x),
+                                                  EPS_IN, _stream()), "conv_k3_bwd_data_fused_apply")
+    return g, sums, dx
+
+
+def _k3_epilogue_profile(gy, x):
+    gc, c = gy.shape[-1], x.shape[-1]
+    kid = _k3_kid(_tname(x), min(gc, 32), 16, sums=True, geom=tuple(gy.shape[:4]), m=c) + "+ea"
+    return kid, (gy.numel() + 2 * x.numel()) * _esize(x) + gc * c * 27 * _esize(x), 2.0 * (x.numel() // c) * 27 * gc * c
+
+
+def _bwd_k3_epilogue(gy, wpb, x, xs):
+    """the 24^3 / 12^3 levels: the backward-data launch applies the InstanceNorm+ReLU backward to its own outputs (csrc/igemm_k3b.h EA): no apply launch -> g, applied"""
+    sums, g = _new_stats(x.shape[0], x.shape[-1], x.device), torch.empty_like(x)
+    sync = _ea_sync(gy.shape[0], x.device)
+    with _timed(lambda: _k3_epilogue_profile(gy, x), detail="bwd+ea gy%s->m%d" % (tuple(gy.shape), x.shape[-1])):
+        check(lib.vs_conv_k3_bwd_data_applied(gy.data_ptr(), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(), sums.data_ptr(), sync.data_ptr(),
+                                              _chain_fault_word(x.device).data_ptr(), *gy.shape, x.shape[-1], vs_dtype(x), EPS_IN, _stream()),
+              "conv_k3_bwd_data_applied")
+    return g
+
+
+def _s2_epilogue_profile(gy, x, kind, scatter, add):
+    n, c = x.shape[0], x.shape[-1]
+    gn, gd, gh, gw_, gc = gy.shape
+    tiles = gn * ((gd * gh * gw_ + 255) // 256) if scatter else n * ((x.numel() // (n * c) + 255) // 256)
+    rows = (8 * c + 15) // 16 * 16 if scatter else (c + 15) // 16 * 16
+    kid = "g1_kernel<%s,%d,%d,%d,%d>+ea" % (_tname(x), min(gc, 32), 2 if scatter else kind, _pick_mt(rows, tiles), 2 if scatter else 0)
+    return (kid, (gy.numel() + (2 if add is None else 3) * x.numel()) * _esize(x) + 8 * gc * c * _esize(x),
+            2.0 * ((gy.numel() // gc) if scatter else (x.numel() // c)) * 8 * gc * c)
+
+
+def _bwd_s2_epilogue(gy, wpb, x, xs, kind, scatter):
+    """the stride-2 / transposed launches of the <= 48^3 levels: g1_kernel applies the InstanceNorm+ReLU backward to its own outputs (csrc/igemm.h), the
+    skip's parked gradient of the same tensor summed in as the standalone apply would -> g, applied"""
+    sums, g = _new_stats(x.shape[0], x.shape[-1], x.device), torch.empty_like(x)
+    sync = _ea_sync(gy.shape[0], x.device)
+    add = _collect_gradient(x)
+    with _timed(lambda: _s2_epilogue_profile(gy, x, kind, scatter, add), detail="bwd+ea gy%s->m%d" % (tuple(gy.shape), x.shape[-1])):
+        check(lib.vs_conv_s2_bwd_data_applied(gy.data_ptr(), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(), sums.data_ptr(), _p(add), sync.data_ptr(),
+                                              _chain_fault_word(x.device).data_ptr(), *gy.shape, x.shape[-1], 1 if scatter else 0, vs_dtype(x), EPS_IN,
+                                              _stream()), "conv_s2_bwd_data_applied")
+    return g
+
+
+def _scatter_profile(gy, x):
+    c = x.shape[-1]
+    gn, gd, gh, gw_, gc = gy.shape
+    kid = "g1_kernel<%s,%d,2,%d,2>" % (_tname(x), min(gc, 32), _pick_mt((8 * c + 15) // 16 * 16, gn * ((gd * gh * gw_ + 255) // 256)))
+    return kid, (gy.numel() + 2 * x.numel()) * _esize(x) + 8 * gc * c * _esize(x), 2.0 * (gy.numel() // gc) * 8 * gc * c
+
+
+def _bwd_scatter(gy, wpb, x, xs):
+    """backward-data of a stride-2 conv (a scatter over gy's grid) -> (g, sums)"""
+    sums, g = _new_stats(x.shape[0], x.shape[-1], x.device), torch.empty_like(x)
+    with _timed(lambda: _scatter_profile(gy, x), detail="bwd gy%s->m%d" % (tuple(gy.shape), x.shape[-1])):
+        check(lib.vs_conv_scatter_bwd_data(gy.data_ptr(), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(),
+                                           sums.data_ptr(), *gy.shape, x.shape[-1], vs_dtype(x), EPS_IN, _stream()), "conv_scatter_bwd_data")
+    return g, sums
+
+
+def _gather_profile(gy, x, kind, real_channels):
+    n, c, gc = x.shape[0], x.shape[-1], gy.shape[-1]
+    rows16 = (c + 15) // 16 * 16
+    if kind == VS_CONV_K3:
+        taps, kid = 27, _k3_kid(_tname(x), min(gc, 32), _pick_mt(rows16, _k3_tiles(gy.shape)), sums=True, geom=tuple(gy.shape[:4]), m=c)
+    else:
+        taps, kid = 8, "g1_kernel<%s,%d,%d,%d,0>" % (_tname(x), min(gc, 32), kind, _pick_mt(rows16, n * ((x.numel() // (n * c) + 255) // 256)))
+    cr, mr = real_channels if real_channels else (gc, c)
+    vox_out = x.numel() // c
+    return kid, (gy.numel() // gc * cr + 2 * vox_out * mr) * _esize(x) + cr * mr * taps * _esize(x), 2.0 * vox_out * taps * cr * mr
+
+
+def _bwd_gather(gy, wpb, x, xs, kind, real_channels):
+    """backward-data as a gather over x's grid (3x3x3, transposed 2x2x2) -> (g, sums)"""
+    sums, g = _new_stats(x.shape[0], x.shape[-1], x.device), torch.empty_like(x)
+    with _timed(lambda: _gather_profile(gy, x, kind, real_channels), detail="bwd gy%s->m%d" % (tuple(gy.shape), x.shape[-1])):
+        check(lib.vs_conv_gather_bwd_data(gy.data_ptr(), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(),
+                                          sums.data_ptr(), *gy.shape, x.shape[-1], kind, vs_dtype(x), EPS_IN, _stream()), "conv_gather_bwd_data")
+    return g, sums
+
+
+def _conv_bwd_data(gy, wpb, x, xs, kind, scatter=False, real_channels=None, defer=False, lazy=None, want_dx=False, fuse_wgrad=None):
     """Gradient w.r.t. the raw tensor x of a lazy activation a = relu(instnorm(x)) that fed a conv:
     g = conv-backward-data(gy) with the InstanceNorm+ReLU-backward sums accumulated in the same kernel's epilogue,
-    then the (in-place) apply pass.  kind / scatter select the backward-data form of the forward conv.
-    lazy = (act_x, act_stats, act_sums): gy itself is an un-applied gradient (see _LAZY_APPLY) — its apply is fused into this launch's
-    staging and the call returns (g, applied gy or None [want_dx]).  defer: leave g un-applied and register it for x's producer.
-    fuse_wgrad = (weight, m_real, c_real): the launch also forms the layer's weight gradient (see _wgrad_fusable) and the call returns (g, gw)."""
-    n, c = x.shape[0], x.shape[-1]
-    sums = _new_stats(n, c, x.device)
-    g = torch.empty_like(x)
-    gn, gd, gh, gw, gc = gy.shape
-    dt = vs_dtype(x)
+    then the (in-place) apply pass (_finish).  kind / scatter select the backward-data form of the forward conv.
+    lazy = (act_x, act_stats, act_sums): gy itself is an un-applied gradient — its apply is fused into this launch's staging, and the applied gy comes
+    back as dx when want_dx.  defer: leave g un-applied and register it for x's producer.
+    fuse_wgrad = (weight, m_real, c_real): the launch also forms the layer's weight gradient gw (see _wgrad_fusable).
+    -> (g, dx, gw), None for what the form does not produce.  The forms are tried in this order."""
+    gn, gd, gh, gw_, gc = gy.shape
+    c, dt = x.shape[-1], vs_dtype(x)
+    dx = gw = None
     if fuse_wgrad is not None:
-        weight, m_real, c_real = fuse_wgrad
-        ax, axs, asums = lazy if lazy is not None else (None, None, None)
-        nslabs = lib.vs_conv_k3_bwd_data_wgrad_slabs(gn, gd, gh, gw)
-        slabs = torch.empty(nslabs * 1728, dtype=torch.float32, device=x.device)
-        kid = nb = fl = None
-        if PROFILE is not None:
-            kid = "k3tw_kernel<%s,%s>" % (_tname(x), "true" if lazy is not None else "false")
-            nb = ((3 if lazy is not None else 2) * gy.numel() + 2 * g.numel()) * _esize(x)
-            fl = 2.0 * 2.0 * (g.numel() // c) * 27 * gc * c
-        with _timed(kid, nb, fl, "bwd+wgrad gy%s->m%d" % (tuple(gy.shape), c)):
-            check(lib.vs_conv_k3_bwd_data_wgrad(gy.data_ptr(), _p(ax), _p(axs), _p(asums), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(),
-                                                sums.data_ptr(), slabs.data_ptr(), gn, gd, gh, gw, gc, c, dt, EPS_IN, _stream()), "conv_k3_bwd_data_wgrad")
-        gw_t = _group_submit_slabs(weight, slabs, nslabs, m_real, c_real, (gy, x, xs))
-        if defer:
-            _defer_register(g, x, xs, sums)
-        else:
-            _apply_in_place(g, x, xs, sums)
-        return g, gw_t
-    if lazy is not None:
-        ax, axs, asums = lazy
-        dx = torch.empty_like(gy) if want_dx else None
-        kid = nb = fl = None
-        if PROFILE is not None:
-            tiles = gn * ((gd + 3) // 4) * ((gh + 3) // 4) * ((gw + 15) // 16)
-            kid = _k3_kid(_tname(x), min(gc, 32), _pick_mt((c + 15) // 16 * 16, tiles), sums=True, geom=(gn, gd, gh, gw), m=c) + "+apply"
-            nb = (2 * gy.numel() + 2 * g.numel() + (gy.numel() if want_dx else 0)) * _esize(x) + gc * c * 27 * _esize(x)
-            fl = 2.0 * (g.numel() // c) * 27 * gc * c
-        with _timed(kid, nb, fl, "bwd+apply gy%s->m%d" % (tuple(gy.shape), c)):
-            check(lib.vs_conv_k3_bwd_data_fused_apply(gy.data_ptr(), ax.data_ptr(), axs.data_ptr(), asums.data_ptr(), wpb.data_ptr(), g.data_ptr(),
-                                                      x.data_ptr(), xs.data_ptr(), sums.data_ptr(), _p(dx), gn, gd, gh, gw, gc, c, dt, EPS_IN,
-                                                      _stream()), "conv_k3_bwd_data_fused_apply")
-        if defer:
-            _defer_register(g, x, xs, sums)
-        else:
-            _apply_in_place(g, x, xs, sums)
-        return g, dx
-    if (not scatter and kind == VS_CONV_K3 and not defer and EPILOGUE_APPLY and (x.data_ptr(), tuple(x.shape)) not in _PENDING["grads"]
-            and lib.vs_conv_k3_bwd_data_applied_supported(gn, gd, gh, gw, gc, c, dt)):
-        # the 24^3 / 12^3 levels: the backward-data launch applies the InstanceNorm+ReLU backward to its own outputs (csrc/igemm_k3b.h EA): no apply launch
-        sync = _ea_sync(gn, x.device)
-        kid = nb = fl = None
-        if PROFILE is not None:
-            tiles = gn * ((gd + 3) // 4) * ((gh + 3) // 4) * ((gw + 15) // 16)
-            kid = _k3_kid(_tname(x), min(gc, 32), 16, sums=True, geom=(gn, gd, gh, gw), m=c) + "+ea"
-            nb = (gy.numel() + 2 * g.numel()) * _esize(x) + gc * c * 27 * _esize(x)
-            fl = 2.0 * (g.numel() // c) * 27 * gc * c
-        with _timed(kid, nb, fl, "bwd+ea gy%s->m%d" % (tuple(gy.shape), c)):
-            check(lib.vs_conv_k3_bwd_data_applied(gy.data_ptr(), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(), sums.data_ptr(), sync.data_ptr(),
-                                                  _chain_fault_word(x.device).data_ptr(), gn, gd, gh, gw, gc, c, dt, EPS_IN, _stream()), "conv_k3_bwd_data_applied")
-        return g
-    if (kind != VS_CONV_K3 and not defer and EPILOGUE_APPLY and EPILOGUE_APPLY_S2 and lib.vs_conv_s2_bwd_data_applied_supported(gn, gd, gh, gw, gc, c, 1 if scatter else 0, dt)):
-        # the stride-2 / transposed launches of the <= 48^3 levels: g1_kernel applies the InstanceNorm+ReLU backward to its own outputs (csrc/igemm.h), the
-        # skip's parked gradient of the same tensor summed in as the standalone apply would
-        sync = _ea_sync(gn, x.device)
-        add = _collect_gradient(x)
-        kid = nb = fl = None
-        if PROFILE is not None:
-            tiles = gn * ((gd * gh * gw + 255) // 256) if scatter else n * ((g.numel() // (n * c) + 255) // 256)
-            rows = (8 * c + 15) // 16 * 16 if scatter else (c + 15) // 16 * 16
-            kid = "g1_kernel<%s,%d,%d,%d,%d>+ea" % (_tname(x), min(gc, 32), 2 if scatter else kind, _pick_mt(rows, tiles), 2 if scatter else 0)
-            nb = (gy.numel() + (2 if add is None else 3) * g.numel()) * _esize(x) + 8 * gc * c * _esize(x)
-            fl = 2.0 * ((gy.numel() // gc) if scatter else (g.numel() // c)) * 8 * gc * c
-        with _timed(kid, nb, fl, "bwd+ea gy%s->m%d" % (tuple(gy.shape), c)):
-            check(lib.vs_conv_s2_bwd_data_applied(gy.data_ptr(), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(), sums.data_ptr(), _p(add), sync.data_ptr(),
-                                                  _chain_fault_word(x.device).data_ptr(), gn, gd, gh, gw, gc, c, 1 if scatter else 0, dt, EPS_IN, _stream()),
-                  "conv_s2_bwd_data_applied")
-        return g
-    if scatter:
-        kid = nb = fl = None
-        if PROFILE is not None:
-            tiles = gn * ((gd * gh * gw + 255) // 256)
-            kid = "g1_kernel<%s,%d,2,%d,2>" % (_tname(x), min(gc, 32),
-                                               _pick_mt((8 * c + 15) // 16 * 16, tiles))
-            nb = (gy.numel() + 2 * g.numel()) * _esize(x) + 8 * gc * c * _esize(x)
-            fl = 2.0 * (gy.numel() // gc) * 8 * gc * c
-        with _timed(kid, nb, fl, "bwd gy%s->m%d" % (tuple(gy.shape), c)):
-            check(lib.vs_conv_scatter_bwd_data(gy.data_ptr(), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(),
-                                               sums.data_ptr(), gn, gd, gh, gw, gc, c, dt, EPS_IN, _stream()), "conv_scatter_bwd_data")
+        g, sums, gw = _bwd_fused_wgrad(gy, wpb, x, xs, lazy, *fuse_wgrad)
+    elif lazy is not None:
+        g, sums, dx = _bwd_fused_apply(gy, wpb, x, xs, lazy, want_dx)
+    elif (not scatter and kind == VS_CONV_K3 and not defer and EPILOGUE_APPLY and (x.data_ptr(), tuple(x.shape)) not in _PENDING["grads"]
+            and lib.vs_conv_k3_bwd_data_applied_supported(gn, gd, gh, gw_, gc, c, dt)):
+        return _bwd_k3_epilogue(gy, wpb, x, xs), None, None
+    elif (kind != VS_CONV_K3 and not defer and EPILOGUE_APPLY and EPILOGUE_APPLY_S2
+            and lib.vs_conv_s2_bwd_data_applied_supported(gn, gd, gh, gw_, gc, c, 1 if scatter else 0, dt)):
+        return _bwd_s2_epilogue(gy, wpb, x, xs, kind, scatter), None, None
+    elif scatter:
+        g, sums = _bwd_scatter(gy, wpb, x, xs)
     else:
-        kid = nb = fl = None
-        if PROFILE is not None:
-            taps = 27 if kind == VS_CONV_K3 else 8
-            if kind == VS_CONV_K3:
-                tiles = gn * ((gd + 3) // 4) * ((gh + 3) // 4) * ((gw + 15) // 16)
-            else:
-                tiles = n * ((g.numel() // (n * c) + 255) // 256)
-            tname = _tname(x)
-            if kind == VS_CONV_K3:
-                kid = _k3_kid(tname, min(gc, 32), _pick_mt((c + 15) // 16 * 16, tiles), sums=True, geom=(gn, gd, gh, gw), m=c)
-            else:
-                kid = "g1_kernel<%s,%d,%d,%d,0>" % (tname, min(gc, 32), kind, _pick_mt((c + 15) // 16 * 16, tiles))
-            cr = real_channels[0] if real_channels else gc
-            mr = real_channels[1] if real_channels else c
-            vox_out = g.numel() // c
-            nb = (gy.numel() // gc * cr + 2 * vox_out * mr) * _esize(x) + cr * mr * taps * _esize(x)
-            fl = 2.0 * vox_out * taps * cr * mr
-        with _timed(kid, nb, fl, "bwd gy%s->m%d" % (tuple(gy.shape), c)):
-            check(lib.vs_conv_gather_bwd_data(gy.data_ptr(), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(),
-                                              sums.data_ptr(), gn, gd, gh, gw, gc, c, kind, dt, EPS_IN, _stream()), "conv_gather_bwd_data")
-    if defer:
-        _defer_register(g, x, xs, sums)
-        return g
-    return _apply_in_place(g, x, xs, sums)
+        g, sums = _bwd_gather(gy, wpb, x, xs, kind, real_channels)
+    return _finish(g, x, xs, sums, defer), dx, gw
 
 
-def _apply_in_place(g, x, xs, sums):
-    n, c = x.shape[0], x.shape[-1]
-    voxels = x.numel() // (n * c)
-    tname = _tname(x)
-    add = _collect_gradient(x)                 # the skip's gradient of the same tensor, if one was parked
-    with _timed("in_relu_bwd_apply_kernel<%s>" % tname, (3 if add is None else 4) * x.numel() * _esize(x), 6.0 * x.numel(), str(tuple(x.shape))):
-        check(lib.vs_instnorm_relu_bwd_apply_add(g.data_ptr(), x.data_ptr(), xs.data_ptr(), sums.data_ptr(), _p(add), g.data_ptr(), n, voxels,
-                                                 c, vs_dtype(x), EPS_IN, _stream()), "instnorm_relu_bwd_apply")
-    return g
+def conv_bwd_data_lazy(gy, wpb, x, xs, kind, lazy=None, fuse_wgrad=None, **kw):
+    """_conv_bwd_data for callers outside this module, who get only what the form produces: g, (g, dx) with lazy, (g, gw) with fuse_wgrad"""
+    g, dx, gw = _conv_bwd_data(gy, wpb, x, xs, kind, lazy=lazy, fuse_wgrad=fuse_wgrad, **kw)
+    return (g, gw) if fuse_wgrad is not None else (g, dx) if lazy is not None else g
 
 
 def conv_wgrad(p, ps, q, qs, m_real, c_real, kind, out_shape, out_ptr=None):
@@ -756,14 +814,11 @@ def conv_wgrad(p, ps, q, qs, m_real, c_real, kind, out_shape, out_ptr=None):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
     dw = torch.empty(out_shape, dtype=torch.float32, device=p.device) if out_ptr is None else None
     dw_ptr = dw.data_ptr() if out_ptr is None else out_ptr
-    kid = nb = fl = None
-    if PROFILE is not None:
-        taps = 27 if kind == VS_CONV_K3 else 8
-        cb, kk = 16 if c_ch >= 16 else 8, 0 if kind == VS_CONV_K3 else 1
-        kid = "g3_kernel<float,%d,%d>" % (cb, kk) if p.dtype == torch.float32 else "g3b_kernel<%d,%d>" % (cb, kk)
-        nb = (p.numel() // m_ch * m_real + q.numel() // c_ch * c_real) * _esize(p) + m_real * c_real * taps * 4
-        fl = 2.0 * (p.numel() // m_ch) * taps * m_real * c_real
-    with _timed(kid, nb, fl, "p%s q%s" % (tuple(p.shape), tuple(q.shape))):
+    def profile():
+        taps, cb, kk = 27 if kind == VS_CONV_K3 else 8, 16 if c_ch >= 16 else 8, 0 if kind == VS_CONV_K3 else 1
+        return ("g3_kernel<float,%d,%d>" % (cb, kk) if p.dtype == torch.float32 else "g3b_kernel<%d,%d>" % (cb, kk),
+                (p.numel() // m_ch * m_real + q.numel() // c_ch * c_real) * _esize(p) + m_real * c_real * taps * 4, 2.0 * (p.numel() // m_ch) * taps * m_real * c_real)
+    with _timed(profile, detail="p%s q%s" % (tuple(p.shape), tuple(q.shape))):
         check(lib.vs_conv_wgrad(p.data_ptr(), _p(ps), q.data_ptr(), _p(qs), dw_ptr, ws.data_ptr(), nbytes, n, dp, hp,
                                 wp_, m_ch, c_ch, m_real, c_real, kind, vs_dtype(p), EPS_IN, _stream()), "conv_wgrad")
     return dw
@@ -794,9 +849,10 @@ class WgradDesc(_ctypes.Structure):
                 ("m_real", _ctypes.c_int), ("c_real", _ctypes.c_int), ("kind", _ctypes.c_int), ("reserved_", _ctypes.c_int)]
 
 
-_GROUP = {"enabled": os.environ.get("VS_WGRAD_GROUP", "1") != "0", "descs": [], "keep": [], "callback": False, "dtype": None,
-          "bytes": 0.0, "flops": 0.0, "split": None, "slots": {}}
-# "slots": id(weight) -> (gw, gb) handed to autograd by the FIRST use of that weight in the current backward pass.  A weight used several
+# settings (enabled, split) and the queue: (descriptor, first phase?, bytes, flops, voxels) entries of one storage type and the tensors they keep alive.  The queue may
+# outlive the pass (the caller's second phase under set_wgrad_split); what belongs to the pass is in _PENDING.
+_GROUP = {"enabled": os.environ.get("VS_WGRAD_GROUP", "1") != "0", "split": None, "descs": [], "keep": [], "dtype": None}
+# _PENDING["slots"]: id(weight) -> the destination handed to autograd by the FIRST use of that weight in the current backward pass.  A weight used several
 # times (the VAE inside Embed runs three times per forward, joint_model.py:469-500) queues one descriptor per use, all with the first use's
 # destination: vs_conv_wgrad_multi sums the uses, and the later uses return None to autograd (nothing left to accumulate).
 
@@ -823,6 +879,11 @@ def set_wgrad_grouping(enabled=True):
     _GROUP["enabled"] = bool(enabled)
 
 
+def wgrad_grouping():
+    """-> is the grouped (deferred) weight-gradient mode on? (set_wgrad_grouping)"""
+    return _GROUP["enabled"]
+
+
 def set_wgrad_split(first=None):
     """Two-phase issue for the data-parallel step (ddp.FlatGradSync): with `first` = a predicate on a parameter, the launches at the end
     of backward cover only the layers whose weight satisfies it; the caller issues the rest with flush_wgrads() after it has started the
@@ -835,25 +896,30 @@ def drop_stale_wgrads():
     """Forget deferred descriptors left behind by a backward pass that raised before its end-of-pass callback ran (their raw pointers
     may be recycled by now).  Called at the top of every forward (stats_arena_begin)."""
     g = _GROUP
-    if g["descs"] and not g["callback"]:
+    if g["descs"] and not _PENDING["queued"]:
         return                                  # a caller-managed second phase (set_wgrad_split) is pending: not stale
-    if g["descs"] or g["callback"]:
-        g["descs"], g["keep"], g["callback"], g["bytes"], g["flops"] = [], [], False, 0.0, 0.0
-    g["slots"] = {}
-    _UP_JOBS.clear()
+    g["descs"], g["keep"] = [], []
     # the same for gradients parked / handed over un-applied by a pass that died: their addresses may be recycled by now, and a later
     # backward must never mistake a fresh tensor at such an address for one of them
-    for reg in (_PENDING, _LAZY_APPLY):
-        reg["grads"].clear()
-        reg["callback"] = False
+    _PENDING.reset()
+
+
+def _queue_desc(weight, d, dtype, nb, fl, voxels, keep):
+    """Queue the finished descriptor d of `weight`'s gradient (operands of storage type `dtype`; profile bytes / flops / voxels; `keep`: the tensors its raw
+    pointers need alive) for the launches at the end of the pass; outside a backward pass nothing will call back, so it is issued at once."""
+    g = _GROUP
+    if g["descs"] and g["dtype"] != dtype:
+        flush_wgrads()                          # one grouped launch has one storage type
+    g["dtype"] = dtype
+    first = g["split"] is None or bool(g["split"](weight))
+    g["descs"].append((d, first, nb, fl, voxels))
+    g["keep"].extend(t for t in keep if t is not None)
+    if not _PENDING.join():
+        flush_wgrads()
 
 
 def _group_submit(weight, keep, wgrad_args, bias_args, gw, gb, up_co=0):
     p, ps, q, qs, m_real, c_real, kind = wgrad_args
-    g = _GROUP
-    if g["descs"] and g["dtype"] != p.dtype:
-        flush_wgrads()
-    g["dtype"] = p.dtype
     n, dp, hp, wp_, m_ch = p.shape
     gw_ptr = gw if isinstance(gw, int) else gw.data_ptr()
     if kind == VS_CONV_UP:                   # p is the FINE gradient (n, 2dp, 2hp, 2wp, Co): the descriptor's grid is the coarse one, its rows the 8 Co view channels
@@ -864,24 +930,12 @@ def _group_submit(weight, keep, wgrad_args, bias_args, gw, gb, up_co=0):
         bg = bias_args[0]
         gb_ptr = gb if isinstance(gb, int) else gb.data_ptr()
         d.bias_g, d.db, d.bias_rows, d.bias_c_ch, d.bias_c_real = bg.data_ptr(), gb_ptr, bg.numel() // bg.shape[-1], bg.shape[-1], bias_args[1]
-        g["keep"].append(bg)
+        keep = tuple(keep) + (bg,)
     taps = 8 if kind == VS_CONV_K2S2 else 27
     nb = (p.numel() + q.numel() // q.shape[-1] * c_real) * _esize(p) + m_real * c_real * taps * 4 if kind == VS_CONV_UP else \
         (p.numel() // m_ch * m_real + q.numel() // q.shape[-1] * c_real) * _esize(p) + m_real * c_real * taps * 4
     fl = 2.0 * (q.numel() // q.shape[-1]) * taps * m_real * c_real if kind == VS_CONV_UP else 2.0 * (p.numel() // m_ch) * taps * m_real * c_real
-    first = g["split"] is None or bool(g["split"](weight))
-    voxels = n * dp * hp * wp_
-    g["descs"].append((d, first, nb, fl, voxels))
-    g["keep"].extend(t for t in keep if t is not None)
-    if not _on_backward_end(g, _group_backward_done):
-        flush_wgrads()                          # not inside a backward pass: nothing will call back
-
-
-def _group_backward_done():
-    _USE_EPOCH[0] += 1                          # a backward pass ended: the use counts of the next forward start over (_count_use)
-    _GROUP["callback"] = False
-    flush_wgrads(first_only=_GROUP["split"] is not None)
-    _GROUP["slots"] = {}
+    _queue_desc(weight, d, p.dtype, nb, fl, n * dp * hp * wp_, keep)
 
 
 def pending_wgrads():
@@ -906,17 +960,16 @@ def flush_wgrads(first_only=False):
 
 
 # Weight gradient fused into the backward-data launch (csrc/igemm_k3tw.h; round 5): the 8 -> 8 3x3x3 layers whose backward-data kernel already holds both
-# operands of dW.  Taken when the weight is used exactly ONCE in this pass (counted at forward time; _USE_EPOCH moves on when a backward pass ends) and its
+# operands of dW.  Taken when the weight is used exactly ONCE in this pass (counted at forward time; _PENDING["epoch"] moves on when a backward pass ends) and its
 # gradient can be deferred like every grouped one; the slabs the launch writes join the grouped reduction as a VS_WGRAD_SLABS descriptor.
 FUSE_WGRAD = os.environ.get("VS_FUSE_WGRAD", "1") != "0"
 VS_WGRAD_SLABS = 16
-_USE_EPOCH = [0]
 
 
 def _count_use(weight):
     u = getattr(weight, "_vs_use", None)
-    if u is None or u[0] != _USE_EPOCH[0]:
-        weight._vs_use = [_USE_EPOCH[0], 1]
+    if u is None or u[0] != _PENDING["epoch"]:
+        weight._vs_use = [_PENDING["epoch"], 1]
     else:
         u[1] += 1
 
@@ -924,7 +977,7 @@ def _count_use(weight):
 def _wgrad_fusable(gy, x, weight):
     if not (FUSE_WGRAD and _GROUP["enabled"] and gy.dtype != torch.float32 and gy.shape[-1] == 8 and x.shape[-1] == 8):
         return False
-    if getattr(weight, "_vs_use", None) != [_USE_EPOCH[0], 1] or _GROUP["slots"].get(id(weight)) is not None:
+    if getattr(weight, "_vs_use", None) != [_PENDING["epoch"], 1] or id(weight) in _PENDING["slots"]:
         return False
     if not (weight.is_leaf and weight.grad is None and not _has_hooks(weight) and not torch.is_grad_enabled()):
         return False                            # the conditions under which _side_grads defers a gradient
@@ -933,28 +986,19 @@ def _wgrad_fusable(gy, x, weight):
 
 
 def _group_submit_slabs(weight, slabs, nslabs, m_real, c_real, keep, bias=None):
-    """register the slabs of a fused launch with the pass's grouped weight gradients; -> the (still unwritten) gradient tensor handed to autograd
-    (bias = (parameter, partial sums double [nslabs][m_real]): -> (gw, gb))"""
-    g = _GROUP
-    if g["descs"] and g["dtype"] != keep[0].dtype:
-        flush_wgrads()
-    g["dtype"] = keep[0].dtype
+    """register the slabs of a fused launch with the pass's grouped weight gradients; -> (gw, gb), the (still unwritten) gradient tensors handed to autograd
+    (bias = (parameter, partial sums double [nslabs][m_real]); gb None without)"""
     gw = _grad_slot(weight, weight.shape)
     gb = None
     d = WgradDesc(slabs.data_ptr(), None, None, None, gw.data_ptr(), None, None, 0, 0, 0, nslabs, 0, 0, 0, 8, 8, m_real, c_real, VS_WGRAD_SLABS, 0)
     if bias is not None:
         gb = _grad_slot(bias[0], (m_real,))
         d.bias_g, d.db, d.bias_rows, d.bias_c_ch, d.bias_c_real = bias[1].data_ptr(), gb.data_ptr(), nslabs, m_real, m_real
-        g["keep"].append(bias[1])
-    # third field: this destination belongs to a SLAB descriptor — vs_conv_wgrad_multi does not let a regular descriptor share it (ADVICE r05: the forward-time use
+    # from_slabs: this destination belongs to a SLAB descriptor — vs_conv_wgrad_multi does not let a regular descriptor share it (ADVICE r05: the forward-time use
     # count can read 1 with two live uses when an unrelated backward pass ended between two forwards of the same weight); _side_grads gives a later use its own
-    g["slots"][id(weight)] = (gw.data_ptr(), None if gb is None else gb.data_ptr(), True)
-    first = g["split"] is None or bool(g["split"](weight))
-    g["descs"].append((d, first, float(slabs.numel() * 4), 0.0, 0))
-    g["keep"].append(slabs)
-    if not _on_backward_end(g, _group_backward_done):
-        flush_wgrads()
-    return gw if bias is None else (gw, gb)
+    _PENDING["slots"][id(weight)] = _Slot(gw.data_ptr(), _p(gb), True)
+    _queue_desc(weight, d, keep[0].dtype, float(slabs.numel() * 4), 0.0, 0, (None if bias is None else bias[1], slabs))
+    return gw, gb
 
 
 def _grad_slot(param, shape):
@@ -975,12 +1019,12 @@ def _side_grads(weight, keep, wgrad_args, bias_args, bias=None):
     off, the parameter already holds a gradient to accumulate into, carries hooks, or grad mode is on (autograd would then clone the
     still-unwritten tensor); -> (gw, gb)."""
     grouping = _GROUP["enabled"]
-    slot = _GROUP["slots"].get(id(weight)) if grouping and weight.is_leaf else None
-    if slot is not None and len(slot) > 2 and slot[2]:
+    slot = _PENDING["slots"].get(id(weight)) if grouping and weight.is_leaf else None
+    if slot is not None and slot.from_slabs:
         slot = None                             # the first use went into its backward-data launch (slabs): this use gets a destination of its own, autograd adds the two
     if slot is not None:
         # a later use of the same weight in this pass: one more descriptor with the first use's destination, nothing returned to autograd
-        _group_submit(weight, keep, wgrad_args, bias_args if slot[1] is not None else None, slot[0], slot[1])
+        _group_submit(weight, keep, wgrad_args, bias_args if slot.gb_ptr is not None else None, slot.gw_ptr, slot.gb_ptr)
         return None, None
     gw = _grad_slot(weight, weight.shape)
     gb = None
@@ -992,7 +1036,7 @@ def _side_grads(weight, keep, wgrad_args, bias_args, bias=None):
     deferrable = (weight.is_leaf and weight.grad is None and not _has_hooks(weight) and not torch.is_grad_enabled()
                   and (bias is None or (bias.is_leaf and not _has_hooks(bias))))
     if grouping and deferrable:
-        _GROUP["slots"][id(weight)] = (gw.data_ptr(), None if gb is None else gb.data_ptr())      # addresses, not tensors: see below
+        _PENDING["slots"][id(weight)] = _Slot(gw.data_ptr(), _p(gb), False)      # addresses, not tensors: see below
         # the descriptor holds raw pointers only: AccumulateGrad must find gw / gb unshared to adopt them as .grad without a copy
         _group_submit(weight, keep, wgrad_args, bias_args, gw, gb)
         return gw, gb
@@ -1007,16 +1051,28 @@ def _dead_bias_grad(bias, n, device):
     the flat bucket when one is registered, else zeros carved from the statistics arena (no fill launch).  Later uses of the same
     bias in one pass return None (nothing to accumulate)."""
     if bias is not None and _GROUP["enabled"]:
-        key = ("dead", id(bias))
-        if key in _GROUP["slots"]:
+        if id(bias) in _PENDING["dead_biases"]:
             return None
-        _GROUP["slots"][key] = True
-        if not _on_backward_end(_GROUP, _group_backward_done):
-            _GROUP["slots"].pop(key, None)
+        if _PENDING.join():
+            _PENDING["dead_biases"].add(id(bias))
     view = getattr(bias, "_vs_grad_view", None) if bias is not None else None
     if view is not None and bias.grad is None:
         return view.detach()
     return _new_stats(1, (n + 1) // 2, device, width=1).view(-1).view(torch.float32)[:n]
+
+
+def _conv_param_grads(weight, bias, keep, wgrad_args, bias_args, needs, live_bias=True):
+    """The parameter-gradient tail of a conv backward -> (gw, gb).  keep / wgrad_args: as _side_grads takes them; bias_args = (the gradient the bias gradient sums,
+    real channels); needs: the Function's needs_input_grad (weight at 2, bias at 3).  live_bias False: the bias feeds InstanceNorm (_dead_bias_grad)."""
+    want_b = bias is not None and needs[3]
+    gw = gb = None
+    if needs[2]:
+        gw, gb = _side_grads(weight, keep, wgrad_args, bias_args if want_b and live_bias else None, bias if live_bias else None)
+    elif want_b and live_bias:
+        gb = bias_grad(*bias_args)
+    if want_b and not live_bias:
+        gb = _dead_bias_grad(bias, bias.shape[0], weight.device)
+    return gw, gb
 
 
 def in_relu_bwd(g, x, xs, inplace=True):
@@ -1060,7 +1116,7 @@ class ConvK3(torch.autograd.Function):
         ctx.save_for_backward(x, xs, weight)
         ctx.has_bias = bias is not None
         ctx.bias_ref = bias                   # a Parameter (long-lived leaf): only its gradient slot is looked up in backward
-        ctx.defer = bool(getattr(x, "_vs_defer_apply", False)) and xs is not None     # see _LAZY_APPLY
+        ctx.defer = _wants_defer(x, xs)
         if ctx.needs_input_grad[2]:
             _count_use(weight)                # see _wgrad_fusable
         ctx.mark_non_differentiable(ys)
@@ -1076,41 +1132,26 @@ class ConvK3(torch.autograd.Function):
         cout, cin = weight.shape[0], weight.shape[1]
         gx = gw = gb = None
         lazy = _take_lazy(gy)                   # gy is an un-applied gradient handed over by the consumer of this conv's output
-        if lazy is not None and not (ctx.needs_input_grad[0] and _fa_supported(gy, x, xs is not None)):
+        if lazy is not None and not (ctx.needs_input_grad[0] and lib.vs_conv_k3_fused_apply_supported(*gy.shape, x.shape[-1], 1 if xs is not None else 0, vs_dtype(gy))):
             gy, lazy = apply_lazy(gy, lazy), None     # no fused-apply kernel for this launch / no input gradient wanted: apply now
         if ctx.needs_input_grad[0]:
             wpb = pack_weight_cached(weight, VS_PACK_ROWS_D1_FLIP, gy.shape[-1], k3_pack_dtype(gy))
             want_gb0 = ctx.has_bias and ctx.needs_input_grad[3] and ctx.live_bias
             if xs is not None and ctx.needs_input_grad[2] and not want_gb0 and _wgrad_fusable(gy, x, weight):
                 # the backward-data launch of this layer forms its weight gradient as well (nothing else reads the applied gradient)
-                gx, gw = conv_bwd_data_lazy(gy, wpb, x, xs, VS_CONV_K3, real_channels=(cout, cin), defer=ctx.defer, lazy=lazy,
-                                            fuse_wgrad=(weight, cout, cin))
+                gx, _, gw = _conv_bwd_data(gy, wpb, x, xs, VS_CONV_K3, real_channels=(cout, cin), defer=ctx.defer, lazy=lazy,
+                                               fuse_wgrad=(weight, cout, cin))
                 gb = _dead_bias_grad(ctx.bias_ref, ctx.bias_ref.shape[0], x.device) if ctx.has_bias and ctx.needs_input_grad[3] else None
                 return gx, None, gw, gb, None
-            if lazy is not None and xs is not None:
-                gx, gy = conv_bwd_data_lazy(gy, wpb, x, xs, VS_CONV_K3, real_channels=(cout, cin), defer=ctx.defer, lazy=lazy,
-                                            want_dx=ctx.needs_input_grad[2])
-            elif lazy is not None:                # the conv's own input is a stored tensor (VAE.in_block on the prediction): no sums to fuse
-                ax, axs, asums = lazy
-                gx = torch.empty_like(x)
-                dx = torch.empty_like(gy) if ctx.needs_input_grad[2] else None
-                n_, d_, h_, w_, c_ = gy.shape
-                check(lib.vs_conv_k3_bwd_data_fused_apply(gy.data_ptr(), ax.data_ptr(), axs.data_ptr(), asums.data_ptr(), wpb.data_ptr(), gx.data_ptr(),
-                                                          None, None, None, _p(dx), n_, d_, h_, w_, c_, x.shape[-1], vs_dtype(x), EPS_IN, _stream()),
-                      "conv_k3_bwd_data_fused_apply")
-                gy = dx
-            elif xs is not None:
-                gx = conv_bwd_data_lazy(gy, wpb, x, xs, VS_CONV_K3, real_channels=(cout, cin), defer=ctx.defer)
+            if lazy is not None or xs is not None:
+                gx, dx, _ = _conv_bwd_data(gy, wpb, x, xs, VS_CONV_K3, real_channels=(cout, cin), defer=ctx.defer, lazy=lazy,
+                                               want_dx=ctx.needs_input_grad[2])
+                if lazy is not None:
+                    gy = dx                         # the applied gradient of this conv's output: what its weight gradient reads
             else:
                 gx, _ = conv_gather(gy, None, wpb, None, x.shape[-1], VS_CONV_K3, False, real_channels=(cout, cin))
-        want_gb = ctx.has_bias and ctx.needs_input_grad[3]
-        if ctx.needs_input_grad[2]:
-            gw, gb = _side_grads(weight, (gy, x, xs), (gy, None, x, xs, cout, cin, VS_CONV_K3),
-                                 (gy, cout) if want_gb and ctx.live_bias else None, ctx.bias_ref if ctx.live_bias else None)
-        elif want_gb and ctx.live_bias:
-            gb = bias_grad(gy, cout)
-        if want_gb and not ctx.live_bias:
-            gb = _dead_bias_grad(ctx.bias_ref, ctx.bias_ref.shape[0], x.device)
+        gw, gb = _conv_param_grads(weight, ctx.bias_ref, (gy, x, xs), (gy, None, x, xs, cout, cin, VS_CONV_K3), (gy, cout), ctx.needs_input_grad,
+                                   live_bias=ctx.live_bias)
         return gx, None, gw, gb, None
 
 
@@ -1262,14 +1303,9 @@ class ConvK3Chain(torch.autograd.Function):
                                        vs_dtype(gy), EPS_IN, _stream()), "conv_k3_chain (backward)")
         out = [g_in if ctx.needs_input_grad[0] else None, None]
         for l in range(nl):
-            wt, bias = weights[l], ctx.bias_refs[l]
-            gw = gb = None
-            if ctx.needs_input_grad[2 + 2 * l]:
-                ax, axs = acts[l]
-                gw, _ = _side_grads(wt, (applied[l], ax, axs), (applied[l], None, ax, axs, wt.shape[0], wt.shape[1], VS_CONV_K3), None, None)
-            if bias is not None and ctx.needs_input_grad[3 + 2 * l]:
-                gb = _dead_bias_grad(bias, bias.shape[0], dev)
-            out += [gw, gb]
+            wt, (ax, axs) = weights[l], acts[l]
+            out += _conv_param_grads(wt, ctx.bias_refs[l], (applied[l], ax, axs), (applied[l], None, ax, axs, wt.shape[0], wt.shape[1], VS_CONV_K3), None,
+                                     ctx.needs_input_grad[2 * l:], live_bias=False)
         return tuple(out)
 
 
@@ -1299,7 +1335,7 @@ class ConvK3Softmax(torch.autograd.Function):
         ctx.has_bias = bias is not None
         ctx.bias_ref = bias
         ctx.drop = (float(drop_p), drop_seed)
-        ctx.defer = bool(getattr(x, "_vs_defer_apply", False)) and xs is not None
+        ctx.defer = _wants_defer(x, xs)
         if ctx.needs_input_grad[2]:
             _count_use(weight)                # see _wgrad_fusable
         return prob
@@ -1314,26 +1350,15 @@ class ConvK3Softmax(torch.autograd.Function):
             fused = _out_block_bwd_fused(ctx, x, xs, weight, prob, gprob, None)      # the whole backward as one launch (csrc/igemm_k3tw.h SM)
             if fused is not None:
                 return fused
-        gl = torch.empty((n, d, h, w, 8), dtype=x.dtype, device=x.device)
-        if ctx.fused2:
-            check(lib.vs_softmax2_dropout_bwd(prob.data_ptr(), gprob.data_ptr(), gl.data_ptr(), n, d * h * w, 8, vs_dtype(x),
-                                              ctx.drop[0], ctx.drop[1], _stream()), "softmax2_bwd")
-        else:
-            check(lib.vs_softmax_cl_bwd(prob.data_ptr(), gprob.data_ptr(), gl.data_ptr(), n, d * h * w, 8, nc, vs_dtype(x),
-                                        ctx.drop[0], ctx.drop[1], _stream()), "softmax_cl_bwd")
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            wpb = pack_weight_cached(weight, VS_PACK_ROWS_D1_FLIP, 8, k3_pack_dtype(x))
-            if xs is not None:
-                gx = conv_bwd_data_lazy(gl, wpb, x, xs, VS_CONV_K3, real_channels=(nc, weight.shape[1]), defer=ctx.defer)
+
+        def softmax_bwd(gl):
+            if ctx.fused2:
+                check(lib.vs_softmax2_dropout_bwd(prob.data_ptr(), gprob.data_ptr(), gl.data_ptr(), n, d * h * w, 8, vs_dtype(x),
+                                                  ctx.drop[0], ctx.drop[1], _stream()), "softmax2_bwd")
             else:
-                gx, _ = conv_gather(gl, None, wpb, None, c, VS_CONV_K3, False)
-        if ctx.needs_input_grad[2]:
-            gw, gb = _side_grads(weight, (gl, x, xs), (gl, None, x, xs, nc, weight.shape[1], VS_CONV_K3),
-                                 (gl, nc) if ctx.has_bias and ctx.needs_input_grad[3] else None, ctx.bias_ref)
-        elif ctx.has_bias and ctx.needs_input_grad[3]:
-            gb = bias_grad(gl, nc)
-        return gx, None, gw, gb, None, None
+                check(lib.vs_softmax_cl_bwd(prob.data_ptr(), gprob.data_ptr(), gl.data_ptr(), n, d * h * w, 8, nc, vs_dtype(x),
+                                            ctx.drop[0], ctx.drop[1], _stream()), "softmax_cl_bwd")
+        return _out_block_bwd_unfused(ctx, x, xs, weight, softmax_bwd, nc)
 
 
 class ConvK3SoftmaxCL(torch.autograd.Function):
@@ -1357,7 +1382,7 @@ class ConvK3SoftmaxCL(torch.autograd.Function):
         ctx.has_bias = bias is not None
         ctx.bias_ref = bias
         ctx.drop = (float(drop_p), drop_seed)
-        ctx.defer = bool(getattr(x, "_vs_defer_apply", False)) and xs is not None
+        ctx.defer = _wants_defer(x, xs)
         if ctx.needs_input_grad[2]:
             _count_use(weight)                # see _wgrad_fusable
         ctx.set_materialize_grads(False)
@@ -1374,22 +1399,28 @@ class ConvK3SoftmaxCL(torch.autograd.Function):
         fused = _out_block_bwd_fused(ctx, x, xs, weight, prob, gprob, gcl)
         if fused is not None:
             return fused
-        gl = torch.empty((n, d, h, w, 8), dtype=x.dtype, device=x.device)
-        check(lib.vs_softmax2_cl_bwd(prob.data_ptr(), _p(gprob), _p(gcl), gl.data_ptr(), n, d * h * w, 8, vs_dtype(x), ctx.drop[0], ctx.drop[1],
-                                     _stream()), "softmax2_cl_bwd")
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            wpb = pack_weight_cached(weight, VS_PACK_ROWS_D1_FLIP, 8, k3_pack_dtype(x))
-            if xs is not None:
-                gx = conv_bwd_data_lazy(gl, wpb, x, xs, VS_CONV_K3, real_channels=(2, weight.shape[1]), defer=ctx.defer)
-            else:
-                gx, _ = conv_gather(gl, None, wpb, None, c, VS_CONV_K3, False)
-        if ctx.needs_input_grad[2]:
-            gw, gb = _side_grads(weight, (gl, x, xs), (gl, None, x, xs, 2, weight.shape[1], VS_CONV_K3),
-                                 (gl, 2) if ctx.has_bias and ctx.needs_input_grad[3] else None, ctx.bias_ref)
-        elif ctx.has_bias and ctx.needs_input_grad[3]:
-            gb = bias_grad(gl, 2)
-        return gx, None, gw, gb, None, None
+
+        def softmax_bwd(gl):
+            check(lib.vs_softmax2_cl_bwd(prob.data_ptr(), _p(gprob), _p(gcl), gl.data_ptr(), n, d * h * w, 8, vs_dtype(x), ctx.drop[0], ctx.drop[1],
+                                         _stream()), "softmax2_cl_bwd")
+        return _out_block_bwd_unfused(ctx, x, xs, weight, softmax_bwd, 2)
+
+
+def _out_block_bwd_unfused(ctx, x, xs, weight, softmax_bwd, nc):
+    """out_block's backward as its separate launches: softmax_bwd(gl) writes the gradient of the 8 stored logit channels (nc real), then the 3x3x3 conv's
+    backward-data and parameter gradients.  -> the tuple ConvK3Softmax[CL].backward returns"""
+    n, d, h, w, c = x.shape
+    gl = torch.empty((n, d, h, w, 8), dtype=x.dtype, device=x.device)
+    softmax_bwd(gl)
+    gx = None
+    if ctx.needs_input_grad[0]:
+        wpb = pack_weight_cached(weight, VS_PACK_ROWS_D1_FLIP, 8, k3_pack_dtype(x))
+        if xs is not None:
+            gx = _conv_bwd_data(gl, wpb, x, xs, VS_CONV_K3, real_channels=(nc, weight.shape[1]), defer=ctx.defer)[0]
+        else:
+            gx, _ = conv_gather(gl, None, wpb, None, c, VS_CONV_K3, False)
+    gw, gb = _conv_param_grads(weight, ctx.bias_ref, (gl, x, xs), (gl, None, x, xs, nc, weight.shape[1], VS_CONV_K3), (gl, nc), ctx.needs_input_grad)
+    return gx, None, gw, gb, None, None
 
 
 FUSE_SOFTMAX_BWD = os.environ.get("VS_FUSE_SOFTMAX_BWD", "1") != "0"
@@ -1419,26 +1450,17 @@ def _out_block_bwd_fused(ctx, x, xs, weight, prob, gprob, gcl):
     nslabs = lib.vs_conv_k3_bwd_data_wgrad_slabs(n, d, h, w) if want_w else 0
     slabs = torch.empty(nslabs * 1728, dtype=torch.float32, device=x.device) if want_w else None
     bpart = torch.empty(nslabs * 2, dtype=torch.float64, device=x.device) if (want_w and want_b) else None
-    kid = nb = fl = None
-    if PROFILE is not None:
-        kid = "k3tw_kernel<%s,2,%s>" % (_tname(x), "true" if want_w else "false")
-        nb = (4 * n * d * h * w * 4) + (0 if gcl is None else gcl.numel() * _esize(x)) + 2 * g.numel() * _esize(x)
-        fl = (2.0 if want_w else 1.0) * 2.0 * (g.numel() // c) * 27 * 2 * weight.shape[1]
-    with _timed(kid, nb, fl, "out_block bwd%s (%d, %d, %d, %d)" % ("+wgrad" if want_w else "", n, d, h, w)):
+    profile = lambda: ("k3tw_kernel<%s,2,%s>" % (_tname(x), "true" if want_w else "false"),
+                       (4 * n * d * h * w * 4) + (0 if gcl is None else gcl.numel() * _esize(x)) + 2 * g.numel() * _esize(x),
+                       (2.0 if want_w else 1.0) * 2.0 * (g.numel() // c) * 27 * 2 * weight.shape[1])
+    with _timed(profile, detail="out_block bwd%s (%d, %d, %d, %d)" % ("+wgrad" if want_w else "", n, d, h, w)):
         check(lib.vs_conv_k3_softmax2_bwd_data(prob.data_ptr(), _p(gprob), _p(gcl), wpb.data_ptr(), g.data_ptr(), x.data_ptr(), xs.data_ptr(), sums.data_ptr(),
                                                _p(slabs), _p(bpart), n, d, h, w, vs_dtype(x), EPS_IN, ctx.drop[0], ctx.drop[1], _stream()),
               "conv_k3_softmax2_bwd_data")
     gw = gb = None
     if want_w:
-        if want_b:
-            gw, gb = _group_submit_slabs(weight, slabs, nslabs, 2, weight.shape[1], (x,), bias=(ctx.bias_ref, bpart))
-        else:
-            gw = _group_submit_slabs(weight, slabs, nslabs, 2, weight.shape[1], (x,))
-    if ctx.defer:
-        _defer_register(g, x, xs, sums)
-    else:
-        _apply_in_place(g, x, xs, sums)
-    return g, None, gw, gb, None, None
+        gw, gb = _group_submit_slabs(weight, slabs, nslabs, 2, weight.shape[1], (x,), bias=(ctx.bias_ref, bpart) if want_b else None)
+    return _finish(g, x, xs, sums, ctx.defer), None, gw, gb, None, None
 
 
 def out_block_softmax(x, xs, weight, bias, drop_p=0.0, drop_seed=0):
@@ -1470,9 +1492,8 @@ class ConvK2S2(torch.autograd.Function):
         wp = pack_weight_cached(weight, VS_PACK_ROWS_D0, x.shape[-1], x.dtype)
         y, _ = conv_gather(x, xs, wp, bias, cpad(weight.shape[0]), VS_CONV_K2S2, False)
         ctx.save_for_backward(x, xs, weight)
-        ctx.has_bias = bias is not None
         ctx.bias_ref = bias
-        ctx.defer = bool(getattr(x, "_vs_defer_apply", False)) and xs is not None     # see _LAZY_APPLY
+        ctx.defer = _wants_defer(x, xs)
         return y
 
     @staticmethod
@@ -1484,14 +1505,10 @@ class ConvK2S2(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             wpb = pack_weight_cached(weight, VS_PACK_SCATTER_D1, gy.shape[-1], gy.dtype)
             if xs is not None:
-                gx = conv_bwd_data_lazy(gy, wpb, x, xs, VS_CONV_K2S2, scatter=True, defer=ctx.defer)
+                gx = _conv_bwd_data(gy, wpb, x, xs, VS_CONV_K2S2, scatter=True, defer=ctx.defer)[0]
             else:
                 gx = conv_scatter(gy, None, wpb, None, x.shape[-1])
-        if ctx.needs_input_grad[2]:
-            gw, gb = _side_grads(weight, (gy, x, xs), (gy, None, x, xs, cout, cin, VS_CONV_K2S2),
-                                 (gy, cout) if ctx.has_bias and ctx.needs_input_grad[3] else None, ctx.bias_ref)
-        elif ctx.has_bias and ctx.needs_input_grad[3]:
-            gb = bias_grad(gy, cout)
+        gw, gb = _conv_param_grads(weight, ctx.bias_ref, (gy, x, xs), (gy, None, x, xs, cout, cin, VS_CONV_K2S2), (gy, cout), ctx.needs_input_grad)
         return gx, None, gw, gb
 
 
@@ -1504,9 +1521,8 @@ class ConvT2S2(torch.autograd.Function):
         wp = pack_weight_cached(weight, VS_PACK_SCATTER_D1, x.shape[-1], x.dtype)
         y = conv_scatter(x, xs, wp, bias, cpad(weight.shape[1]))
         ctx.save_for_backward(x, xs, weight)
-        ctx.has_bias = bias is not None
         ctx.bias_ref = bias
-        ctx.defer = bool(getattr(x, "_vs_defer_apply", False)) and xs is not None     # see _LAZY_APPLY
+        ctx.defer = _wants_defer(x, xs)
         return y
 
     @staticmethod
@@ -1518,14 +1534,10 @@ class ConvT2S2(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             wpb = pack_weight_cached(weight, VS_PACK_ROWS_D0, gy.shape[-1], gy.dtype)
             if xs is not None:
-                gx = conv_bwd_data_lazy(gy, wpb, x, xs, VS_CONV_K2S2, defer=ctx.defer)
+                gx = _conv_bwd_data(gy, wpb, x, xs, VS_CONV_K2S2, defer=ctx.defer)[0]
             else:
                 gx, _ = conv_gather(gy, None, wpb, None, x.shape[-1], VS_CONV_K2S2, False)
-        if ctx.needs_input_grad[2]:
-            gw, gb = _side_grads(weight, (gy, x, xs), (x, xs, gy, None, cin, cout, VS_CONV_K2S2),
-                                 (gy, cout) if ctx.has_bias and ctx.needs_input_grad[3] else None, ctx.bias_ref)
-        elif ctx.has_bias and ctx.needs_input_grad[3]:
-            gb = bias_grad(gy, cout)
+        gw, gb = _conv_param_grads(weight, ctx.bias_ref, (gy, x, xs), (x, xs, gy, None, cin, cout, VS_CONV_K2S2), (gy, cout), ctx.needs_input_grad)
         return gx, None, gw, gb
 
 
@@ -1640,19 +1652,15 @@ class UpConvK3(torch.autograd.Function):
         ctx.b3 = b3                                # the 3x3x3 conv's bias: dead (InstanceNorm follows) — its gradient is returned as zeros
         y = torch.empty((n, 2 * d, 2 * h, 2 * w, co), dtype=x.dtype, device=x.device)
         ys = _new_stats(n, co, x.device)
-        kid = nb = fl = None
-        if PROFILE is not None:
-            kid = "k4t_kernel<%d,%s>" % (min(c, 32), _tname(x))
-            nb = (x.numel() + y.numel()) * _esize(x) + 64 * co * c * _esize(x)
-            fl = 2.0 * (x.numel() // c) * 64 * co * c
-        with _timed(kid, nb, fl, "up x%s->m%d" % (tuple(x.shape), co)):
+        profile = lambda: ("k4t_kernel<%d,%s>" % (min(c, 32), _tname(x)), (x.numel() + y.numel()) * _esize(x) + 64 * co * c * _esize(x), 2.0 * (x.numel() // c) * 64 * co * c)
+        with _timed(profile, detail="up x%s->m%d" % (tuple(x.shape), co)):
             check(lib.vs_up_conv_fwd(x.data_ptr(), _p(xs), plan["img_f"].data_ptr(), plan["taps_f"].data_ptr(), plan["btab"].data_ptr(), y.data_ptr(),
                                      ys.data_ptr(), n, d, h, w, c, co, vs_dtype(x), EPS_IN, _stream()), "up_conv_fwd")
         ctx.save_for_backward(x, xs)
         ctx.plan = plan
         ctx.co = co
         ctx.params = (wt, bt, w3)               # Parameters (long-lived leaves): read by the chain rule, their gradient slots looked up in backward
-        ctx.defer = bool(getattr(x, "_vs_defer_apply", False)) and xs is not None
+        ctx.defer = _wants_defer(x, xs)
         ctx.mark_non_differentiable(ys)
         ctx.set_materialize_grads(False)
         return y, ys
@@ -1677,23 +1685,12 @@ class UpConvK3(torch.autograd.Function):
         gx = torch.empty_like(x)
         sums = _new_stats(n, c, x.device) if xs is not None else None
         plan = ctx.plan
-        kid = nb = fl = None
-        if PROFILE is not None:
-            kid = "k4g_kernel<%s>" % _tname(x)
-            nb = (gy.numel() + (2 if xs is not None else 1) * x.numel()) * _esize(x) + 64 * ctx.co * c * _esize(x)
-            fl = 2.0 * (x.numel() // c) * 64 * ctx.co * c
-        with _timed(kid, nb, fl, "up bwd gy%s->m%d" % (tuple(gy.shape), c)):
+        profile = lambda: ("k4g_kernel<%s>" % _tname(x), (gy.numel() + (2 if xs is not None else 1) * x.numel()) * _esize(x) + 64 * ctx.co * c * _esize(x),
+                           2.0 * (x.numel() // c) * 64 * ctx.co * c)
+        with _timed(profile, detail="up bwd gy%s->m%d" % (tuple(gy.shape), c)):
             check(lib.vs_up_conv_bwd_data(gy.data_ptr(), plan["img_b"].data_ptr(), plan["taps_b"].data_ptr(), gx.data_ptr(), _p(x if xs is not None else None),
                                           _p(xs), _p(sums), n, d, h, w, ctx.co, c, vs_dtype(x), EPS_IN, _stream()), "up_conv_bwd_data")
-        if xs is not None:
-            if ctx.defer:
-                _defer_register(gx, x, xs, sums)
-            else:
-                _apply_in_place(gx, x, xs, sums)
-        return gx, None, gwt, gbt, gw3, gb3
-
-
-_UP_JOBS = {}       # id(w3) -> the pending chain-rule job of a trainable composed Up head in the current backward pass
+        return _finish(gx, x, xs, sums, ctx.defer), None, gwt, gbt, gw3, gb3
 
 
 def _up_weight_grads(gy, x, xs, params, co, needs):
@@ -1702,7 +1699,7 @@ def _up_weight_grads(gy, x, xs, params, co, needs):
     (unwritten until then, like every deferred weight gradient); later uses of the same weights in one pass add to the first use's job."""
     wt, bt, w3 = params
     n, d, h, w, c = x.shape
-    job = _UP_JOBS.get(id(w3))
+    job = _PENDING["up_jobs"].get(id(w3))
     first = job is None
     if first:
         dev = x.device
@@ -1714,7 +1711,7 @@ def _up_weight_grads(gy, x, xs, params, co, needs):
         job = {"dweff": torch.empty(8 * co * c * 27, dtype=torch.float32, device=dev),
                "faces": _new_stats(1, 27 * co // 2, dev),          # zeroed, statistics format: vs_up_faces accumulates (every use of the weights)
                "gwt": _p(gwt), "gbt": _p(gbt), "gw3": _p(gw3), "params": params, "co": co}
-        _UP_JOBS[id(w3)] = job
+        _PENDING["up_jobs"][id(w3)] = job
     check(lib.vs_up_faces(gy.data_ptr(), job["faces"].data_ptr(), n, 2 * d, 2 * h, 2 * w, co, vs_dtype(gy), _stream()), "up_faces")
     _group_submit(w3, (gy, x, xs), (gy, None, x, xs, 8 * co, c, VS_CONV_UP), None, job["dweff"], None, up_co=co)
     deferrable = all(p is None or (p.is_leaf and p.grad is None and not _has_hooks(p)) for p in (wt, bt, w3)) and not torch.is_grad_enabled()
@@ -1724,11 +1721,11 @@ def _up_weight_grads(gy, x, xs, params, co, needs):
 
 
 def _run_up_jobs():
-    for job in _UP_JOBS.values():
+    for job in _PENDING["up_jobs"].values():
         wt, bt, w3 = job["params"]
         check(lib.vs_up_chain(job["dweff"].data_ptr(), job["faces"].data_ptr(), wt.data_ptr(), _p(bt), w3.data_ptr(), job["gwt"], job["gbt"],
                               job["gw3"], wt.shape[0], wt.shape[1], job["co"], _stream()), "up_chain")
-    _UP_JOBS.clear()
+    _PENDING["up_jobs"].clear()
 
 
 class Materialize(torch.autograd.Function):
