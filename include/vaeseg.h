@@ -985,6 +985,34 @@ int vs_grad_finite_multi(const float* const* grads, const long long* sizes, cons
                          float* found_inf, void* stream);
 int vs_loss_scale_update(float* scale, int* growth_tracker, float* found_inf, float growth_factor, float backoff_factor,
                          int growth_interval, void* stream);
+/* ---- global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, norm type 2) and Nesterov momentum -------------------------------------
+ * The norm spans every tensor of every param group, is taken AFTER the all-reduce and AFTER unscaling, and is summed in ONE order (no atomics),
+ * so every data-parallel rank derives the same coefficient from the same all-reduced bits:
+ *   vs_grad_sqnorm_multi   partials[b] = sum of squares (fp64 of exact fp32 x fp32 products) of chunk b of the tables vs_grad_finite_multi takes;
+ *                          a function of the chunk's values alone (aligned vector loads and ragged / misaligned dword loads add in the same order).
+ *                          The caller concatenates the partials of all its groups: partials + offset per group.
+ *   vs_grad_clip_finish    one workgroup adds all n_partials in a fixed order.  clip is a DEVICE record float[4] = {max_norm, norm, coef, 0}:
+ *                          max_norm is READ (a captured launch follows a change), norm = (float)(sqrt(sum) / S) with S = loss_scale[0] (NULL: 1),
+ *                          coef = min(1, max_norm / (norm + 1e-6f)) in fp32 — a NaN norm gives 1, an infinite norm gives 0.
+ * The steps take clip_coef = clip + 2 (NULL: no clipping) and multiply the unscaled gradient by it before weight decay is added:
+ *   gi = (g / S) * coef + wd * p;  b = momentum * m + gi;  p -= lr * (nesterov ? gi + momentum * b : b)          (momentum == 0: p -= lr * gi)
+ * Each of these multiply-adds is ONE fused multiply-add, as vs_sgd_momentum_*_multi has always been compiled, so a step with coef == 1 and
+ * nesterov == 0 gives the bits of the plain step.  vs_sgd_step_multi with clip_coef NULL and nesterov 0 IS vs_sgd_momentum_scaled_multi.
+ * vs_sgd_step_dev_multi reads hyper[4] = {lr, momentum, weight_decay, nesterov (0 / 1)} from DEVICE memory.  Momentum buffers must exist and
+ * hold zeros before the first step. */
+int vs_grad_sqnorm_multi(const float* const* grads, const long long* sizes, const int* block_map, int n_blocks, double* partials,
+                         void* stream);
+int vs_grad_clip_finish(const double* partials, int n_partials, float* clip, const float* loss_scale, void* stream);
+int vs_sgd_step_multi(float* const* params, const float* const* grads, float* const* bufs, const long long* sizes,
+                      const int* block_map, int n_blocks, float lr, float momentum, float weight_decay, int nesterov,
+                      const float* clip_coef, const float* loss_scale, const float* found_inf, void* stream);
+int vs_sgd_step_dev_multi(float* const* params, const float* const* grads, float* const* bufs, const long long* sizes,
+                          const int* block_map, int n_blocks, const float* hyper, const float* clip_coef, const float* loss_scale,
+                          const float* found_inf, void* stream);
+int vs_adam_clip_multi(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                       const long long* sizes, const int* block_map, int n_blocks, float lr, double beta1, double beta2,
+                       float eps, float weight_decay, int step, const float* clip_coef, const float* loss_scale, const float* found_inf,
+                       void* stream);
 /* EMA teacher: t = alpha*t + (1-alpha)*s       (main_target.py:512-516) */
 int vs_ema_multi(float* const* teacher, const float* const* student, const long long* sizes, const int* block_map,
                  int n_blocks, float alpha, void* stream);

@@ -1,0 +1,38 @@
+"""numpy oracle of the clipped / Nesterov SGD step (vae_segmentation_amd/optim.py, csrc/misc.hip): the global gradient norm in fp64, the clip
+coefficient by torch.nn.utils.clip_grad_norm_'s rule in fp32, and the update with every fp32 operation rounded on its own."""
+import numpy as np
+
+F = np.float32
+
+
+def global_norm(grads):
+    """2-norm over ALL tensors, summed in fp64 (an fp32 x fp32 product is exact there) -> python float"""
+    total = 0.0
+    for g in grads:
+        g64 = np.asarray(g, dtype=np.float64).ravel()
+        total += float(np.dot(g64, g64))
+    return float(np.sqrt(total))
+
+
+def clip_coef(norm32, max_norm):
+    """c = max_norm / (norm + 1e-6), coef = c if c < 1 else 1, all in fp32: a NaN norm gives 1, an infinite norm gives 0"""
+    with np.errstate(all="ignore"):
+        c = F(max_norm) / (F(norm32) + F(1e-6))
+    return c if c < F(1.0) else F(1.0)
+
+
+def sgd_step(p, g, m, lr, momentum, wd, nesterov, coef=1.0, inv_scale=1.0):
+    """-> (p, m) after one step:  gi = (g * inv_scale) * coef + wd * p;  b = momentum * m + gi;  p -= lr * (gi + momentum * b if nesterov else b)
+    (momentum == 0: p -= lr * gi).  m = zeros on the first step (b = gi: torch's clone)."""
+    p, g, m = (np.asarray(a, dtype=F) for a in (p, g, m))
+    lr, momentum, wd, coef, inv_scale = F(lr), F(momentum), F(wd), F(coef), F(inv_scale)
+    gi = ((g * inv_scale).astype(F) * coef).astype(F) + (wd * p).astype(F)
+    gi = gi.astype(F)
+    b = ((momentum * m).astype(F) + gi).astype(F)
+    if momentum == 0:
+        upd = gi
+    elif nesterov:
+        upd = (gi + (momentum * b).astype(F)).astype(F)
+    else:
+        upd = b
+    return (p - (lr * upd).astype(F)).astype(F), b

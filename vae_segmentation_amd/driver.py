@@ -233,9 +233,13 @@ def load_prefix(module, prefix, name="best_model.ckpt"):
 
 
 def make_optimizer(args, groups):
+    """--adam / --momentum / --weight_decay / --nesterov / --grad_clip; without them the reference's SGD(momentum 0.9) or Adam, launched as it always was"""
+    max_norm = getattr(args, "grad_clip", 0.0) or None                 # 0 = off
+    wd = getattr(args, "weight_decay", 0.0)
     if getattr(args, "adam", False):
-        return optim.Adam(groups, lr=args.lr_seg, betas=(0.9, 0.999), weight_decay=0.0)
-    return optim.SGD(groups, lr=args.lr_seg, momentum=0.9, weight_decay=0.0)
+        return optim.Adam(groups, lr=args.lr_seg, betas=(0.9, 0.999), weight_decay=wd, max_norm=max_norm)
+    return optim.SGD(groups, lr=args.lr_seg, momentum=getattr(args, "momentum", 0.9), weight_decay=wd,
+                     nesterov=bool(getattr(args, "nesterov", False)), max_norm=max_norm)
 
 
 def save_checkpoint(prefix, epoch_label, model, optimizer, best):
@@ -808,8 +812,12 @@ def run(args, side="source"):
 
     stepper, stepper_key = None, None
     best, n_outer = 0.0, max(1, args.max_epoch // args.eval_epoch)
+    base_lrs = [grp["lr"] for grp in optimizer.param_groups]
     for epoch in range(n_outer):
         cur["epoch"] = epoch
+        if getattr(args, "lr_schedule", "constant") == "poly":          # a captured step follows through sync_hyper(): no re-capture
+            for grp, base in zip(optimizer.param_groups, base_lrs):
+                grp["lr"] = optim.poly_lr(base, epoch, n_outer, args.poly_power)
         if sampler is not None:
             sampler.set_epoch(epoch)
         skip_da = method in ("domain_adaptation", "domain_adaptation_dis") and epoch == 0 and not getattr(args, "train_first_epoch", False)    # main_target.py:506,697: `if epoch == 0: continue`
@@ -909,6 +917,8 @@ def run(args, side="source"):
                 seen += bs
                 if rank == 0 and idx % args.display_freq == 0:              # logging syncs the host every display_freq steps only
                     parts = ", ".join("%s %.4f" % (k, v.item()) for k, v in aux.items() if k != "batch")
+                    if optimizer.max_norm is not None and optimizer.grad_norm is not None:
+                        parts += ", grad_norm %.4f" % optimizer.grad_norm.item()      # the last step's unclipped global norm, read where the losses are read
                     print("[%3d, %3d] loss: %s" % ((epoch + 1) * args.eval_epoch, idx + 1, parts))
                 if args.max_iters and idx + 1 >= args.max_iters:
                     break
@@ -1101,6 +1111,10 @@ def check_aug_flags(parser, a, seg_loss_methods=SEG_LOSS_METHODS):
         parser.error("--standardize reads the percentiles of merge.npy cases: it needs --real_data")
     if getattr(a, "standardize_above", None) is not None and getattr(a, "standardize", None) is None:
         parser.error("--standardize_above selects the voxels --standardize reads: it needs --standardize")
+    if getattr(a, "nesterov", False) and getattr(a, "adam", False):
+        parser.error("--nesterov is a form of SGD's momentum: it cannot be combined with --adam")
+    if getattr(a, "nesterov", False) and not getattr(a, "momentum", 0.9) > 0:
+        parser.error("--nesterov needs a --momentum above 0")
     if getattr(a, "train_patches", False) and not getattr(a, "real_data", False):
         parser.error("--train_patches cuts its windows from merge.npy cases: it needs --real_data")
     if getattr(a, "train_patches", False) and len(str(a.pan_index).split(",")) + 1 > 8:
@@ -1145,6 +1159,15 @@ def add_native_flags(parser):
                    "-(1 - p)^G ln p; 0 = plain cross-entropy")
     g.add_argument("--class_weights", type=_class_weights, default=None, metavar="W0,W1,...", help="with --seg_loss dice_ce: one cross-entropy weight "
                    ">= 0 per class, the background first — exactly n_class numbers (torch's weighted mean); default all 1")
+    g.add_argument("--momentum", type=_nonnegative, default=0.9, metavar="M", help="SGD's momentum (the reference: 0.9; nnU-Net: 0.99 with --nesterov)")
+    g.add_argument("--weight_decay", type=_nonnegative, default=0.0, metavar="W", help="L2 weight decay of SGD / Adam (the reference: 0; nnU-Net: 3e-5)")
+    g.add_argument("--nesterov", action="store_true", help="SGD with Nesterov momentum: the step is lr * (g + momentum * buf) instead of lr * buf")
+    g.add_argument("--grad_clip", type=_nonnegative, default=0.0, metavar="N", help="clip the global 2-norm of the gradients — over every param group, "
+                   "after the all-reduce and after unscaling — to N on the device, inside the (captured) optimiser step; the loss line then also prints "
+                   "the last step's unclipped norm.  0 (default) = off; nnU-Net: 12")
+    g.add_argument("--lr_schedule", default="constant", choices=["constant", "poly"], help="poly: at the top of every outer epoch each group's learning "
+                   "rate becomes its initial rate * (1 - epoch / epochs) ** --poly_power (nnU-Net's schedule); constant (default): the reference's")
+    g.add_argument("--poly_power", type=_nonnegative, default=0.9, metavar="P", help="with --lr_schedule poly: the exponent")
     g.add_argument("--latent_noise", default="torch", choices=["torch", "philox"], help="vae_train / embed_train / refine_vae: where the VAE's latent noise "
                    "comes from — torch: torch.randn per call, the step launched eagerly (the reference's draw); philox: a stated Philox4x32-10 stream per "
                    "rank (ops.LatentStream, seed 1000 rank + 700) drawn inside the forward launch from a counter in device memory, so the step is captured "

@@ -72,13 +72,86 @@ class LossScaler:
         check(lib.vs_loss_scale_update(self.scale.data_ptr(), self.tracker.data_ptr(), self.found_inf.data_ptr(), g, b, i, _stream()), "loss_scale_update")
 
 
-class SGD(torch.optim.Optimizer):
-    """torch.optim.SGD(lr, momentum, weight_decay) — dampening 0, no nesterov — as one kernel per group."""
+def poly_lr(base, epoch, n_epochs, power=0.9):
+    """nnU-Net's polynomial decay, base * (1 - epoch / n_epochs) ** power for 0 <= epoch < n_epochs, in Python floats"""
+    if not 0 <= epoch < n_epochs:
+        raise ValueError("poly_lr: epoch %r outside [0, %r)" % (epoch, n_epochs))
+    return base * (1 - epoch / n_epochs) ** power
 
-    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+
+class _GlobalClip:
+    """Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, 2-norm) for the multi-tensor optimisers, on the device: the norm spans EVERY param
+    group, is taken after the all-reduce (the optimiser is handed the averaged views) and after unscaling, and is summed in one fixed order
+    (vs_grad_sqnorm_multi + vs_grad_clip_finish: no atomics), so every data-parallel rank derives the same coefficient from the same bits.  The update
+    launches read the coefficient from the device record; nothing in the step reads it back.
+
+    ``max_norm`` is an attribute of the optimiser (None = off), not a param-group key: set it between steps and the record follows (a captured launch
+    reads it from device memory).  Switching between None and a number adds / removes launches — capture_key says so and train.GraphedStep re-captures."""
+
+    max_norm = None
+    _clip = None                         # device float[4] = {max_norm, norm, coef, 0}
+    _clip_host = None                    # the max_norm the record holds
+    _partials = None                     # device double[chunks of all groups]
+
+    @staticmethod
+    def _check_max_norm(max_norm):
+        if max_norm is not None and not float(max_norm) > 0.0:
+            raise ValueError("max_norm must be positive or None, got %r" % (max_norm,))
+        return max_norm
+
+    @property
+    def grad_norm(self):
+        """0-dim DEVICE view of the unclipped, unscaled global gradient norm of the last clipped step (reading it is the caller's synchronisation);
+        None before the first one"""
+        return None if self._clip is None else self._clip[1]
+
+    def _clip_prepare(self, n_partials, device):
+        """the record and the partial buffer, built OUTSIDE a capture (prepare() or the first eager step), the record holding the current max_norm"""
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._clip is None or self._clip.device != device:
+            if capturing:
+                raise RuntimeError("the clip record must exist before a capture: call prepare() first")
+            self._clip_host = float(self.max_norm)
+            self._clip = torch.tensor([self._clip_host, 0.0, 0.0, 0.0], dtype=torch.float32).to(device)
+        if self._partials is None or self._partials.device != device or self._partials.numel() < n_partials:
+            if capturing:
+                raise RuntimeError("the gradient set grew since prepare(): the partial-norm buffer cannot be rebuilt inside a capture")
+            self._partials = torch.zeros(n_partials, dtype=torch.float64, device=device)
+        if not capturing:
+            self._clip_sync()            # (a captured step is synchronised by sync_hyper() before its replay)
+
+    def _clip_sync(self):
+        """max_norm moved: one float in device memory (stream-ordered before whatever is launched next).  -> 1 if rewritten"""
+        if self.max_norm is None or self._clip is None or self._clip_host == float(self.max_norm):
+            return 0
+        self._clip_host = float(self.max_norm)
+        self._clip[:1].copy_(torch.tensor([self._clip_host], dtype=torch.float32), non_blocking=False)
+        return 1
+
+    def _clip_launch(self, tables, scaler):
+        """tables: (grads ptr table, sizes, block map, n_blocks) per group -> the device address of the coefficient"""
+        off = 0
+        for gp, sizes, bm, nb in tables:
+            check(lib.vs_grad_sqnorm_multi(gp.data_ptr(), sizes.data_ptr(), bm.data_ptr(), nb, self._partials.data_ptr() + 8 * off, _stream()),
+                  "grad_sqnorm_multi")
+            off += nb
+        check(lib.vs_grad_clip_finish(self._partials.data_ptr(), off, self._clip.data_ptr(), None if scaler is None else scaler.scale.data_ptr(),
+                                      _stream()), "grad_clip_finish")
+        return self._clip.data_ptr() + 8
+
+
+class SGD(_GlobalClip, torch.optim.Optimizer):
+    """torch.optim.SGD(lr, momentum, weight_decay, nesterov) — dampening 0 — as one kernel per group, with torch.nn.utils.clip_grad_norm_(max_norm)
+    folded in (_GlobalClip: two more launches per step, the update reads the coefficient on the device).  Constructed without nesterov / max_norm it
+    launches exactly the plain step (vs_sgd_momentum_*_multi)."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, max_norm=None):
+        if nesterov and not momentum > 0:
+            raise ValueError("Nesterov momentum requires a momentum")
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=bool(nesterov)))
+        self.max_norm = self._check_max_norm(max_norm)
         self._tables = {}
-        self._hyper = {}                 # group index -> [device float[3] = (lr, momentum, weight_decay), the host values it holds]
+        self._hyper = {}                 # group index -> [device float[4] = (lr, momentum, weight_decay, nesterov), the host values it holds]
 
     @torch.no_grad()
     def step_with(self, params, grads, scaler=None, device_hyper=False):
@@ -95,13 +168,18 @@ class SGD(torch.optim.Optimizer):
         return self.step(_override={id(p): g for p, g in zip(params, grads)}, scaler=scaler, _dry=True)
 
     def hyper(self):
-        return [(float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])) for g in self.param_groups]
+        return [(float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]), 1.0 if g.get("nesterov", False) else 0.0) for g in self.param_groups]
+
+    def _ext(self):
+        """does the step need vs_sgd_step_*_multi (a clip coefficient or Nesterov momentum somewhere) — or is it the plain step, launched as it always was"""
+        return self.max_norm is not None or any(g.get("nesterov", False) for g in self.param_groups)
 
     @torch.no_grad()
     def sync_hyper(self):
-        """Write each group's current (lr, momentum, weight_decay) into its device-resident triple if a scheduler moved them (stream-ordered
-        before whatever is launched next: a graph replay that follows reads the new values).  -> number of groups rewritten."""
-        moved = 0
+        """Write each group's current (lr, momentum, weight_decay, nesterov) into its device-resident record, and max_norm into the clip record, if a
+        scheduler moved them (stream-ordered before whatever is launched next: a graph replay that follows reads the new values).
+        -> number of records rewritten."""
+        moved = self._clip_sync()
         for gi, vals in enumerate(self.hyper()):
             ent = self._hyper.get(gi)
             if ent is not None and ent[1] != vals:
@@ -118,9 +196,10 @@ class SGD(torch.optim.Optimizer):
         return ent
 
     def capture_key(self, params):
-        """what a captured step_with(params, ...) launch has baked in besides the gradient addresses: the parameter set and the momentum buffers"""
+        """what a captured step_with(params, ...) launch has baked in besides the gradient addresses: the parameter set, the momentum buffers, and WHICH
+        launches the step is made of (clipping on or off, the plain or the extended update) — not the values of max_norm / nesterov, which are device-resident"""
         return tuple((id(p), p.data_ptr(), self.state[p]["momentum_buffer"].data_ptr() if "momentum_buffer" in self.state.get(p, {}) else 0)
-                     for p in params)
+                     for p in params) + ((self.max_norm is not None, self._ext()),)
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0, _override=None, scaler=None, _dry=False, _device_hyper=False):
@@ -149,6 +228,9 @@ class SGD(torch.optim.Optimizer):
             tab = self._tables.setdefault(gi, _Tables())
             (pp, gp, bp, sizes, bm), nb = tab.get([ps, grads, bufs], ps[0].device)
             todo.append((group, grads, pp, gp, bp, sizes, bm, nb, gi))
+        clip = self.max_norm is not None and bool(todo)
+        if clip:
+            self._clip_prepare(sum(t[7] for t in todo), todo[0][2].device)
         if _dry:
             for t in todo:
                 self._hyper_dev(t[8], t[2].device)
@@ -158,12 +240,24 @@ class SGD(torch.optim.Optimizer):
         if scaler is not None:
             for t in todo:                                   # every group is checked before any group is updated
                 scaler.check(t[1], t[8])
+        # the norm of ALL groups, unscaled, before any group is updated
+        coef = self._clip_launch([(t[3], t[5], t[6], t[7]) for t in todo], scaler) if clip else None
+        ext = self._ext()
         sp, fp = (scaler.scale.data_ptr(), scaler.found_inf.data_ptr()) if scaler is not None else (None, None)
         for group, grads, pp, gp, bp, sizes, bm, nb, gi in todo:
             if _device_hyper:
                 hyp = self._hyper_dev(gi, pp.device)[0]
+                if ext:
+                    check(lib.vs_sgd_step_dev_multi(pp.data_ptr(), gp.data_ptr(), bp.data_ptr(), sizes.data_ptr(), bm.data_ptr(), nb,
+                                                    hyp.data_ptr(), coef, sp, fp, _stream()), "sgd_step_dev_multi")
+                    continue
                 check(lib.vs_sgd_momentum_dev_multi(pp.data_ptr(), gp.data_ptr(), bp.data_ptr(), sizes.data_ptr(), bm.data_ptr(), nb,
                                                     hyp.data_ptr(), sp, fp, _stream()), "sgd_momentum_dev_multi")
+                continue
+            if ext:
+                check(lib.vs_sgd_step_multi(pp.data_ptr(), gp.data_ptr(), bp.data_ptr(), sizes.data_ptr(), bm.data_ptr(), nb,
+                                            float(group["lr"]) * float(grad_scale), float(group["momentum"]), float(group["weight_decay"]),
+                                            1 if group.get("nesterov", False) else 0, coef, sp, fp, _stream()), "sgd_step_multi")
                 continue
             check(lib.vs_sgd_momentum_scaled_multi(pp.data_ptr(), gp.data_ptr(), bp.data_ptr(), sizes.data_ptr(), bm.data_ptr(), nb,
                                                    float(group["lr"]) * float(grad_scale), float(group["momentum"]),
@@ -174,14 +268,15 @@ class SGD(torch.optim.Optimizer):
         return None
 
 
-class Adam(torch.optim.Optimizer):
-    """torch.optim.Adam(lr, betas, eps, weight_decay) as one kernel per group.
+class Adam(_GlobalClip, torch.optim.Optimizer):
+    """torch.optim.Adam(lr, betas, eps, weight_decay) as one kernel per group; ``max_norm``: torch.nn.utils.clip_grad_norm_ folded in (_GlobalClip).
     Deviation under a LossScaler (fp16 only; the reference has no mixed precision): when the device-side overflow flag skips an update the
     host-side ``state['step']`` has still advanced (reading the flag would sync), so after a skipped step the bias corrections run one step
     ahead of torch.cuda.amp.GradScaler's."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.max_norm = self._check_max_norm(max_norm)
         self._tables = {}
 
     @torch.no_grad()
@@ -215,12 +310,22 @@ class Adam(torch.optim.Optimizer):
             tab = self._tables.setdefault(gi, _Tables())
             (pp, gp, ap, vp, sizes, bm), nb = tab.get([ps, grads, m1, m2], ps[0].device)
             todo.append((group, grads, pp, gp, ap, vp, sizes, bm, nb, step))
+        clip = self.max_norm is not None and bool(todo)
+        if clip:
+            self._clip_prepare(sum(t[8] for t in todo), todo[0][2].device)
         if scaler is not None:
             for i, t in enumerate(todo):
                 scaler.check(t[1], i)
+        # the norm of ALL groups, unscaled, before any group is updated
+        coef = self._clip_launch([(t[3], t[6], t[7], t[8]) for t in todo], scaler) if clip else None
         sp, fp = (scaler.scale.data_ptr(), scaler.found_inf.data_ptr()) if scaler is not None else (None, None)
         for group, grads, pp, gp, ap, vp, sizes, bm, nb, step in todo:
             b1, b2 = group["betas"]
+            if clip:
+                check(lib.vs_adam_clip_multi(pp.data_ptr(), gp.data_ptr(), ap.data_ptr(), vp.data_ptr(), sizes.data_ptr(), bm.data_ptr(),
+                                             nb, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                             float(group["weight_decay"]), step, coef, sp, fp, _stream()), "adam_clip_multi")
+                continue
             check(lib.vs_adam_scaled_multi(pp.data_ptr(), gp.data_ptr(), ap.data_ptr(), vp.data_ptr(), sizes.data_ptr(), bm.data_ptr(),
                                            nb, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                            float(group["weight_decay"]), step, sp, fp, _stream()), "adam_multi")

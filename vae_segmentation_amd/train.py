@@ -302,8 +302,10 @@ class GraphedStep:
     re-pack of the trainable weight images — is part of the same graph, so a step is ONE graph launch and nothing else.  Conditions (otherwise
     the tail stays eager, `self.tail` says which): one bucket (not the two-phase overlapped form), optim.SGD (Adam's bias corrections are
     host-side per-step state), every gradient written straight into its flat slot (no stragglers to gather), the process group is RCCL or absent.
-    The learning rate, momentum and weight decay are read by the captured launch from DEVICE memory (optim.SGD.sync_hyper rewrites the three
-    floats when a scheduler moved them: main_source.py:674-677 — no re-capture); what IS baked in — the set of live parameters and the
+    The learning rate, momentum, weight decay, the Nesterov flag and max_norm are read by the captured launches from DEVICE memory (optim.SGD.sync_hyper
+    rewrites them when a scheduler moved them: main_source.py:674-677 — no re-capture).  With optim.SGD(max_norm=) the tail also holds the two launches of the
+    global gradient norm, behind the all-reduce's wait and on the averaged flat views, so every rank derives the same clip coefficient from the same bits;
+    switching clipping on or off changes the launches and re-captures.  What IS baked in — the set of live parameters and the
     addresses of parameters and momentum buffers — is compared on every step() and a change (requires_grad toggled, load_state_dict) re-captures
     (`self.recaptures`).  A LossScaler's scale, overflow flag and growth tracker are device scalars, so the scaled step captures as it is.
     Models with dropout > 0 cannot be captured (ops.next_dropout_seed raises during capture): run them eagerly.
@@ -487,7 +489,7 @@ class GraphedStep:
                 self._warm(1)                                # one eager pass with the new set: who gets a gradient now, tables rebuilt outside the capture
                 self._capture_guarded()
         if self.tail:                                        # (a re-capture may have found stragglers and left the tail eager)
-            self.optimizer.sync_hyper()                      # a scheduler moved lr / momentum / weight decay: three floats in device memory, no re-capture
+            self.optimizer.sync_hyper()                      # a scheduler moved lr / momentum / weight decay / nesterov / max_norm: floats in device memory, no re-capture
             self.graph.replay()
             return self.loss
         self.graph.replay()
