@@ -946,6 +946,31 @@ int vs_seg_loss_fwd(const float* p, const float* label, const float* class_w, do
                     long long voxels, int bot, int top, float eps, float dice_w, float ce_w, int batch_dice, float gamma, void* stream);
 int vs_seg_loss_bwd(const float* p, const float* label, const float* class_w, const double* scratch, const float* gout, float* gp, int batch, int channels,
                     long long voxels, int bot, int top, float eps, float dice_w, float ce_w, int batch_dice, float gamma, void* stream);
+/* Deep-supervision head (csrc/dshead.hip): the 1x1x1 convolution of a coarse channels-last feature map, the softmax of its logits and the
+ * loss of vs_seg_loss_* against the FULL-resolution label picked at stride s, fused: no logit or probability is stored.
+ *   feat   [batch][d][h][w][channels], dtype VS_F32 / VS_BF16 / VS_F16, channels 8 / 16 / 32 / 64;   weight fp32 [classes][channels], bias fp32 [classes],
+ *   1 <= classes <= 8;   label fp32 [batch][s d][s h][s w], s = stride in {2, 4, 8}: coarse voxel (z, y, x) takes the label at
+ *   (s z + s/2, s y + s/2, s x + s/2), read in place (scipy.ndimage.zoom(label, 1/s, order=0, mode="nearest", grid_mode=True)).
+ *   logit_k = bias_k + sum_c weight[k][c] feat_c in fp32 over the stored value of feat;  p = softmax(logit), max-subtracted, fp32;  dice_term and ce_term of
+ *   p against that label by the rule of vs_seg_loss_fwd (class_w: a HOST array of 8 floats);  terms = (dice_term, ce_term);
+ *   final = scale * ((dice_w * dice_term) + ce_w * ce_term) in fp32, scale >= 0 the level's weight.
+ * scratch: vs_ds_head_scratch_doubles() doubles, contents undefined on entry.  The forward (two launches) leaves the per-sample totals in its first
+ * batch * (3 * classes + 2) entries; the backward (two launches) reads them, recomputes p and writes
+ *   dlogit_k = p_k (gp_k - sum_j gp_j p_j), gp = gout[0] * scale * (the gradient of vs_seg_loss_bwd), formed in fp64;
+ *   dfeat_c = sum_k weight[k][c] dlogit_k (fp32, rounded once to dtype), exactly 0 in every channel of an ignored voxel;
+ *   dweight[k][c] = sum_v dlogit_k feat_c and dbias[k] = sum_v dlogit_k in fp32: per-workgroup partials behind the forward's part of scratch, added in a
+ *   fixed order.  gout is read on the device.
+ * No atomics, no memset, nothing allocated, synchronised or read back: the same bits eagerly, under graph replay and in both builds.  A null pointer,
+ * classes outside [1, 8], bot / top out of order, a negative (or NaN) weight, gamma, eps or scale, a stride outside {2, 4, 8}: VS_EINVAL; an unknown dtype:
+ * VS_EDTYPE; channels outside {8, 16, 32, 64}, an empty volume, batch > 64 or batch * d * h * w >= 2^31: VS_ESHAPE; feat / dfeat not 16-byte, fp32 buffers
+ * not 4-byte or scratch not 8-byte aligned: VS_EALIGN; all answered on the host, in that order, before any launch. */
+size_t vs_ds_head_scratch_doubles(int batch, int classes, int channels);
+int vs_ds_head_fwd(const void* feat, int dtype, const float* weight, const float* bias, const float* label, const float* class_w, double* scratch,
+                   float* terms, float* final_out, int batch, int classes, int channels, int d, int h, int w, int stride, int bot, int top, float eps,
+                   float dice_w, float ce_w, int batch_dice, float gamma, float scale, void* stream);
+int vs_ds_head_bwd(const void* feat, int dtype, const float* weight, const float* bias, const float* label, const float* class_w, double* scratch,
+                   const float* gout, void* dfeat, float* dweight, float* dbias, int batch, int classes, int channels, int d, int h, int w, int stride,
+                   int bot, int top, float eps, float dice_w, float ce_w, int batch_dice, float gamma, float scale, void* stream);
 /* nn.BCELoss() mean reduction (utils/evaluation.py:29-39), log clamped at -100 like torch */
 int vs_bce_fwd(const float* p, const float* t, float* out, double* scratch, long long count, void* stream);
 int vs_bce_bwd(const float* p, const float* t, const float* gout, float* gp, long long count, void* stream);

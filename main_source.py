@@ -3,7 +3,8 @@
 
 Methods (all native): vae_train, seg_train, joint_train (the ones the reference's scripts/source/*.bash use), sep_joint_train, embed_train,
 refine_vae (main_source.py:546-659).  seg_train and joint_train take --seg_loss dice_ce: Dice plus cross-entropy against the label, fused on the device
-(--ce_weight, --batch_dice, --focal_gamma, --class_weights; vae_segmentation_amd/driver.py add_native_flags).
+(--ce_weight, --batch_dice, --focal_gamma, --class_weights; vae_segmentation_amd/driver.py add_native_flags), and with it --deep_supervision L: the
+same loss on L coarser decoder levels through fused 1x1x1 heads.
 Optimiser: the reference's SGD(momentum 0.9) / --adam by default; --momentum, --weight_decay, --nesterov, --grad_clip N (global gradient norm, clipped on
 the device inside the captured step) and --lr_schedule poly (--poly_power) give nnU-Net's recipe.
 Data: --synthetic volumes (see vae_segmentation_amd/driver.py).  Multi-GPU: `python -m torch.distributed.run

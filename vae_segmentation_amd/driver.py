@@ -242,10 +242,25 @@ def make_optimizer(args, groups):
                      nesterov=bool(getattr(args, "nesterov", False)), max_norm=max_norm)
 
 
-def save_checkpoint(prefix, epoch_label, model, optimizer, best):
+def load_ds_heads(deep, prefix, name="best_model.ckpt"):
+    """the deep-supervision heads of '3dmodel/<prefix>/<name>' (save_checkpoint's "ds_heads_state_dict"); a checkpoint written without
+    --deep_supervision has none: the heads keep their fresh initialisation, and the run says so"""
+    path = os.path.join("3dmodel", prefix, name)
+    sd = torch.load(path, map_location="cpu").get("ds_heads_state_dict")
+    if sd is None:
+        print("%s holds no ds_heads_state_dict: the deep-supervision heads start fresh" % path)
+        return False
+    deep.load_state_dict(sd)
+    print("loaded the deep-supervision heads of %s" % path)
+    return True
+
+
+def save_checkpoint(prefix, epoch_label, model, optimizer, best, deep=None):
     path = os.path.join("3dmodel", prefix)
     os.makedirs(path, exist_ok=True)
     blob = {"epoch": epoch_label, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict()}
+    if deep is not None:
+        blob["ds_heads_state_dict"] = deep.state_dict()      # a key of its own: model_state_dict loads into a plain network
     torch.save(blob, os.path.join(path, "model_epoch%d.ckpt" % epoch_label))
     if best:
         torch.save(blob, os.path.join(path, "best_model.ckpt"))
@@ -689,13 +704,24 @@ def run(args, side="source"):
     from . import modules as _modules
     _modules.set_recompute(bool(getattr(args, "recompute", False)))
 
+    deep = None                                                             # --deep_supervision L: auxiliary heads on the decoder's coarse levels
+    if getattr(args, "deep_supervision", 0) and method in SEG_LOSS_METHODS:
+        deep = _modules.DeepSupervision(trainable, args.deep_supervision).cuda()
+        resumed = args.load_prefix if method == "seg_train" else (args.load_prefix_joint or args.load_prefix)
+        if resumed:
+            load_ds_heads(deep, resumed, args.checkpoint_name)
+
     if hasattr(model, "Seg") and hasattr(model, "Vae"):
         groups = [{"params": list(model.Seg.parameters()), "lr": args.lr_seg, "model": "Seg"},
                   {"params": list(model.Vae.parameters()), "lr": args.lr_vae, "model": "Vae"}]
     else:
         groups = [{"params": list(model.parameters()), "lr": args.lr_seg}]
+    if deep is not None:
+        groups.append({"params": list(deep.parameters()), "lr": args.lr_seg, "model": "DeepSupervision"})
     optimizer = make_optimizer(args, groups)
     params = [p for p in trainable.parameters() if p.requires_grad]
+    if deep is not None:
+        params += list(deep.parameters())
     sync = ddp.FlatGradSync(params) if world > 1 else None
     if sync is not None:
         sync.broadcast_parameters(0)
@@ -750,14 +776,15 @@ def run(args, side="source"):
             use_graph = False
 
     seg_loss = seg_loss_of(args)                                            # --seg_loss dice_ce: ops.seg_loss's arguments; None: the reference's Dice
+    deep_kw = {} if deep is None else {"deep": deep}
 
     def loss_fn():
         if method == "vae_train":
             return T.vae_train_losses(model, lab_buf, scale=0.35, noise=latent, eps=eps, n_class=nc)
         if method == "seg_train":
-            return T.seg_train_losses(model, img_buf, lab_buf, eps=eps, n_class=nc, loss=seg_loss)
+            return T.seg_train_losses(model, img_buf, lab_buf, eps=eps, n_class=nc, loss=seg_loss, **deep_kw)
         if method == "joint_train":
-            return T.joint_train_losses(model, img_buf, lab_buf, lambda_vae=lambda_vae, eps=eps, n_class=nc, loss=seg_loss)
+            return T.joint_train_losses(model, img_buf, lab_buf, lambda_vae=lambda_vae, eps=eps, n_class=nc, loss=seg_loss, **deep_kw)
         if method == "sep_joint_train":
             return T.sep_joint_train_losses(model, teacher, img_buf, lab_buf, eps=eps, n_class=nc)
         if method == "embed_train":
@@ -916,7 +943,9 @@ def run(args, side="source"):
                     aux.update(T.pseudo_batch_losses(model, pimg_buf, plab_buf, eps=eps, n_class=nc))
                 seen += bs
                 if rank == 0 and idx % args.display_freq == 0:              # logging syncs the host every display_freq steps only
-                    parts = ", ".join("%s %.4f" % (k, v.item()) for k, v in aux.items() if k != "batch")
+                    parts = ", ".join("%s %.4f" % (k, v.item()) for k, v in aux.items() if k not in ("batch", "ds_losses"))
+                    for lvl, (d_i, ce_i) in enumerate(aux.get("ds_losses", ()), 1):      # --deep_supervision: the coarse levels' terms
+                        parts += ", ds%d_dice_loss %.4f, ds%d_ce_loss %.4f" % (lvl, d_i.item(), lvl, ce_i.item())
                     if optimizer.max_norm is not None and optimizer.grad_norm is not None:
                         parts += ", grad_norm %.4f" % optimizer.grad_norm.item()      # the last step's unclipped global norm, read where the losses are read
                     print("[%3d, %3d] loss: %s" % ((epoch + 1) * args.eval_epoch, idx + 1, parts))
@@ -974,7 +1003,7 @@ def run(args, side="source"):
                         json.dump(fine_log, f)
             print("epoch %d validation result: %f, best result %f." % (epoch + 1, mean, best))
             if not args.test_only and (epoch + 1) % max(1, args.save_epoch // args.eval_epoch) == 0:
-                save_checkpoint(args.prefix, (epoch + 1) * args.eval_epoch, model, optimizer, mean > best)
+                save_checkpoint(args.prefix, (epoch + 1) * args.eval_epoch, model, optimizer, mean > best, deep=deep)
             best = max(best, mean)
         if world > 1:
             dist.barrier()
@@ -1072,7 +1101,8 @@ SEG_LOSS_METHODS = ("seg_train", "joint_train")
 def check_seg_loss_flags(parser, a, methods=SEG_LOSS_METHODS):
     """--seg_loss and the flags that shape the compound loss belong to the methods whose loss is a Dice against the label: seg_train and joint_train
     of main_source.py (main_target.py passes methods=())"""
-    given = [n for n, default in (("seg_loss", "dice"), ("ce_weight", 1.0), ("batch_dice", False), ("focal_gamma", 0.0), ("class_weights", None))
+    given = [n for n, default in (("seg_loss", "dice"), ("ce_weight", 1.0), ("batch_dice", False), ("focal_gamma", 0.0), ("class_weights", None),
+                                  ("deep_supervision", 0))
              if getattr(a, n, default) != default]
     if not given:
         return a
@@ -1159,6 +1189,10 @@ def add_native_flags(parser):
                    "-(1 - p)^G ln p; 0 = plain cross-entropy")
     g.add_argument("--class_weights", type=_class_weights, default=None, metavar="W0,W1,...", help="with --seg_loss dice_ce: one cross-entropy weight "
                    ">= 0 per class, the background first — exactly n_class numbers (torch's weighted mean); default all 1")
+    g.add_argument("--deep_supervision", type=int, default=0, choices=[0, 1, 2], metavar="L", help="with --seg_loss dice_ce: the same loss on L coarser "
+                   "levels of the decoder — 1: the half-resolution skip sum, 2: the quarter-resolution one as well — through 1x1x1 heads fused with their "
+                   "loss (ops.ds_head, DESIGN 3.21), against the label picked at stride 2 / 4, the levels weighted 2^-i and normalised (L = 2: 4/7, "
+                   "2/7, 1/7); the heads train with the network, are saved beside it and are never used for prediction.  0 (default) = off")
     g.add_argument("--momentum", type=_nonnegative, default=0.9, metavar="M", help="SGD's momentum (the reference: 0.9; nnU-Net: 0.99 with --nesterov)")
     g.add_argument("--weight_decay", type=_nonnegative, default=0.0, metavar="W", help="L2 weight decay of SGD / Adam (the reference: 0; nnU-Net: 3e-5)")
     g.add_argument("--nesterov", action="store_true", help="SGD with Nesterov momentum: the step is lr * (g + momentum * buf) instead of lr * buf")

@@ -396,8 +396,11 @@ class Segmentation(nn.Module):
         # skips (joint_model.py:380,382).  x3 / x2 also feed down3 / down2's strided conv: their skip gradient is parked for that conv's
         # backward to sum in (ops._park_gradient -> ops._PENDING["grads"]) instead of an add launch of autograd's
         u = _dropout(Act(ops.Materialize.apply(u.raw, u.stats, x3.raw, x3.stats, True), None), dropout)
+        tap4 = u.raw                        # the quarter-resolution sum up4 reads: DeepSupervision's level 2
         u = _run_block(self.up4, u)
         u = _dropout(Act(ops.Materialize.apply(u.raw, u.stats, x2.raw, x2.stats, True), None), dropout)
+        if getattr(self, "ds_taps", False):
+            data_dict["ds_feats"] = [u.raw, tap4]       # [half resolution, quarter resolution]: no launch, no new tensor
         u = _dropout(_run_block(self.up5, u), dropout)
         if u.stats is not None:
             ops.mark_defer_apply(u.raw, self.up5.conv[1].conv[6])           # up5's last conv feeds out_block only
@@ -407,6 +410,37 @@ class Segmentation(nn.Module):
         else:
             data_dict[out_key] = ops.out_block_softmax(u.raw, u.stats, self.out_block.weight, self.out_block.bias)
         return data_dict
+
+
+class DeepSupervision(nn.Module):
+    """Auxiliary heads on the decoder's intermediate resolutions (not in the reference): heads[0] = Conv3d(n_fmaps[1], n_class, 1) on the
+    half-resolution skip sum up5 reads (level 1, label stride 2), heads[1] = Conv3d(n_fmaps[2], n_class, 1) on the quarter-resolution sum up4 reads
+    (level 2, stride 4).  The module owns the heads and is NOT a submodule of `seg` — Segmentation.state_dict() keeps its keys and validation never sees
+    them; it only sets the plain attribute seg.ds_taps, with which Segmentation.forward also hands the two (already materialised) tensors out in
+    data_dict["ds_feats"].  Each tap then has two consumers, up4 / up5 and its head: autograd adds their two gradients.
+    forward(batch, target, scales=None, **loss_args) -> [(final_i, (dice_term_i, ce_term_i)) per level]: ops.ds_head on each tap against the
+    full-resolution ops.LabelTarget; scales: the levels' weights (default 1 each); loss_args: ops.ds_head's."""
+
+    def __init__(self, seg, levels=2):
+        super().__init__()
+        levels = int(levels)
+        if levels not in (1, 2):
+            raise ValueError("DeepSupervision: 1 or 2 levels (the half- and quarter-resolution skip sums), got %r" % (levels,))
+        chans = [seg.up5.conv[0].in_channels, seg.up4.conv[0].in_channels][:levels]
+        for c in chans:
+            if c not in ops.DS_CHANNELS:
+                raise NotImplementedError("DeepSupervision: the fused head reads %s feature channels, got %d" % ("/".join(map(str, ops.DS_CHANNELS)), c))
+        self.heads = nn.ModuleList([nn.Conv3d(c, seg.n_class, 1) for c in chans])
+        seg.ds_taps = True                  # a plain attribute, no parameter or buffer: seg.state_dict() is unchanged
+
+    def forward(self, batch, target, scales=None, **loss_args):
+        feats = batch.get("ds_feats")
+        if feats is None:
+            raise RuntimeError("DeepSupervision: the batch holds no 'ds_feats' — was it produced by the Segmentation this module was built on?")
+        scales = [1.0] * len(self.heads) if scales is None else list(scales)
+        if len(scales) != len(self.heads):
+            raise ValueError("DeepSupervision: %d scales for %d levels" % (len(scales), len(self.heads)))
+        return [ops.ds_head(feats[i], head.weight, head.bias, target, 2 << i, scale=scales[i], **loss_args) for i, head in enumerate(self.heads)]
 
 
 class Joint(nn.Module):

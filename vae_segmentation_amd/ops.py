@@ -2435,6 +2435,80 @@ def seg_loss(p, target, dice_weight=1.0, ce_weight=1.0, batch_dice=False, class_
     return final, tuple(terms.unbind(0))
 
 
+DS_STRIDES = (2, 4, 8)
+DS_CHANNELS = (8, 16, 32, 64)
+
+
+class DSHead(torch.autograd.Function):
+    """A deep-supervision head, fused (csrc/dshead.hip): final = scale * SegLoss(softmax(conv1x1x1(feat)), label picked at `stride`) for a
+    channels-last feature map feat (N, d, h, w, C) in its storage dtype, the (K, C, 1, 1, 1) weight and (K,) bias of an nn.Conv3d(C, K, 1) and the
+    FULL-resolution label (N, 1, s d, s h, s w) — TWO forward and TWO backward launches, no logit or probability stored; the backward recomputes the
+    probabilities.  -> (final, terms[2] = (dice_term, ce_term)); terms are not differentiable.  Gradients: feat's in its storage dtype, the weight's and
+    the bias's written where _grad_slot says (the data-parallel flat bucket when there is one)."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, bias, label, stride, scale, bot, top, eps, dice_weight, ce_weight, batch_dice, class_weights, gamma):
+        _require_cuda(feat, weight, bias, label)
+        if feat.dim() != 5 or feat.dtype not in _DT_VS:
+            raise TypeError("ds_head: feat is a channels-last (N, d, h, w, C) tensor in float32, bfloat16 or float16")
+        feat, label = _contig(feat), _contig(label.float())
+        w32, b32 = _contig(weight.float()), _contig(bias.float())
+        n, d, h, w, c = feat.shape
+        k = w32.shape[0]
+        if w32.numel() != k * c or b32.numel() != k:
+            raise ValueError("ds_head: weight %s / bias %s do not fit %d feature channels" % (tuple(weight.shape), tuple(bias.shape), c))
+        s = int(stride)
+        if label.numel() != n * d * h * w * s ** 3:
+            raise ValueError("label target: expected %d x %s labels at stride %d, got %s" % (n, (s * d, s * h, s * w), s, tuple(label.shape)))
+        scratch = torch.empty(max(1, lib.vs_ds_head_scratch_doubles(n, k, c)), dtype=torch.float64, device=feat.device)
+        terms = torch.empty(2, dtype=torch.float32, device=feat.device)
+        final = torch.empty((), dtype=torch.float32, device=feat.device)
+        cfg = (n, k, c, d, h, w, s, int(bot), int(top), float(eps), float(dice_weight), float(ce_weight), 1 if batch_dice else 0, float(gamma), float(scale))
+        wp = (_ctypes.c_float * 8)(*([float(x) for x in class_weights] + [0.0] * 8)[:8])
+        check(lib.vs_ds_head_fwd(feat.data_ptr(), vs_dtype(feat), w32.data_ptr(), b32.data_ptr(), label.data_ptr(), _ctypes.addressof(wp), scratch.data_ptr(),
+                                 terms.data_ptr(), final.data_ptr(), *cfg, _stream()), "ds_head_fwd")
+        ctx.save_for_backward(feat, weight, bias, label, scratch)
+        ctx.cfg, ctx.class_weights = cfg, [float(x) for x in class_weights]
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)      # no zero-fill launch for the terms' gradient
+        return final, terms
+
+    @staticmethod
+    def backward(ctx, g, _gterms):
+        feat, weight, bias, label, scratch = ctx.saved_tensors
+        if g is None:
+            return (None,) * 14
+        g = _contig(g.float())
+        w32, b32 = _contig(weight.float()), _contig(bias.float())
+        gf = torch.empty_like(feat)
+        # the launch writes all three; a gradient nobody asked for is dropped
+        gw = _grad_slot(weight, weight.shape) if ctx.needs_input_grad[1] else torch.empty(weight.shape, dtype=torch.float32, device=feat.device)
+        gb = _grad_slot(bias, bias.shape) if ctx.needs_input_grad[2] else torch.empty(bias.shape, dtype=torch.float32, device=feat.device)
+        wp = (_ctypes.c_float * 8)(*(ctx.class_weights + [0.0] * 8)[:8])
+        check(lib.vs_ds_head_bwd(feat.data_ptr(), vs_dtype(feat), w32.data_ptr(), b32.data_ptr(), label.data_ptr(), _ctypes.addressof(wp), scratch.data_ptr(),
+                                 g.data_ptr(), gf.data_ptr(), gw.data_ptr(), gb.data_ptr(), *ctx.cfg, _stream()), "ds_head_bwd")
+        return (gf if ctx.needs_input_grad[0] else None, gw if ctx.needs_input_grad[1] else None, gb if ctx.needs_input_grad[2] else None) + (None,) * 11
+
+
+def ds_head(feat, weight, bias, target, stride, scale=1.0, dice_weight=1.0, ce_weight=1.0, batch_dice=False, class_weights=None, gamma=0.0, botindex=0,
+            topindex=2, eps=1e-6):
+    """scale * (dice_weight * (1 - Dice) + ce_weight * CE) of softmax(conv1x1x1(feat; weight, bias)) against the label of an ops.LabelTarget picked at
+    `stride` (2, 4 or 8: coarse voxel (z, y, x) takes the label at (s z + s/2, s y + s/2, s x + s/2)) -> (final, (dice_term, ce_term)); feat is a
+    channels-last (N, d, h, w, C) tensor, C in 8 / 16 / 32 / 64, in any storage dtype; the loss arguments are seg_loss's (DSHead)."""
+    if not isinstance(target, LabelTarget):
+        raise TypeError("ds_head takes its target as an ops.LabelTarget (the full-resolution label volume)")
+    classes = weight.shape[0]
+    bot, top = (botindex, min(topindex, classes)) if classes > 1 else (0, 1)
+    if class_weights is None:
+        class_weights = [1.0] * classes
+    class_weights = [float(w) for w in class_weights]
+    if len(class_weights) != classes:
+        raise ValueError("ds_head: %d class weights for %d classes" % (len(class_weights), classes))
+    final, terms = DSHead.apply(feat, weight, bias, target.label, int(stride), scale, bot, top, eps, dice_weight, ce_weight, bool(batch_dice), class_weights,
+                                gamma)
+    return final, tuple(terms.unbind(0))
+
+
 class BCE(torch.autograd.Function):
     """nn.BCELoss() (mean) — utils/evaluation.py:29-39."""
 

@@ -41,8 +41,38 @@ def _seg_loss_args(loss):
     return kw
 
 
-def joint_train_losses(joint, img, label, lambda_vae=0.1, eps=EPS_MAIN_SOURCE, n_class=2, loss=None):
+def ds_weights(levels):
+    """the weights of deep supervision: 2^-i for the full resolution (i = 0) and the `levels` coarser ones, normalised to sum 1 —
+    levels = 2: 4/7, 2/7, 1/7"""
+    raw = [2.0 ** -i for i in range(int(levels) + 1)]
+    total = sum(raw)
+    return [r / total for r in raw]
+
+
+def _deep_seg_loss(pred, batch, label, deep, kw, n_class, eps):
+    """the compound loss with deep supervision: w0 * seg_loss(pred) + sum_i ds_head_i(scale = w_i), added in that order
+    -> (final, (dice_term, ce_term) of the full resolution, [(dice_term_i, ce_term_i) per level])"""
+    w = ds_weights(len(deep.heads))
+    target = ops.LabelTarget(label)
+    kw0 = dict(kw, dice_weight=kw.get("dice_weight", 1.0) * w[0], ce_weight=kw.get("ce_weight", 1.0) * w[0])
+    final, terms = ops.seg_loss(pred, target, botindex=1, topindex=n_class, eps=eps, **kw0)
+    levels = deep(batch, target, scales=w[1:], botindex=1, topindex=n_class, eps=eps, **kw)
+    for part, _ in levels:
+        final = final + part
+    return final, terms, [t for _, t in levels]
+
+
+def joint_train_losses(joint, img, label, lambda_vae=0.1, eps=EPS_MAIN_SOURCE, n_class=2, loss=None, deep=None):
+    """deep: a modules.DeepSupervision built on joint.Seg (needs `loss`): see seg_train_losses"""
+    if deep is not None and loss is None:
+        raise TypeError("deep supervision applies the compound loss to the coarse levels: pass loss= as well")
     batch = {"img": img}
+    if loss is not None and deep is not None:
+        batch["label"] = label
+        batch = joint(batch, "img", "pred", "recon")
+        vae_part, (recon_loss,) = ops.dice_loss_sum(batch["pred"], [(batch["recon"], lambda_vae)], botindex=1, topindex=n_class, eps=eps)
+        seg_part, (dsc_loss, ce_loss), ds_losses = _deep_seg_loss(batch["pred"], batch, label, deep, _seg_loss_args(loss), n_class, eps)
+        return vae_part + seg_part, {"recon_loss": recon_loss, "dice_loss": dsc_loss, "ce_loss": ce_loss, "ds_losses": ds_losses, "batch": batch}
     if loss is not None:
         # the compound loss (ops.seg_loss, DESIGN 3.20) against the label volume in place of the ground-truth Dice term; the VAE term stays a Dice
         batch["label"] = label
@@ -58,8 +88,17 @@ def joint_train_losses(joint, img, label, lambda_vae=0.1, eps=EPS_MAIN_SOURCE, n
     return final, {"recon_loss": recon_loss, "dice_loss": dsc_loss, "batch": batch}
 
 
-def seg_train_losses(seg, img, label, eps=EPS_MAIN_SOURCE, n_class=2, loss=None):
+def seg_train_losses(seg, img, label, eps=EPS_MAIN_SOURCE, n_class=2, loss=None, deep=None):
+    """deep: a modules.DeepSupervision built on `seg` (needs `loss`): the full-resolution compound loss is weighted ds_weights()[0], head i of the
+    coarser levels ds_weights()[i] (ops.ds_head's scale), final is their sum and aux["ds_losses"] holds the levels' (dice_term, ce_term)"""
+    if deep is not None and loss is None:
+        raise TypeError("deep supervision applies the compound loss to the coarse levels: pass loss= as well")
     batch = {"img": img}
+    if loss is not None and deep is not None:
+        batch["label"] = label
+        batch = seg(batch, "img", "pred")
+        final, (dsc_loss, ce_loss), ds_losses = _deep_seg_loss(batch["pred"], batch, label, deep, _seg_loss_args(loss), n_class, eps)
+        return final, {"dice_loss": dsc_loss, "ce_loss": ce_loss, "ds_losses": ds_losses, "batch": batch}
     if loss is not None:
         batch["label"] = label
         batch = seg(batch, "img", "pred")
