@@ -1,4 +1,4 @@
-"""The loss and label operations of csrc/misc.hip restated in plain fp64 torch / numpy: the formulas and nothing else.  No project code is used
+"""The loss and label operations of csrc/loss.hip and csrc/softmax.hip restated in plain fp64 torch / numpy: the formulas and nothing else.  No project code is used
 here; tests/test_host_loss.py pins these functions against the oracle and the recorded reference values before a kernel is compared with them.
 Gradients are fp64 autograd on these functions (inputs: fp64 leaves with requires_grad), except BCE's, whose clamped form nn.BCELoss defines."""
 import numpy as np

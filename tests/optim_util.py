@@ -1,4 +1,4 @@
-"""numpy oracle of the clipped / Nesterov SGD step (vae_segmentation_amd/optim.py, csrc/misc.hip): the global gradient norm in fp64, the clip
+"""numpy oracle of the clipped / Nesterov SGD step (vae_segmentation_amd/optim.py, csrc/optim.hip): the global gradient norm in fp64, the clip
 coefficient by torch.nn.utils.clip_grad_norm_'s rule in fp32, and the update with every fp32 operation rounded on its own."""
 import numpy as np
 

@@ -1,4 +1,4 @@
-"""The loss and label kernels of csrc/misc.hip against their fp64 restatement (tests/loss_util.py, pinned on the host by tests/test_host_loss.py), in
+"""The loss and label kernels of csrc/loss.hip and csrc/softmax.hip against their fp64 restatement (tests/loss_util.py, pinned on the host by tests/test_host_loss.py), in
 both builds, at the sizes where the kernels change path.  Inputs are planar fp32 tensors (B, C, 1, 4, V / 4), so the voxel count V of a plane is set directly.
 
 Branch reached by each DiceLossSum plane size (nblk = ceil(V / 2048) partial blocks, at most DICE_MULTI_BLOCKS = 256; the finish kernel gives 16 threads

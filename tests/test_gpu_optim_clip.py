@@ -1,4 +1,4 @@
-"""GPU: global gradient-norm clipping, Nesterov momentum and their captured form (vae_segmentation_amd/optim.py, csrc/misc.hip
+"""GPU: global gradient-norm clipping, Nesterov momentum and their captured form (vae_segmentation_amd/optim.py, csrc/optim.hip
 vs_grad_sqnorm_multi / vs_grad_clip_finish / vs_sgd_step_*_multi / vs_adam_clip_multi) against the numpy oracle (tests/optim_util.py) and
 torch.nn.utils.clip_grad_norm_ + torch.optim on the CPU.
 

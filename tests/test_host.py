@@ -469,7 +469,8 @@ def test_isa_phase_counts_finds_the_tile_loop_of_k3t():
 
 def test_isa_diff_verdicts_on_inline_assembly():
     """tools/isa_diff.py's comparison (no compile): equal text is `identical`, scalar moves that traded places are `equivalent` (the same count of every
-    mnemonic, the same descriptor), one extra instruction is DIFFERENT, and a symbol that only one side has is reported as such."""
+    mnemonic, the same descriptor), one extra instruction is DIFFERENT, and a symbol that only one side has is reported as such.  A file split into
+    several (--moved) is compared against the union of their symbols; a symbol two of them carry counts once if its text is equal and is DIFFERENT if not."""
     sys.path.insert(0, os.path.join(REPO, "tools"))
     try:
         import isa_diff
@@ -490,6 +491,17 @@ def test_isa_diff_verdicts_on_inline_assembly():
     assert isa_diff.compare(asm(base), asm(base).replace("next_free_vgpr 4", "next_free_vgpr 5")) == {"kern": "DIFFERENT"}
     other = "\t.type\tlone,@function\nlone:\n\ts_endpgm\n\t.size\tlone, 4\n"
     assert isa_diff.compare(asm(base), asm(base, extra=other)) == {"kern": "identical", "lone": "only in new"}
+    # --moved: one old file against the union of the files its code went to.  `shared` stands for a static kernel of a header both new files include
+    shared = "\t.type\tshared,@function\nshared:\n\ts_nop 0\n\ts_endpgm\n\t.size\tshared, 8\n"
+    old = asm(base, extra=other + shared)
+    new_a, new_b = asm(swapped, extra=shared), shared + other + "\t.ident\t\"b\"\n"
+    assert isa_diff.compare_moved(old, [new_a, new_b]) == {"kern": "equivalent", "lone": "identical", "shared": "identical"}
+    assert isa_diff.compare_moved(old, [new_b, new_a]) == isa_diff.compare_moved(old, [new_a, new_b])
+    assert isa_diff.compare_moved(old, [new_a]) == {"kern": "equivalent", "lone": "only in old", "shared": "identical"}
+    assert isa_diff.compare_moved(asm(base), [new_a, new_b]) == {"kern": "equivalent", "shared": "only in new", "lone": "only in new"}
+    unequal = new_b.replace("s_nop 0", "s_nop 1")
+    assert isa_diff.compare_moved(old, [new_a, unequal]) == {"kern": "equivalent", "lone": "identical", "shared": "DIFFERENT"}
+    assert isa_diff.compare_moved(asm(base), [new_a, unequal])["shared"] == "DIFFERENT"      # whatever the old file held
 
 
 def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path):

@@ -84,6 +84,19 @@ def test_optimisers_take_torch_s_keys_and_reject_what_torch_rejects():
     assert optim.Adam(ps, max_norm=3.0).max_norm == 3.0
 
 
+def test_chunk_size_has_one_source_and_the_block_map_follows_it():
+    """VS_MT_CHUNK of include/vaeseg.h is what the library reports and what optim._Tables cuts tensors by: one entry {tensor, first element} per chunk,
+    a tensor of exactly one chunk has one entry and one element more starts a second"""
+    import re
+    from vae_segmentation_amd import _lib, optim
+    header = int(re.search(r"^#define\s+VS_MT_CHUNK\s+(\d+)\s*$", open(_lib.HEADER).read(), re.M).group(1))
+    assert _lib.lib.vs_mt_chunk() == 4096 == header == optim._CHUNK
+    a, b, c = torch.zeros(1), torch.zeros(4096), torch.zeros(4097)
+    (ptrs, sizes, bm), nb = optim._Tables().get([[a, b, c]], "cpu")
+    assert nb == 4 and bm.dtype == torch.int32 and bm.view(-1, 2).tolist() == [[0, 0], [1, 0], [2, 0], [2, 4096]]
+    assert sizes.tolist() == [1, 4096, 4097] and ptrs.tolist() == [t.data_ptr() for t in (a, b, c)]
+
+
 def test_entry_points_parse_the_optimiser_flags():
     import main_source
     import main_target

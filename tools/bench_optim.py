@@ -1,4 +1,4 @@
-"""The clipped / Nesterov optimiser step (optim.SGD(nesterov=, max_norm=), csrc/misc.hip) against the plain one and against what one could write without
+"""The clipped / Nesterov optimiser step (optim.SGD(nesterov=, max_norm=), csrc/optim.hip) against the plain one and against what one could write without
 it -> profiles/optim_clip_bench.json.
 
 ONE process on ONE machine, device events around BATCH calls, medians of SAMPLES after WARMUP:

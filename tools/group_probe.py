@@ -1,4 +1,4 @@
-"""GPU-box aid: price of the group protocol an in-epilogue InstanceNorm-backward apply would need (csrc/misc.hip, grid_barrier_probe_kernel modes 2 / 3):
+"""GPU-box aid: price of the group protocol an in-epilogue InstanceNorm-backward apply would need (tools/probe/probe.hip, grid_barrier_probe_kernel modes 2 / 3):
 partial sums by fp64 atomics (done today), then group counter + poll + atomic loads of the totals.  usage: python tools/group_probe.py [iters]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -490,6 +490,9 @@ static inline hipError_t vs_zero_async(void* p, size_t bytes, hipStream_t stream
         if (e__ != hipSuccess) return (int)e__;            \
     } while (0)
 
+// grid of a 256-thread grid-stride launch over n items (softmax.hip, latent.hip, loss.hip)
+#define GRID1D(n) dim3((unsigned)((((n) + 255) / 256) < 65536LL * 16 ? (((n) + 255) / 256) : 65536LL * 16))
+
 // run f with a null pointer of the storage type as tag: f((float*)0) / f((unsigned short*)0) [bf16 bits] / f((vs_half*)0) [fp16]
 template <typename F>
 static inline void dispatch_t(int dtype, F&& f) {

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         }
     };
-    auto write_x_sm = [&](const TileCoord& c) {              // softmax2_bwd_kernel (misc.hip) on the staged voxels
+    auto write_x_sm = [&](const TileCoord& c) {              // softmax2_bwd_kernel (softmax.hip) on the staged voxels
         const int base = (((c.n * p.D + c.z0 - 1) * p.H + c.y0 - 1) * p.W + c.x0 - 1) * 16;
 #pragma unroll
         for (int b = 0; b < NIT; ++b) {

@@ -1,7 +1,7 @@
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw, "Parallel random numbers: as easy as 1, 2, 3", SC'11): four 32-bit counter words and two key words ->
 // four output words, ten rounds of two 32 x 32 -> 64 bit products.  A pure function of its arguments: no state, the same bits in every launch geometry.
 // Users: elastic.hip (counter word 2 = the field's axis, 0..2; words w0, w1), augment.hip (counter word 2 = 0x100 + channel; all four words) and
-// misc.hip's latent stream (counter (pair, draw low, 0x200, draw high); all four words).
+// latent.hip's latent stream (counter (pair, draw low, 0x200, draw high); all four words).
 #pragma once
 #include <math.h>
 
@@ -23,7 +23,7 @@ __device__ __forceinline__ double vs_philox_u53(unsigned int a, unsigned int b) 
     return (double)(a >> 5) * 67108864.0 + (double)(b >> 6);
 }
 // Box-Muller on four output words: radius r = sqrt(-2 ln u1) with u1 = (u53 + 0.5) / 2^53 in (0, 1), angle a = 2 pi u2 with u2 = u53 / 2^53; the pair of
-// normals is (r cos a, r sin a).  Contraction off: augment.hip and misc.hip's latent stream are pinned bit for bit to this order of roundings.
+// normals is (r cos a, r sin a).  Contraction off: augment.hip and latent.hip's latent stream are pinned bit for bit to this order of roundings.
 // (elastic.hip's uniform spells its u53 out: it compiles under the default contraction, the same exact value through one fused multiply-add.)
 __device__ __forceinline__ void vs_philox_box_muller(unsigned int w0, unsigned int w1, unsigned int w2, unsigned int w3, double& r, double& a) {
 #pragma clang fp contract(off)

@@ -3,7 +3,7 @@
 //
 //   valid voxel: label >= 0 && label < C in fp32 (NaN fails both), class l = (int)label.  Every other voxel — the -1 of the quad padding, an ignore value
 //   such as 255, NaN — is IGNORED: it adds to no sum, S included, and gets gradient 0 in every channel.  This deliberately differs from
-//   vs_dice_loss_multi_labels_* (misc.hip), where a voxel whose label matches no class still counts in S.
+//   vs_dice_loss_multi_labels_* (loss.hip), where a voxel whose label matches no class still counts in S.
 //
 // Forward = two launches.  seg_partial_kernel is voxel-major: a thread owns quads of voxels, loads the label quad and the C probability quads (16-byte loads,
 // coalesced per plane), classifies each voxel once and updates 2C + 2 fp64 sums (S, I, sum w f, sum w) and C integer counts (T) — one read of p and one of the

@@ -2,12 +2,14 @@
 per-tensor torch.optim loops (main_source.py:279-294, main_target.py:347-352), and the EMA teacher update
 (main_target.py:512-516).  Semantics and state keys follow torch.optim.SGD / torch.optim.Adam so optimizer
 state_dicts stay interchangeable with the reference's checkpoints (main_source.py:827-843)."""
+import collections
+
 import torch
 
 from . import ops
-from ._lib import check, lib
+from ._lib import _stream, check, lib
 
-_CHUNK = 4096        # must equal MT_CHUNK in csrc/misc.hip
+_CHUNK = int(lib.vs_mt_chunk())      # VS_MT_CHUNK: the elements of one tensor a workgroup of the *_multi kernels owns (csrc/optim.hip)
 
 
 class _Tables:
@@ -33,10 +35,6 @@ class _Tables:
             self.n_blocks = bm.numel() // 2
             self.key = key
         return self.dev, self.n_blocks
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class LossScaler:
@@ -79,8 +77,21 @@ def poly_lr(base, epoch, n_epochs, power=0.9):
     return base * (1 - epoch / n_epochs) ** power
 
 
-class _GlobalClip:
-    """Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, 2-norm) for the multi-tensor optimisers, on the device: the norm spans EVERY param
+class _Group(collections.namedtuple("_Group", "group index params grads params_ptr grads_ptr state_ptrs sizes block_map n_blocks device")):
+    """One param group with work in this step: the group and its index, the parameters that have a gradient and those gradients, and the device tables
+    of _Tables.get([params, grads, *state buffers]) by name."""
+    __slots__ = ()
+
+    @property
+    def tables(self):
+        """the leading arguments of every step entry point"""
+        return tuple(t.data_ptr() for t in (self.params_ptr, self.grads_ptr) + self.state_ptrs + (self.sizes, self.block_map)) + (self.n_blocks,)
+
+
+class _MultiTensor:
+    """What SGD and Adam share: the walk over the param groups (_groups) and what happens before any group is updated (_check_and_norm).
+
+    Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, 2-norm) for the multi-tensor optimisers, on the device: the norm spans EVERY param
     group, is taken after the all-reduce (the optimiser is handed the averaged views) and after unscaling, and is summed in one fixed order
     (vs_grad_sqnorm_multi + vs_grad_clip_finish: no atomics), so every data-parallel rank derives the same coefficient from the same bits.  The update
     launches read the coefficient from the device record; nothing in the step reads it back.
@@ -128,21 +139,50 @@ class _GlobalClip:
         self._clip[:1].copy_(torch.tensor([self._clip_host], dtype=torch.float32), non_blocking=False)
         return 1
 
-    def _clip_launch(self, tables, scaler):
-        """tables: (grads ptr table, sizes, block map, n_blocks) per group -> the device address of the coefficient"""
+    def _clip_launch(self, todo, scaler):
+        """-> the device address of the coefficient"""
         off = 0
-        for gp, sizes, bm, nb in tables:
-            check(lib.vs_grad_sqnorm_multi(gp.data_ptr(), sizes.data_ptr(), bm.data_ptr(), nb, self._partials.data_ptr() + 8 * off, _stream()),
-                  "grad_sqnorm_multi")
-            off += nb
+        for g in todo:
+            check(lib.vs_grad_sqnorm_multi(g.grads_ptr.data_ptr(), g.sizes.data_ptr(), g.block_map.data_ptr(), g.n_blocks,
+                                           self._partials.data_ptr() + 8 * off, _stream()), "grad_sqnorm_multi")
+            off += g.n_blocks
         check(lib.vs_grad_clip_finish(self._partials.data_ptr(), off, self._clip.data_ptr(), None if scaler is None else scaler.scale.data_ptr(),
                                       _stream()), "grad_clip_finish")
         return self._clip.data_ptr() + 8
 
+    def _groups(self, override, state_bufs):
+        """The param groups with work, as _Group records: the parameters named by override ({id(p): gradient}) or, without one, those with a p.grad
+        (made contiguous); state_bufs(params) creates and returns the optimiser's state buffers, a tuple of lists; the device tables come from the
+        group's _Tables.  With clipping on, the clip record and the partial buffer are made ready for all of them."""
+        todo = []
+        for gi, group in enumerate(self.param_groups):
+            if override is not None:
+                ps = [p for p in group["params"] if id(p) in override]
+                grads = [override[id(p)] for p in ps]
+            else:
+                ps = [p for p in group["params"] if p.grad is not None]
+                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
+            if not ps:
+                continue
+            (pp, gp, *sp, sizes, bm), nb = self._tables.setdefault(gi, _Tables()).get([ps, grads, *state_bufs(ps)], ps[0].device)
+            todo.append(_Group(group, gi, ps, grads, pp, gp, tuple(sp), sizes, bm, nb, ps[0].device))
+        if self.max_norm is not None and todo:
+            self._clip_prepare(sum(g.n_blocks for g in todo), todo[0].device)
+        return todo
 
-class SGD(_GlobalClip, torch.optim.Optimizer):
+    def _check_and_norm(self, todo, scaler):
+        """Every group is checked, and the norm of ALL groups taken (unscaled), before any group is updated.
+        -> the device addresses (clip coefficient, loss scale, overflow flag), None where there is none"""
+        if scaler is not None:
+            for g in todo:
+                scaler.check(g.grads, g.index)
+        coef = self._clip_launch(todo, scaler) if self.max_norm is not None and todo else None
+        return (coef,) + ((scaler.scale.data_ptr(), scaler.found_inf.data_ptr()) if scaler is not None else (None, None))
+
+
+class SGD(_MultiTensor, torch.optim.Optimizer):
     """torch.optim.SGD(lr, momentum, weight_decay, nesterov) — dampening 0 — as one kernel per group, with torch.nn.utils.clip_grad_norm_(max_norm)
-    folded in (_GlobalClip: two more launches per step, the update reads the coefficient on the device).  Constructed without nesterov / max_norm it
+    folded in (_MultiTensor: two more launches per step, the update reads the coefficient on the device).  Constructed without nesterov / max_norm it
     launches exactly the plain step (vs_sgd_momentum_*_multi)."""
 
     def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, max_norm=None):
@@ -201,75 +241,52 @@ class SGD(_GlobalClip, torch.optim.Optimizer):
         return tuple((id(p), p.data_ptr(), self.state[p]["momentum_buffer"].data_ptr() if "momentum_buffer" in self.state.get(p, {}) else 0)
                      for p in params) + ((self.max_norm is not None, self._ext()),)
 
+    def _momentum_buffers(self, ps):
+        for p in ps:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("vae_segmentation_amd.optim.SGD needs contiguous fp32 CUDA parameters")
+        bufs = []
+        for p in ps:
+            st = self.state[p]
+            if "momentum_buffer" not in st or st["momentum_buffer"] is None:
+                st["momentum_buffer"] = torch.zeros_like(p)      # buf = 0*m + g on the first step = torch's clone(g)
+            bufs.append(st["momentum_buffer"])
+        return (bufs,)
+
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0, _override=None, scaler=None, _dry=False, _device_hyper=False):
         ops.flush_wgrads()
-        todo = []
-        for gi, group in enumerate(self.param_groups):
-            if _override is not None:
-                ps = [p for p in group["params"] if id(p) in _override]
-            else:
-                ps = [p for p in group["params"] if p.grad is not None]
-            if not ps:
-                continue
-            for p in ps:
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("vae_segmentation_amd.optim.SGD needs contiguous fp32 CUDA parameters")
-            if _override is not None:
-                grads = [_override[id(p)] for p in ps]
-            else:
-                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
-            bufs = []
-            for p in ps:
-                st = self.state[p]
-                if "momentum_buffer" not in st or st["momentum_buffer"] is None:
-                    st["momentum_buffer"] = torch.zeros_like(p)      # buf = 0*m + g on the first step = torch's clone(g)
-                bufs.append(st["momentum_buffer"])
-            tab = self._tables.setdefault(gi, _Tables())
-            (pp, gp, bp, sizes, bm), nb = tab.get([ps, grads, bufs], ps[0].device)
-            todo.append((group, grads, pp, gp, bp, sizes, bm, nb, gi))
-        clip = self.max_norm is not None and bool(todo)
-        if clip:
-            self._clip_prepare(sum(t[7] for t in todo), todo[0][2].device)
+        todo = self._groups(_override, self._momentum_buffers)
         if _dry:
-            for t in todo:
-                self._hyper_dev(t[8], t[2].device)
+            for g in todo:
+                self._hyper_dev(g.index, g.device)
                 if scaler is not None:
-                    scaler.prepare(t[1], t[8])
+                    scaler.prepare(g.grads, g.index)
             return None
-        if scaler is not None:
-            for t in todo:                                   # every group is checked before any group is updated
-                scaler.check(t[1], t[8])
-        # the norm of ALL groups, unscaled, before any group is updated
-        coef = self._clip_launch([(t[3], t[5], t[6], t[7]) for t in todo], scaler) if clip else None
+        coef, sp, fp = self._check_and_norm(todo, scaler)
         ext = self._ext()
-        sp, fp = (scaler.scale.data_ptr(), scaler.found_inf.data_ptr()) if scaler is not None else (None, None)
-        for group, grads, pp, gp, bp, sizes, bm, nb, gi in todo:
+        for g in todo:
+            group = g.group
             if _device_hyper:
-                hyp = self._hyper_dev(gi, pp.device)[0]
+                hyp = self._hyper_dev(g.index, g.device)[0]
                 if ext:
-                    check(lib.vs_sgd_step_dev_multi(pp.data_ptr(), gp.data_ptr(), bp.data_ptr(), sizes.data_ptr(), bm.data_ptr(), nb,
-                                                    hyp.data_ptr(), coef, sp, fp, _stream()), "sgd_step_dev_multi")
-                    continue
-                check(lib.vs_sgd_momentum_dev_multi(pp.data_ptr(), gp.data_ptr(), bp.data_ptr(), sizes.data_ptr(), bm.data_ptr(), nb,
-                                                    hyp.data_ptr(), sp, fp, _stream()), "sgd_momentum_dev_multi")
-                continue
-            if ext:
-                check(lib.vs_sgd_step_multi(pp.data_ptr(), gp.data_ptr(), bp.data_ptr(), sizes.data_ptr(), bm.data_ptr(), nb,
-                                            float(group["lr"]) * float(grad_scale), float(group["momentum"]), float(group["weight_decay"]),
+                    check(lib.vs_sgd_step_dev_multi(*g.tables, hyp.data_ptr(), coef, sp, fp, _stream()), "sgd_step_dev_multi")
+                else:
+                    check(lib.vs_sgd_momentum_dev_multi(*g.tables, hyp.data_ptr(), sp, fp, _stream()), "sgd_momentum_dev_multi")
+            elif ext:
+                check(lib.vs_sgd_step_multi(*g.tables, float(group["lr"]) * float(grad_scale), float(group["momentum"]), float(group["weight_decay"]),
                                             1 if group.get("nesterov", False) else 0, coef, sp, fp, _stream()), "sgd_step_multi")
-                continue
-            check(lib.vs_sgd_momentum_scaled_multi(pp.data_ptr(), gp.data_ptr(), bp.data_ptr(), sizes.data_ptr(), bm.data_ptr(), nb,
-                                                   float(group["lr"]) * float(grad_scale), float(group["momentum"]),
-                                                   float(group["weight_decay"]), 0, sp, fp, _stream()), "sgd_momentum_multi")
+            else:
+                check(lib.vs_sgd_momentum_scaled_multi(*g.tables, float(group["lr"]) * float(grad_scale), float(group["momentum"]),
+                                                       float(group["weight_decay"]), 0, sp, fp, _stream()), "sgd_momentum_multi")
         if scaler is not None:
             scaler.update()
         ops.weights_changed()
         return None
 
 
-class Adam(_GlobalClip, torch.optim.Optimizer):
-    """torch.optim.Adam(lr, betas, eps, weight_decay) as one kernel per group; ``max_norm``: torch.nn.utils.clip_grad_norm_ folded in (_GlobalClip).
+class Adam(_MultiTensor, torch.optim.Optimizer):
+    """torch.optim.Adam(lr, betas, eps, weight_decay) as one kernel per group; ``max_norm``: torch.nn.utils.clip_grad_norm_ folded in (_MultiTensor).
     Deviation under a LossScaler (fp16 only; the reference has no mixed precision): when the device-side overflow flag skips an update the
     host-side ``state['step']`` has still advanced (reading the flag would sync), so after a skipped step the bias corrections run one step
     ahead of torch.cuda.amp.GradScaler's."""
@@ -283,52 +300,32 @@ class Adam(_GlobalClip, torch.optim.Optimizer):
     def step_with(self, params, grads, scaler=None):
         return self.step(_override={id(p): g for p, g in zip(params, grads)}, scaler=scaler)
 
+    def _moments(self, ps):
+        m1, m2 = [], []
+        for p in ps:
+            st = self.state[p]
+            if "exp_avg" not in st:
+                st["step"] = 0
+                st["exp_avg"] = torch.zeros_like(p)
+                st["exp_avg_sq"] = torch.zeros_like(p)
+            st["step"] = int(st["step"]) + 1
+            m1.append(st["exp_avg"])
+            m2.append(st["exp_avg_sq"])
+        return m1, m2
+
     @torch.no_grad()
     def step(self, closure=None, _override=None, scaler=None):
         ops.flush_wgrads()
-        todo = []
-        for gi, group in enumerate(self.param_groups):
-            if _override is not None:
-                ps = [p for p in group["params"] if id(p) in _override]
-                grads = [_override[id(p)] for p in ps]
-            else:
-                ps = [p for p in group["params"] if p.grad is not None]
-                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
-            if not ps:
-                continue
-            m1, m2 = [], []
-            for p in ps:
-                st = self.state[p]
-                if "exp_avg" not in st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p)
-                    st["exp_avg_sq"] = torch.zeros_like(p)
-                st["step"] = int(st["step"]) + 1
-                m1.append(st["exp_avg"])
-                m2.append(st["exp_avg_sq"])
-            step = int(self.state[ps[0]]["step"])
-            tab = self._tables.setdefault(gi, _Tables())
-            (pp, gp, ap, vp, sizes, bm), nb = tab.get([ps, grads, m1, m2], ps[0].device)
-            todo.append((group, grads, pp, gp, ap, vp, sizes, bm, nb, step))
-        clip = self.max_norm is not None and bool(todo)
-        if clip:
-            self._clip_prepare(sum(t[8] for t in todo), todo[0][2].device)
-        if scaler is not None:
-            for i, t in enumerate(todo):
-                scaler.check(t[1], i)
-        # the norm of ALL groups, unscaled, before any group is updated
-        coef = self._clip_launch([(t[3], t[6], t[7], t[8]) for t in todo], scaler) if clip else None
-        sp, fp = (scaler.scale.data_ptr(), scaler.found_inf.data_ptr()) if scaler is not None else (None, None)
-        for group, grads, pp, gp, ap, vp, sizes, bm, nb, step in todo:
-            b1, b2 = group["betas"]
-            if clip:
-                check(lib.vs_adam_clip_multi(pp.data_ptr(), gp.data_ptr(), ap.data_ptr(), vp.data_ptr(), sizes.data_ptr(), bm.data_ptr(),
-                                             nb, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+        todo = self._groups(_override, self._moments)
+        coef, sp, fp = self._check_and_norm(todo, scaler)
+        for g in todo:
+            group, (b1, b2), step = g.group, g.group["betas"], int(self.state[g.params[0]]["step"])
+            if coef is not None:
+                check(lib.vs_adam_clip_multi(*g.tables, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                              float(group["weight_decay"]), step, coef, sp, fp, _stream()), "adam_clip_multi")
-                continue
-            check(lib.vs_adam_scaled_multi(pp.data_ptr(), gp.data_ptr(), ap.data_ptr(), vp.data_ptr(), sizes.data_ptr(), bm.data_ptr(),
-                                           nb, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                           float(group["weight_decay"]), step, sp, fp, _stream()), "adam_multi")
+            else:
+                check(lib.vs_adam_scaled_multi(*g.tables, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                               float(group["weight_decay"]), step, sp, fp, _stream()), "adam_multi")
         if scaler is not None:
             scaler.update()
         ops.weights_changed()
