@@ -971,6 +971,41 @@ int vs_ds_head_fwd(const void* feat, int dtype, const float* weight, const float
 int vs_ds_head_bwd(const void* feat, int dtype, const float* weight, const float* bias, const float* label, const float* class_w, double* scratch,
                    const float* gout, void* dfeat, float* dweight, float* dbias, int batch, int classes, int channels, int d, int h, int w, int stride,
                    int bot, int top, float eps, float dice_w, float ce_w, int batch_dice, float gamma, float scale, void* stream);
+/* Signed distance maps of a label volume and the boundary loss on them (csrc/sdm.hip; Kervadec et al., MIDL 2019).  The reference has
+ * neither; the rule is this library's own.
+ *   label  fp32 (n, 1, d, h, w).  The class of a voxel is (int)label where 0 <= label < n_class in fp32, none otherwise (-1, 255, NaN: the rule of
+ *          vs_seg_loss_*).  P_c = the voxels of class c; every other voxel of the volume, the classless ones included, is outside P_c.
+ *   phi    fp32 (n, top - bot, d, h, w), plane j for class c = bot + j.  With S = diag(spacing) (sz, sy, sx; NULL: the identity):
+ *            v outside P_c:  phi_c(v) = +sqrt(min over u in P_c of |S (v - u)|^2)
+ *            v in P_c:       phi_c(v) = 1 - sqrt(min over u outside P_c of |S (v - u)|^2)       (the "- 1" of one_hot2dist, under a spacing too)
+ *            P_c empty, or the whole volume: the plane is 0.0 — decided per voxel by the "no such voxel" value (INT_MAX / +inf) its own minimum
+ *            still holds: no reduction, nothing read back.
+ *          Squared distances are exact int32 without a spacing and fp64 sums of (s r)^2 with one; square root and subtraction are fp64 and the
+ *          result is rounded to fp32 once.
+ * Three launches (two for h == 1): an x pass that reads the label once and writes both row maps (to P_c, to its complement) of every class into the
+ * workspace, a y pass over both maps in place, a z pass that reads the label again and, per voxel, the map opposite to its membership, and stores
+ * phi.  workspace: vs_signed_distance_workspace_bytes(n, top - bot, ...) bytes (2 maps of int32 / double per class; negative: VS_E*), contents undefined
+ * on entry.  Limits as for vs_edt: d, h <= 1024, d*h*w < 2^31, d^2 + h^2 + w^2 < 2^31 - 1 without a spacing: VS_ESHAPE, as for an empty shape;
+ * n_class < 1, bot / top out of order, a spacing that is not positive and finite, a null pointer, aliased buffers: VS_EINVAL; label / phi / workspace
+ * not 16-byte aligned: VS_EALIGN — all on the host before any launch.  Rows need no alignment and w is arbitrary.  No atomics, no memset, nothing
+ * allocated, synchronised or read back: capturable, the same bits eagerly, under graph replay and in both builds. */
+long long vs_signed_distance_workspace_bytes(int n, int classes, int d, int h, int w, int with_spacing);
+int vs_signed_distance(const float* label, float* phi, int n, int n_class, int bot, int top, int d, int h, int w, const double* spacing,
+                       void* workspace, void* stream);
+/* Boundary loss of planar fp32 probabilities p [b][c][voxels] against label [b][voxels] and phi [b][top - bot][voxels]:
+ *   L_B = 1 / (b (top - bot)) sum_b 1 / N_b sum_{c in [bot, top)} sum_{v valid} p_c(v) phi_c(v),   N_b = the valid voxels of sample b (label in [0, c));
+ * a sample with N_b = 0 contributes 0.  fp64 sums of exactly promoted fp32 products: per-workgroup partials by ordinary stores, then a one-workgroup
+ * finish in a fixed order.  terms = (L_B, w L_B), each rounded once, w = weight_dev[0] read on the DEVICE (a weight schedule needs no re-capture).
+ * scratch: vs_boundary_loss_scratch_doubles() doubles (0: b outside [1, 64] or c < 1), contents undefined on entry; the forward leaves (sum, N_b) per sample
+ * at its head for the backward (one launch), which writes every plane of
+ *   gp[b][c][v] = gout[0] w phi_c(v) / (b (top - bot) N_b)   formed in fp64, rounded once; exactly 0.0 at classless voxels and outside [bot, top).
+ * 16-byte loads and stores when voxels is a multiple of 4 and the volumes are 16-byte aligned, dword accesses otherwise (any voxels >= 1).  A null pointer,
+ * c < 1, bot / top out of order: VS_EINVAL; b > 64 or voxels >= 2^31: VS_ESHAPE; an fp32 buffer not 4-byte or scratch not 8-byte aligned: VS_EALIGN. */
+long long vs_boundary_loss_scratch_doubles(int b, int c);
+int vs_boundary_loss_fwd(const float* p, const float* label, const float* phi, const float* weight_dev, double* scratch, float* terms, int b, int c,
+                         int bot, int top, long long voxels, void* stream);
+int vs_boundary_loss_bwd(const float* label, const float* phi, const float* weight_dev, const double* scratch, const float* gout, float* gp, int b, int c,
+                         int bot, int top, long long voxels, void* stream);
 /* nn.BCELoss() mean reduction (utils/evaluation.py:29-39), log clamped at -100 like torch */
 int vs_bce_fwd(const float* p, const float* t, float* out, double* scratch, long long count, void* stream);
 int vs_bce_bwd(const float* p, const float* t, const float* gout, float* gp, long long count, void* stream);

@@ -777,6 +777,12 @@ def run(args, side="source"):
 
     seg_loss = seg_loss_of(args)                                            # --seg_loss dice_ce: ops.seg_loss's arguments; None: the reference's Dice
     deep_kw = {} if deep is None else {"deep": deep}
+    # --boundary_weight: the boundary term's weight is ONE device scalar, refilled at the top of every outer epoch (train.boundary_weight): the captured
+    # launches read it, so the ramp needs no re-capture.  With the flags at their defaults nothing is built and loss_fn passes nothing on
+    boundary_on = boundary_enabled(args) and method in SEG_LOSS_METHODS and seg_loss is not None
+    boundary_w = torch.zeros((), dtype=torch.float32, device="cuda") if boundary_on else None
+    if boundary_on:
+        deep_kw = dict(deep_kw, boundary={"weight": boundary_w, "spacing": None})
 
     def loss_fn():
         if method == "vae_train":
@@ -845,6 +851,8 @@ def run(args, side="source"):
         if getattr(args, "lr_schedule", "constant") == "poly":          # a captured step follows through sync_hyper(): no re-capture
             for grp, base in zip(optimizer.param_groups, base_lrs):
                 grp["lr"] = optim.poly_lr(base, epoch, n_outer, args.poly_power)
+        if boundary_w is not None:                                      # likewise: the captured launches read the scalar
+            boundary_w.fill_(T.boundary_weight(epoch, args.boundary_weight, args.boundary_ramp, args.boundary_max))
         if sampler is not None:
             sampler.set_epoch(epoch)
         skip_da = method in ("domain_adaptation", "domain_adaptation_dis") and epoch == 0 and not getattr(args, "train_first_epoch", False)    # main_target.py:506,697: `if epoch == 0: continue`
@@ -1119,6 +1127,30 @@ def check_seg_loss_flags(parser, a, methods=SEG_LOSS_METHODS):
     return a
 
 
+BOUNDARY_FLAGS = (("boundary_weight", 0.0), ("boundary_ramp", 0.0), ("boundary_max", None))
+
+
+def boundary_enabled(args):
+    """--boundary_weight / --boundary_ramp switch the boundary term on (a ramp from weight 0 is a schedule too)"""
+    return getattr(args, "boundary_weight", 0.0) > 0 or getattr(args, "boundary_ramp", 0.0) > 0
+
+
+def check_boundary_flags(parser, a, methods=SEG_LOSS_METHODS):
+    """--boundary_weight, --boundary_ramp and --boundary_max add the boundary term to the compound loss: they belong where --seg_loss dice_ce does
+    (seg_train and joint_train of main_source.py; main_target.py passes methods=())"""
+    given = [n for n, default in BOUNDARY_FLAGS if getattr(a, n, default) != default]
+    if not given:
+        return a
+    names = ", ".join("--" + n for n in given)
+    if a.method not in methods:
+        parser.error("%s: the boundary loss belongs to --method seg_train and joint_train of main_source.py, not to --method %s" % (names, a.method))
+    if getattr(a, "seg_loss", "dice") != "dice_ce":
+        parser.error("%s add(s) the boundary term to the compound loss: add --seg_loss dice_ce" % names)
+    if not boundary_enabled(a):
+        parser.error("%s: the boundary term is off — give --boundary_weight or --boundary_ramp above 0" % names)
+    return a
+
+
 def seg_loss_of(args):
     """the `loss` argument of train.seg_train_losses / joint_train_losses from the flags; None for --seg_loss dice (the default): the reference's Dice"""
     if getattr(args, "seg_loss", "dice") != "dice_ce":
@@ -1131,6 +1163,7 @@ def check_aug_flags(parser, a, seg_loss_methods=SEG_LOSS_METHODS):
     """--aug_elastic and --aug_intensity act on the augmented training samples: with --no_aug there are none; --standardize reads real cases;
     the compound-loss flags belong to seg_loss_methods (check_seg_loss_flags)"""
     check_seg_loss_flags(parser, a, seg_loss_methods)
+    check_boundary_flags(parser, a, seg_loss_methods)
     if getattr(a, "aug_elastic", 0.0) > 0 and getattr(a, "no_aug", False):
         parser.error("--aug_elastic deforms the augmented training samples: it cannot be combined with --no_aug")
     if getattr(a, "aug_intensity", False) and getattr(a, "no_aug", False):
@@ -1193,6 +1226,12 @@ def add_native_flags(parser):
                    "levels of the decoder — 1: the half-resolution skip sum, 2: the quarter-resolution one as well — through 1x1x1 heads fused with their "
                    "loss (ops.ds_head, DESIGN 3.21), against the label picked at stride 2 / 4, the levels weighted 2^-i and normalised (L = 2: 4/7, "
                    "2/7, 1/7); the heads train with the network, are saved beside it and are never used for prediction.  0 (default) = off")
+    g.add_argument("--boundary_weight", type=_nonnegative, default=0.0, metavar="A", help="with --seg_loss dice_ce: add A times the boundary loss (Kervadec et "
+                   "al., MIDL 2019) of the full-resolution prediction — the mean of p_c * phi_c over the foreground channels, phi_c the signed distance map of "
+                   "the label, made on the device in every step (ops.boundary_loss, DESIGN 3.22).  0 (default) = off")
+    g.add_argument("--boundary_ramp", type=_nonnegative, default=0.0, metavar="STEP", help="with --seg_loss dice_ce: the boundary weight of outer epoch e is "
+                   "min(A + e * STEP, --boundary_max), refilled on the device at the top of the epoch: a captured step is not rebuilt")
+    g.add_argument("--boundary_max", type=_nonnegative, default=None, metavar="M", help="with --boundary_ramp: the cap of the boundary weight (default: none)")
     g.add_argument("--momentum", type=_nonnegative, default=0.9, metavar="M", help="SGD's momentum (the reference: 0.9; nnU-Net: 0.99 with --nesterov)")
     g.add_argument("--weight_decay", type=_nonnegative, default=0.0, metavar="W", help="L2 weight decay of SGD / Adam (the reference: 0; nnU-Net: 3e-5)")
     g.add_argument("--nesterov", action="store_true", help="SGD with Nesterov momentum: the step is lr * (g + momentum * buf) instead of lr * buf")

@@ -127,6 +127,15 @@ def hd95(A, B, spacing=None, connectivity=6):
     return surface_metrics(A, B, spacing, connectivity)["hd95"]
 
 
+def signed_distance(label_volume, n_class, spacing=None):
+    """The signed distance maps of a (D, H, W) label volume (values 0..n_class-1; anything else belongs to no class) -> fp32 (n_class, D, H, W) on the
+    device (ops.signed_distance): phi_c is the Euclidean distance, under `spacing` = (sz, sy, sx), to the nearest voxel of class c outside
+    the class and 1 - the distance to the nearest voxel outside it inside — Kervadec's one_hot2dist; a class that is absent or fills the volume gives 0."""
+    if label_volume.dim() != 3:
+        raise ValueError("expected a (D, H, W) label volume, got shape %s" % (tuple(label_volume.shape),))
+    return V.signed_distance(label_volume.detach().reshape((1, 1) + tuple(label_volume.shape)), n_class, spacing=spacing)[0]
+
+
 # ----------------------------------------------------------------------------------------------------
 # the objects of a label: per-component measurements, the class confusion matrix and lesion-wise detection scores on the device
 # (csrc/regions.hip).  The reference has no counterpart; tests/regions_util.py restates the definitions with scipy.ndimage and numpy.

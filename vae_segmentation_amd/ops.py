@@ -23,6 +23,7 @@ from . import _lib
 from ._lib import (VS_BF16, VS_CONV_K2S2, VS_CONV_K3, VS_CONV_UP, VS_F16, VS_F32, VS_PACK_ROWS_D0, VS_PACK_ROWS_D1_FLIP,
                    VS_PACK_SCATTER_D1, _contig, _p, _require_cuda, _stream, check, lib)
 from .volume import *  # noqa: F401,F403
+from .volume import signed_distance  # noqa: F401  (reachable as ops.signed_distance; BoundaryLoss's maps)
 from .volume import (PATCH_CHUNK, PATCH_LABEL_DTYPES, PATCH_MAX_CLASSES, PATCH_MAX_SOURCES, patch_gather, patch_index,  # noqa: F401  (volume.PATCH_NAMES)
                      patch_pick)
 
@@ -2433,6 +2434,74 @@ def seg_loss(p, target, dice_weight=1.0, ce_weight=1.0, batch_dice=False, class_
         raise ValueError("seg_loss: %d class weights for %d channels" % (len(class_weights), channels))
     final, terms = SegLoss.apply(p, target.label, bot, top, eps, dice_weight, ce_weight, bool(batch_dice), class_weights, gamma)
     return final, tuple(terms.unbind(0))
+
+
+class BoundaryLoss(torch.autograd.Function):
+    """weighted = w * L_B, L_B = mean over samples and channels [bot, top) of (1 / N_b) sum over the valid voxels of p_c * phi_c (Kervadec et al., MIDL
+    2019; csrc/sdm.hip) for planar fp32 probabilities p (B, C, ...), the LABEL volume (B, 1, ...) whose valid voxels count (SegLoss's rule)
+    and its signed distance maps phi (B, top - bot, ...) — TWO forward launches and ONE backward launch, fp64 sums in a fixed order, no atomics.  w is a
+    0-dim fp32 DEVICE tensor read by the launches, so a captured step follows a weight schedule.  -> (weighted, L_B); L_B is not
+    differentiable, and the only gradient is p's: exactly 0 at classless voxels and in channels outside [bot, top)."""
+
+    @staticmethod
+    def forward(ctx, p, label, phi, weight, bot, top):
+        _require_cuda(p, label, phi, weight)
+        p, label, phi = _contig(p.float()), _contig(label.float()), _contig(phi.float())
+        b, c = p.shape[0], p.shape[1]
+        voxels = p.numel() // (b * c)
+        if label.numel() != b * voxels:
+            raise ValueError("label target: expected %d x %d labels, got %s" % (b, voxels, tuple(label.shape)))
+        if phi.numel() != b * (top - bot) * voxels:
+            raise ValueError("boundary loss: expected %d x %d x %d distances, got %s" % (b, top - bot, voxels, tuple(phi.shape)))
+        if weight.dim() != 0 or weight.dtype != torch.float32:
+            raise TypeError("boundary loss: the weight is a 0-dim float32 device tensor")
+        scratch = torch.empty(max(1, lib.vs_boundary_loss_scratch_doubles(b, c)), dtype=torch.float64, device=p.device)
+        terms = torch.empty(2, dtype=torch.float32, device=p.device)
+        cfg = (b, c, int(bot), int(top), voxels)
+        check(lib.vs_boundary_loss_fwd(p.data_ptr(), label.data_ptr(), phi.data_ptr(), weight.data_ptr(), scratch.data_ptr(), terms.data_ptr(), *cfg,
+                                       _stream()), "boundary_loss_fwd")
+        ctx.save_for_backward(label, phi, weight, scratch)
+        ctx.cfg, ctx.shape = cfg, tuple(p.shape)
+        weighted, term = terms[1], terms[0]
+        ctx.mark_non_differentiable(term)
+        ctx.set_materialize_grads(False)      # no zero-fill launch for the term's gradient
+        return weighted, term
+
+    @staticmethod
+    def backward(ctx, g, _gterms):
+        label, phi, weight, scratch = ctx.saved_tensors
+        gp = None
+        if g is not None and ctx.needs_input_grad[0]:
+            g = _contig(g.float())
+            gp = torch.empty(ctx.shape, dtype=torch.float32, device=phi.device)
+            check(lib.vs_boundary_loss_bwd(label.data_ptr(), phi.data_ptr(), weight.data_ptr(), scratch.data_ptr(), g.data_ptr(), gp.data_ptr(), *ctx.cfg,
+                                           _stream()), "boundary_loss_bwd")
+        return (gp,) + (None,) * 5
+
+
+def boundary_weight_tensor(weight, device):
+    """the weight of ops.boundary_loss as the launches read it: a 0-dim fp32 tensor on `device` (a number is filled into a new one by a launch)"""
+    if torch.is_tensor(weight):
+        if weight.dim() != 0 or weight.dtype != torch.float32 or weight.device != torch.device(device):
+            raise TypeError("boundary_loss: a tensor weight is a 0-dim float32 tensor on the device of p")
+        return weight.detach()
+    return torch.full((), float(weight), dtype=torch.float32, device=device)
+
+
+def boundary_loss(p, target, weight, botindex=0, topindex=None, spacing=None):
+    """weight * L_B -> (weighted, term) for the softmax output p (B, C, D, H, W) and an ops.LabelTarget: the boundary loss (BoundaryLoss) on the
+    signed distance maps of the label (ops.signed_distance with n_class = C, the channels [botindex, topindex), topindex None: C, and `spacing`), made on
+    the device in the same call.  weight: a number, or a 0-dim fp32 device tensor that the launches read — refill it to move the weight of a captured
+    step.  Add `weighted` to a regional loss such as ops.seg_loss's; `term` is L_B itself, not differentiable."""
+    if not isinstance(target, LabelTarget):
+        raise TypeError("boundary_loss takes its target as an ops.LabelTarget (a label volume)")
+    if p.dim() != 5:
+        raise ValueError("boundary_loss: p is a planar (B, C, D, H, W) tensor, got shape %s" % (tuple(p.shape),))
+    channels = p.shape[1]
+    bot, top = int(botindex), channels if topindex is None else min(int(topindex), channels)
+    label = target.label.reshape((p.shape[0], 1) + tuple(p.shape[2:]))
+    phi = signed_distance(label.detach(), channels, bot, top, spacing)
+    return BoundaryLoss.apply(p, label, phi, boundary_weight_tensor(weight, p.device), bot, top)
 
 
 DS_STRIDES = (2, 4, 8)

@@ -62,10 +62,43 @@ def _deep_seg_loss(pred, batch, label, deep, kw, n_class, eps):
     return final, terms, [t for _, t in levels]
 
 
-def joint_train_losses(joint, img, label, lambda_vae=0.1, eps=EPS_MAIN_SOURCE, n_class=2, loss=None, deep=None):
-    """deep: a modules.DeepSupervision built on joint.Seg (needs `loss`): see seg_train_losses"""
+def boundary_weight(epoch, base, step=0.0, cap=None):
+    """the weight of the boundary term in outer epoch `epoch`: min(base + epoch * step, cap) (cap None: no cap) — Kervadec's schedule raises the weight
+    of the boundary term by a fixed amount per epoch"""
+    w = float(base) + int(epoch) * float(step)
+    return w if cap is None else min(w, float(cap))
+
+
+def _boundary_args(boundary, loss):
+    """`boundary` of seg_train_losses / joint_train_losses: None, or {"weight": number or 0-dim fp32 device tensor, "spacing": None or (sz, sy, sx)};
+    it is added to the compound loss, so it needs loss="""
+    if boundary is None:
+        return None
+    if loss is None:
+        raise TypeError("the boundary term is added to the compound loss: pass loss= as well")
+    kw = dict(boundary)
+    unknown = set(kw) - {"weight", "spacing"}
+    if unknown or "weight" not in kw:
+        raise TypeError("boundary: {'weight': ..., 'spacing': None}, got %s" % ", ".join(sorted(kw)))
+    return kw
+
+
+def _add_boundary(final, aux, pred, label, boundary, n_class):
+    """final + weight * L_B on the full-resolution prediction over the channels [1, n_class) (ops.boundary_loss, DESIGN 3.22), added last;
+    aux["boundary_loss"] = L_B"""
+    weighted, term = ops.boundary_loss(pred, ops.LabelTarget(label), boundary["weight"], botindex=1, topindex=n_class, spacing=boundary.get("spacing"))
+    aux["boundary_loss"] = term
+    return final + weighted, aux
+
+
+def joint_train_losses(joint, img, label, lambda_vae=0.1, eps=EPS_MAIN_SOURCE, n_class=2, loss=None, deep=None, boundary=None):
+    """deep: a modules.DeepSupervision built on joint.Seg (needs `loss`): see seg_train_losses; boundary: the boundary term (needs `loss`), likewise"""
     if deep is not None and loss is None:
         raise TypeError("deep supervision applies the compound loss to the coarse levels: pass loss= as well")
+    boundary = _boundary_args(boundary, loss)
+    if boundary is not None:
+        final, aux = joint_train_losses(joint, img, label, lambda_vae=lambda_vae, eps=eps, n_class=n_class, loss=loss, deep=deep)
+        return _add_boundary(final, aux, aux["batch"]["pred"], label, boundary, n_class)
     batch = {"img": img}
     if loss is not None and deep is not None:
         batch["label"] = label
@@ -88,11 +121,17 @@ def joint_train_losses(joint, img, label, lambda_vae=0.1, eps=EPS_MAIN_SOURCE, n
     return final, {"recon_loss": recon_loss, "dice_loss": dsc_loss, "batch": batch}
 
 
-def seg_train_losses(seg, img, label, eps=EPS_MAIN_SOURCE, n_class=2, loss=None, deep=None):
+def seg_train_losses(seg, img, label, eps=EPS_MAIN_SOURCE, n_class=2, loss=None, deep=None, boundary=None):
     """deep: a modules.DeepSupervision built on `seg` (needs `loss`): the full-resolution compound loss is weighted ds_weights()[0], head i of the
-    coarser levels ds_weights()[i] (ops.ds_head's scale), final is their sum and aux["ds_losses"] holds the levels' (dice_term, ce_term)"""
+    coarser levels ds_weights()[i] (ops.ds_head's scale), final is their sum and aux["ds_losses"] holds the levels' (dice_term, ce_term).
+    boundary: {"weight": a number or a 0-dim fp32 device tensor, "spacing": None or (sz, sy, sx)} (needs `loss`) adds weight * the boundary loss of the
+    full-resolution prediction over the channels [1, n_class) behind every other part (ops.boundary_loss); aux["boundary_loss"] holds it"""
     if deep is not None and loss is None:
         raise TypeError("deep supervision applies the compound loss to the coarse levels: pass loss= as well")
+    boundary = _boundary_args(boundary, loss)
+    if boundary is not None:
+        final, aux = seg_train_losses(seg, img, label, eps=eps, n_class=n_class, loss=loss, deep=deep)
+        return _add_boundary(final, aux, aux["batch"]["pred"], label, boundary, n_class)
     batch = {"img": img}
     if loss is not None and deep is not None:
         batch["label"] = label

@@ -160,6 +160,36 @@ def surface_distances(pred, gt, spacing=None, connectivity=6):
     return out
 
 
+# signed distance maps of a label volume (csrc/sdm.hip).  The training loss is its first caller (ops.boundary_loss): ops imports signed_distance by name
+_SDM_WORKSPACES = {}
+
+
+def signed_distance(label, n_class, botindex=0, topindex=None, spacing=None):
+    """The signed distance maps phi_c, c in [botindex, topindex) (topindex None: n_class), of a (N, 1, D, H, W) label volume -> fp32
+    (N, topindex - botindex, D, H, W), by the rule of DESIGN 3.22: a voxel's class is (int)label where 0 <= label < n_class and none otherwise; outside
+    the class phi_c = +distance to its nearest voxel, inside 1 - distance to the nearest voxel outside it (Kervadec's one_hot2dist), exact Euclidean
+    distances under spacing = (sz, sy, sx) or unit spacing; a plane whose class is absent or fills the whole volume is 0.  Three launches, no
+    synchronisation, capturable; the workspace is cached per shape like _EDT_WORKSPACES."""
+    _require_cuda(label)
+    if label.requires_grad:
+        raise RuntimeError("the signed distance map is forward only: detach the input")
+    if label.dim() != 5 or label.shape[1] != 1:
+        raise ValueError("expected a (N, 1, D, H, W) label volume, got shape %s" % (tuple(label.shape),))
+    n_class = int(n_class)
+    bot, top = int(botindex), n_class if topindex is None else int(topindex)
+    if n_class < 1 or not 0 <= bot < top <= n_class:
+        raise ValueError("signed_distance: channels [%d, %d) of %d classes" % (bot, top, n_class))
+    lab = _aligned16(label.float())
+    n, _, d, h, w = lab.shape
+    k = top - bot
+    sp = _spacing_array(spacing)
+    ws = _workspace(_SDM_WORKSPACES, (n, k, d, h, w, sp is not None, lab.device),
+                    lambda: lib.vs_signed_distance_workspace_bytes(n, k, d, h, w, int(sp is not None)), "signed_distance_workspace_bytes", lab.device)
+    phi = torch.empty((n, k, d, h, w), dtype=torch.float32, device=lab.device)
+    check(lib.vs_signed_distance(lab.data_ptr(), phi.data_ptr(), n, n_class, bot, top, d, h, w, sp, ws.data_ptr(), _stream()), "signed_distance")
+    return phi
+
+
 # binary morphology and hole filling (csrc/morph.hip)
 MORPH_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3}          # VS_MORPH_*
 _MORPH_WORKSPACES = {}
