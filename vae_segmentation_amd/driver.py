@@ -11,18 +11,23 @@ One process per GPU: under torchrun (WORLD_SIZE > 1) every rank builds the same 
 synthetic volumes and averages gradients with one RCCL all-reduce per step (vae_segmentation_amd.ddp) — the replacement
 for the reference's nn.DataParallel wrap (main_source.py:354, main_target.py:436-438).
 """
+import argparse
+import copy
 import json
 import os
+import sys
 import time
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ddp, ops, optim, volume
+from . import data_gpu, ddp, ops, optim, volume
 from . import train as T
-from .evaluation import EPS_EVALUATION, EPS_MAIN_SOURCE, avg_dsc
-from .modules import Embed, Encoder, Fusion, Joint, Joint2, Segmentation, VAE, set_kernel_dtype
+from .evaluation import (EPS_EVALUATION, EPS_MAIN_SOURCE, INTENSITY_CLIP, LESION_RECORD_FIELDS, avg_dsc, binarize, coarse_to_fine_predict, confusion,
+                         lesion_metrics, lesion_record_to_host, localise, mutual_information_3d, postprocess, segmentation_model_fn,
+                         sliding_window_predict, tta_flips)
+from .modules import DeepSupervision, Embed, Encoder, Fusion, Joint, Joint2, Segmentation, VAE, set_kernel_dtype, set_recompute
 
 LABEL_KEY, IMG_KEY = "venous_pancreas", "venous"          # main_source.py:355-356
 
@@ -72,7 +77,6 @@ class SyntheticVolumes(torch.utils.data.Dataset):
 # ----------------------------------------------------------------------------------------------------
 def filedict_from_json(json_path, key, epoch=1):
     """main_source.py:123-131: the case names under `key`, repeated `epoch` times"""
-    import json
     with open(json_path, "r") as f:
         names = json.load(f).get(key, [])
     return list(names) * epoch
@@ -92,20 +96,19 @@ class DeviceCaseLoader:
     S^3 windows of the unscaled case (data_gpu.PatchSampler / train_patch) in place of CropResize; validation loaders never do."""
 
     def __init__(self, names, root, args, batch_size, train, shuffle, rank=0, world=1, seed=0):
-        from . import data_gpu
         names = list(names)
         if train and world > 1:
             names = names[:len(names) // world * world]          # every rank the same number of steps (the all-reduce is collective)
         self.names, self.root, self.bs, self.shuffle = names[rank::world], root, batch_size, shuffle
         self.patch, self.mask_index, self.epoch, self.seed = (args.size,) * 3, mask_index_of(args), 0, seed + rank
         self.drop_last = train
-        self.shift = int(getattr(args, "shift", 0)) if train else 0           # main_target.py:204 (training crops only; validation: CropResize default)
+        self.shift = int(args.shift) if train else 0           # main_target.py:204 (training crops only; validation: CropResize default)
         # --train_patches: a training loader cuts windows of the unscaled case in place of CropResize (self.sampler, below).  The sampler has then already
         # chosen where the patch lies, and the spatial transform resamples the gathered block about its centre: random_crop=False
-        patches = bool(train and getattr(args, "train_patches", False))
+        patches = bool(train and args.train_patches)
         self.transform = None
-        if train and not getattr(args, "no_aug", False):                       # main_source.py:195-205
-            p_el = float(getattr(args, "aug_elastic", 0.0) or 0.0)            # --aug_elastic: the stage main_source.py:198 leaves one flag away from on
+        if train and not args.no_aug:                       # main_source.py:195-205
+            p_el = float(args.aug_elastic or 0.0)            # --aug_elastic: the stage main_source.py:198 leaves one flag away from on
             elastic = {"noise": "philox", "seed": seed + 1000 * rank} if p_el > 0 else {}
             self.transform = data_gpu.MySpatialTransform(
                 self.patch, [d // 2 - 5 for d in self.patch], random_crop=not patches, scale=(0.85, 1.15), do_elastic_deform=p_el > 0, alpha=(0, 500),
@@ -113,25 +116,23 @@ class DeviceCaseLoader:
                 border_cval_data=-1024, data_key=IMG_KEY, p_el_per_sample=p_el, label_key=LABEL_KEY, p_scale_per_sample=1, p_rot_per_sample=1,
                 rng=np.random.RandomState(seed + 1000 * rank), **elastic)
         self.intensity = None
-        if train and getattr(args, "aug_intensity", False) and not getattr(args, "no_aug", False):
+        if train and args.aug_intensity and not args.no_aug:
             # --aug_intensity: nnU-Net's intensity stage after CenterIntensities; its own generator, so the spatial draws keep their stream
-            p_lr = float(getattr(args, "aug_lowres", 0.0) or 0.0)            # --aug_lowres: the stage's simulated low resolution, off unless asked for
+            p_lr = float(args.aug_lowres or 0.0)            # --aug_lowres: the stage's simulated low resolution, off unless asked for
             lowres = {"p_lowres": p_lr} if p_lr > 0 else {}
             self.intensity = data_gpu.IntensityAugment(IMG_KEY, LABEL_KEY, rng=np.random.RandomState(seed + 1000 * rank + 500), noise="philox",
                                                        seed=seed + 1000 * rank, **lowres)
         self.standardize = None
-        if getattr(args, "standardize", None) is not None:
+        if args.standardize is not None:
             # --standardize: the case's percentile window onto Clip's, before anything else sees the image; the pipeline behind it keeps its constants
-            from . import evaluation
-            self.standardize = data_gpu.IntensityStandardizer(tuple(args.standardize), target=evaluation.INTENSITY_CLIP,
-                                                              above=getattr(args, "standardize_above", None))
+            self.standardize = data_gpu.IntensityStandardizer(tuple(args.standardize), target=INTENSITY_CLIP,
+                                                              above=args.standardize_above)
         self.sampler = None
         if patches:
             # the sampler has a generator of its own, so the spatial and intensity draws keep their streams; without augmentation nothing resamples a margin away
             self.n_class = n_class_of(args)
-            self.sampler = data_gpu.PatchSampler(self.patch, float(getattr(args, "patch_fg", 0.33)), rng=np.random.RandomState(seed + 1000 * rank + 900),
-                                                 margin=int(getattr(args, "patch_margin", 16)) if self.transform is not None else 0)
-        self._dg = data_gpu
+            self.sampler = data_gpu.PatchSampler(self.patch, float(args.patch_fg), rng=np.random.RandomState(seed + 1000 * rank + 900),
+                                                 margin=int(args.patch_margin) if self.transform is not None else 0)
 
     def _load(self, name):
         """a case's merge array on the device; with --standardize its image channel standardised"""
@@ -150,7 +151,7 @@ class DeviceCaseLoader:
         """--val_whole_volume: every case as it is on disk — (raw image (D, H, W), relabelled label (D, H, W)) on the device, in list order, uncropped"""
         for name in self.names:
             merge = self._load(name)
-            yield merge[..., 0].contiguous(), self._dg.relabel(merge[..., 1].contiguous(), self.mask_index)
+            yield merge[..., 0].contiguous(), data_gpu.relabel(merge[..., 1].contiguous(), self.mask_index)
 
     def __iter__(self):
         order = np.arange(len(self.names))
@@ -162,16 +163,16 @@ class DeviceCaseLoader:
                 merge = self._load(self.names[i])
                 extra = {} if self.intensity is None else {"intensity": self.intensity}
                 if self.sampler is not None:
-                    img, lab, _ = self._dg.train_patch(merge, self.patch, self.sampler, self.n_class, j, self.bs, self.mask_index, self.transform, field=IMG_KEY,
+                    img, lab, _ = data_gpu.train_patch(merge, self.patch, self.sampler, self.n_class, j, self.bs, self.mask_index, self.transform, field=IMG_KEY,
                                                        **extra)
                 else:
-                    img, lab = self._dg.train_sample(merge, self.patch, self.mask_index, self.transform, field=IMG_KEY, shift=self.shift, **extra)
+                    img, lab = data_gpu.train_sample(merge, self.patch, self.mask_index, self.transform, field=IMG_KEY, shift=self.shift, **extra)
                 imgs.append(img); labs.append(lab)
             yield {IMG_KEY: torch.cat(imgs), LABEL_KEY: torch.cat(labs)}
 
 
 def make_loaders(args, rank, world):
-    if getattr(args, "real_data", False):
+    if args.real_data:
         json_path = os.path.join("lists", args.data_path)
         train = DeviceCaseLoader(filedict_from_json(json_path, args.train_list, args.eval_epoch), args.data_root, args, args.batch_size, True,
                                  shuffle=args.method != "domain_adaptation", rank=rank, world=world)       # main_source.py:232-236
@@ -191,8 +192,7 @@ def make_loaders(args, rank, world):
 def make_pseudo_loader(args, rank, world):
     """main_target.py:228-258,299-307: the second, pseudo-labelled training loader of a --pseudo_list run — its own case list, data root and structure indices
     (--pseudo_data_root, --pseudo_pan_index), the training transform stack, shuffled, drop_last."""
-    if getattr(args, "real_data", False):
-        import copy
+    if args.real_data:
         pargs = copy.copy(args)
         pargs.pan_index = args.pseudo_pan_index                # main_target.py:233: NumpyLoader_Multi_merge(mask_index=pseudo_mask_index)
         return DeviceCaseLoader(filedict_from_json(os.path.join("lists", args.data_path), args.pseudo_list, args.eval_epoch), args.pseudo_data_root, pargs,
@@ -212,8 +212,8 @@ def build_joint(args):
     nc = n_class_of(args)
     seg = Segmentation(n_channels=1, n_class=nc, norm_type=1)
     vae = VAE(n_channels=nc, n_class=nc, norm_type=1, dim=128, spatial=args.size)
-    return Joint(models=[seg, vae], vae_forward_scale=getattr(args, "vae_forward_scale", 0.0),                 # main_target.py:324
-                 vae_decoder_dropout=getattr(args, "vae_decoder_dropout", 0.0), seg_dropout=getattr(args, "seg_dropout", 0.0))
+    return Joint(models=[seg, vae], vae_forward_scale=args.vae_forward_scale,                 # main_target.py:324
+                 vae_decoder_dropout=args.vae_decoder_dropout, seg_dropout=args.seg_dropout)
 
 
 def freeze(module):
@@ -234,12 +234,10 @@ def load_prefix(module, prefix, name="best_model.ckpt"):
 
 def make_optimizer(args, groups):
     """--adam / --momentum / --weight_decay / --nesterov / --grad_clip; without them the reference's SGD(momentum 0.9) or Adam, launched as it always was"""
-    max_norm = getattr(args, "grad_clip", 0.0) or None                 # 0 = off
-    wd = getattr(args, "weight_decay", 0.0)
-    if getattr(args, "adam", False):
-        return optim.Adam(groups, lr=args.lr_seg, betas=(0.9, 0.999), weight_decay=wd, max_norm=max_norm)
-    return optim.SGD(groups, lr=args.lr_seg, momentum=getattr(args, "momentum", 0.9), weight_decay=wd,
-                     nesterov=bool(getattr(args, "nesterov", False)), max_norm=max_norm)
+    max_norm = args.grad_clip or None                 # 0 = off
+    if args.adam:
+        return optim.Adam(groups, lr=args.lr_seg, betas=(0.9, 0.999), weight_decay=args.weight_decay, max_norm=max_norm)
+    return optim.SGD(groups, lr=args.lr_seg, momentum=args.momentum, weight_decay=args.weight_decay, nesterov=bool(args.nesterov), max_norm=max_norm)
 
 
 def load_ds_heads(deep, prefix, name="best_model.ckpt"):
@@ -269,6 +267,92 @@ def save_checkpoint(prefix, epoch_label, model, optimizer, best, deep=None):
 # ----------------------------------------------------------------------------------------------------
 # validation (main_source.py:688-822): batch 1, hard Dice of the argmax prediction against the label
 # ----------------------------------------------------------------------------------------------------
+def _cleaned(hard, nc, keep_largest, min_component, closing, fill_holes):
+    """--val_closing / --val_fill_holes / --val_keep_largest: the hard prediction after evaluation.postprocess, or None with all three off"""
+    if not (keep_largest > 0 or closing > 0 or fill_holes):
+        return None
+    return postprocess(hard, closing=closing, fill_holes=fill_holes, keep_largest=keep_largest, min_size=min_component, lo_channel=min(1, nc - 1))
+
+
+def _log_options(log, tta, closing, fill_holes):
+    """what whole_<epoch>.json and fine_<epoch>.json say about the options that shaped their scores"""
+    if tta:
+        log["tta"] = list(tta)
+    if closing > 0 or fill_holes:
+        log["closing"], log["fill_holes"] = int(closing), bool(fill_holes)
+
+
+# the optional measurements of validate(): per case a collector, whose record stays on the device, and after the last case a reporter, which brings
+# the records to the host once, prints the summary line and fills the log dict
+def _surface_case(hard, unfiltered, gt, lo):
+    """-> (distances of the scored prediction, those of the unfiltered one or None when no clean-up is on)"""
+    raw = None if unfiltered is None else volume.surface_distances(unfiltered[:, lo:], gt[:, lo:])
+    return volume.surface_distances(hard[:, lo:], gt[:, lo:]), raw
+
+
+def _surface_report(surf, surface_log):
+    for which, tag in ((0, ""), (1, " without the component filter")):
+        recs = {i: rec[which] for i, rec in surf.items() if rec[which] is not None}
+        if not recs:
+            continue
+        a, h = (torch.stack([recs[i][name].reshape(-1) for i in sorted(recs)]).cpu().numpy() for name in ("assd", "hd95"))     # one host copy per metric
+        undefined = int(np.isnan(a).sum())
+        if undefined == a.size:
+            print("validation surface distances%s: undefined in all %d entries (an empty surface)" % (tag, a.size))
+        else:
+            print("validation surface distances%s: ASSD %f, HD95 %f voxels (%d of %d case x class entries undefined)"
+                  % (tag, float(np.nanmean(a)), float(np.nanmean(h)), undefined, a.size))
+        if surface_log is not None:
+            suffix = "_unfiltered" if tag else ""
+            for row, i in enumerate(sorted(recs)):
+                entry = surface_log.setdefault(i, {})
+                entry["assd" + suffix] = [float(v) for v in a[row]]
+                entry["hd95" + suffix] = [float(v) for v in h[row]]
+
+
+def _lesion_case(hard, gt, lo, nc, min_component):
+    return (lesion_metrics(hard[:, lo:], gt[:, lo:], connectivity=26, min_size=int(min_component)),
+            confusion(hard.argmax(1, keepdim=True), gt.argmax(1, keepdim=True), nc))
+
+
+def _lesion_report(les, lesion_log, min_component):
+    for i in sorted(les):
+        rec, conf = les[i]
+        entry = {k: v[0] for k, v in lesion_record_to_host(rec).items()}                  # batch 1: lists over the foreground classes
+        assert tuple(entry) == LESION_RECORD_FIELDS
+        for name in CONFUSION_LOG_FIELDS:
+            entry[name] = conf[name.replace("class_", "")][0, 0].cpu().tolist()            # over all classes, background first
+        entry["confusion_overflow"] = int(conf["overflow"][0, 0])
+        lesion_log[i] = entry
+    tp, n_gt, fp = (sum(sum(lesion_log[i][k]) for i in lesion_log) for k in ("tp", "n_gt", "fp"))
+    print("validation lesions: %d of %d reference lesions detected, %d false detections (components of at least %d voxels)"
+          % (tp, n_gt, fp, max(int(min_component), 1)))
+
+
+def _intensity_case(image, pred, hard, gt, lo, nc, bins):
+    sides = {}
+    for name, hot in (("pred", hard), ("label", gt)):
+        rec = volume.histogram(image, bins, range=INTENSITY_RANGE, labels=hot.argmax(1, keepdim=True).to(torch.int32), rows=nc - 1)
+        sides[name] = (rec["table"][:, 0, lo:], rec["outside"][:, 0], hot[:, lo:].sum((2, 3, 4)))
+    return sides, torch.stack([mutual_information_3d(pred[:, k], gt[:, k]) for k in range(lo, nc)])
+
+
+def _intensity_report(inten, intensity_log, bins):
+    for i in sorted(inten):
+        sides, nmi = inten[i]
+        entry = {"bins": bins, "range": list(INTENSITY_RANGE)}
+        for name in ("pred", "label"):                                                     # batch 1: lists over the foreground classes
+            table, outside, voxels = sides[name]
+            entry[name + "_hist"] = table[0].cpu().tolist()
+            entry[name + "_voxels"] = [int(v) for v in voxels[0].cpu().tolist()]
+            entry[name + "_outside"] = int(outside[0])
+        entry["nmi"] = [float(v) for v in nmi.cpu().tolist()]
+        assert tuple(entry) == INTENSITY_LOG_FIELDS
+        intensity_log[i] = entry
+    print("validation intensities: %d-bin histograms of the image inside prediction and label, mean normalised mutual information of probability and "
+          "label %f" % (bins, float(np.mean([np.mean(intensity_log[i]["nmi"]) for i in intensity_log]))))
+
+
 @torch.no_grad()
 def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_dir=None, epoch=0, surface=False, surface_log=None, closing=0,
              fill_holes=False, lesion=False, lesion_log=None, intensity=0, intensity_log=None):
@@ -293,12 +377,9 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
     the label (ops.histogram with the class map as labels: one pass over the image per side), and the normalised mutual information of every foreground
     probability with its label channel (evaluation.mutual_information_3d) — on the device, brought to the host once after the last case; the per-case
     values go to the dict intensity_log (INTENSITY_LOG_FIELDS).  The returned scores are not affected, and with intensity 0 nothing of this is launched."""
-    from .evaluation import postprocess
-    les = {}
-    inten = {}
-    post = keep_largest > 0 or closing > 0 or fill_holes
-    scores, raw = {}, {}
-    surf, surf_raw = {}, {}
+    clean = (keep_largest, min_component, closing, fill_holes)
+    want_hard = surface or lesion or intensity > 0 or keep_largest > 0 or closing > 0 or fill_holes         # a measurement or a clean-up reads it
+    scores, raw, surf, les, inten = {}, {}, {}, {}, {}
     lo = min(1, nc - 1)
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
@@ -315,37 +396,19 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
         else:
             seg = model.Seg if hasattr(model, "Seg") else model
             pred = seg({IMG_KEY: batch[IMG_KEY].cuda(non_blocking=True)}, IMG_KEY, "pred")["pred"]
-        filtered = None
-        if post:
+        unfiltered = ops.hard_onehot(pred) if want_hard else None       # the one hard prediction of the case: clean-up and every measurement read it
+        filtered = _cleaned(unfiltered, nc, *clean) if want_hard else None
+        if filtered is not None:
             raw[i] = avg_dsc({"p": pred, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc)
-            filtered = postprocess(ops.hard_onehot(pred), closing=closing, fill_holes=fill_holes, keep_largest=keep_largest, min_size=min_component,
-                                   lo_channel=min(1, nc - 1))
-            scores[i] = avg_dsc({"p": filtered, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc).item()
-        else:
-            scores[i] = avg_dsc({"p": pred, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc).item()
+        hard = unfiltered if filtered is None else filtered             # what is scored and measured
+        scores[i] = avg_dsc({"p": pred if filtered is None else filtered, "g": gt}, "p", "g", binary=True, botindex=1, topindex=nc).item()
         if surface:
-            hard = ops.hard_onehot(pred)
-            if filtered is not None:
-                surf_raw[i] = volume.surface_distances(hard[:, lo:], gt[:, lo:])
-                hard = filtered
-            surf[i] = volume.surface_distances(hard[:, lo:], gt[:, lo:])
-        if lesion and method != "discriminator_train":
-            from .evaluation import confusion, lesion_metrics
-            hard = filtered if filtered is not None else ops.hard_onehot(pred)
-            les[i] = (lesion_metrics(hard[:, lo:], gt[:, lo:], connectivity=26, min_size=int(min_component)),
-                      confusion(hard.argmax(1, keepdim=True), gt.argmax(1, keepdim=True), nc))
-        if intensity > 0 and method != "discriminator_train":
-            from .evaluation import mutual_information_3d
-            hard = filtered if filtered is not None else ops.hard_onehot(pred)
-            image = batch[IMG_KEY].cuda(non_blocking=True).float()[:, :1].contiguous()
-            sides = {}
-            for name, hot in (("pred", hard), ("label", gt)):
-                rec = volume.histogram(image, int(intensity), range=INTENSITY_RANGE, labels=hot.argmax(1, keepdim=True).to(torch.int32), rows=nc - 1)
-                sides[name] = (rec["table"][:, 0, lo:], rec["outside"][:, 0], hot[:, lo:].sum((2, 3, 4)))
-            nmi = torch.stack([mutual_information_3d(pred[:, k], gt[:, k]) for k in range(lo, nc)])
-            inten[i] = (sides, nmi)
+            surf[i] = _surface_case(hard, unfiltered if filtered is not None else None, gt, lo)
+        if lesion:
+            les[i] = _lesion_case(hard, gt, lo, nc, min_component)
+        if intensity > 0:
+            inten[i] = _intensity_case(batch[IMG_KEY].cuda(non_blocking=True).float()[:, :1].contiguous(), pred, hard, gt, lo, nc, int(intensity))
         if save_dir is not None:
-            from .evaluation import binarize
             stem = os.path.join(save_dir, "%d_%d_" % (epoch, i))
             np.save(stem + "pred.join", binarize(pred).cpu().numpy())
             np.save(stem + "pic", batch[IMG_KEY].cpu().numpy())
@@ -357,52 +420,11 @@ def validate(method, model, loader, nc, keep_largest=0, min_component=0, save_di
               % (float(np.mean([v.item() for v in raw.values()])), keep_largest, min_component,
                  ", after closing %d and hole filling %s" % (closing, "on" if fill_holes else "off") if closing > 0 or fill_holes else ""))
     if surf:
-        def table(recs, name):                                   # one host copy per metric, after the last case
-            return torch.stack([recs[i][name].reshape(-1) for i in sorted(recs)]).cpu().numpy()
-        for recs, tag in ((surf, ""), (surf_raw, " without the component filter")):
-            if not recs:
-                continue
-            a, h = table(recs, "assd"), table(recs, "hd95")
-            undefined = int(np.isnan(a).sum())
-            if undefined == a.size:
-                print("validation surface distances%s: undefined in all %d entries (an empty surface)" % (tag, a.size))
-            else:
-                print("validation surface distances%s: ASSD %f, HD95 %f voxels (%d of %d case x class entries undefined)"
-                      % (tag, float(np.nanmean(a)), float(np.nanmean(h)), undefined, a.size))
-            if surface_log is not None:
-                suffix = "_unfiltered" if tag else ""
-                for row, i in enumerate(sorted(recs)):
-                    entry = surface_log.setdefault(i, {})
-                    entry["assd" + suffix] = [float(v) for v in a[row]]
-                    entry["hd95" + suffix] = [float(v) for v in h[row]]
+        _surface_report(surf, surface_log)
     if les and lesion_log is not None:
-        from .evaluation import LESION_RECORD_FIELDS, lesion_record_to_host
-        for i in sorted(les):
-            rec, conf = les[i]
-            entry = {k: v[0] for k, v in lesion_record_to_host(rec).items()}                  # batch 1: lists over the foreground classes
-            assert tuple(entry) == LESION_RECORD_FIELDS
-            for name in CONFUSION_LOG_FIELDS:
-                entry[name] = conf[name.replace("class_", "")][0, 0].cpu().tolist()            # over all classes, background first
-            entry["confusion_overflow"] = int(conf["overflow"][0, 0])
-            lesion_log[i] = entry
-        tp, n_gt = (sum(sum(lesion_log[i][k]) for i in lesion_log) for k in ("tp", "n_gt"))
-        fp = sum(sum(lesion_log[i]["fp"]) for i in lesion_log)
-        print("validation lesions: %d of %d reference lesions detected, %d false detections (components of at least %d voxels)"
-              % (tp, n_gt, fp, max(int(min_component), 1)))
+        _lesion_report(les, lesion_log, min_component)
     if inten and intensity_log is not None:
-        for i in sorted(inten):
-            sides, nmi = inten[i]
-            entry = {"bins": int(intensity), "range": list(INTENSITY_RANGE)}
-            for name in ("pred", "label"):                                                     # batch 1: lists over the foreground classes
-                table, outside, voxels = sides[name]
-                entry[name + "_hist"] = table[0].cpu().tolist()
-                entry[name + "_voxels"] = [int(v) for v in voxels[0].cpu().tolist()]
-                entry[name + "_outside"] = int(outside[0])
-            entry["nmi"] = [float(v) for v in nmi.cpu().tolist()]
-            assert tuple(entry) == INTENSITY_LOG_FIELDS
-            intensity_log[i] = entry
-        print("validation intensities: %d-bin histograms of the image inside prediction and label, mean normalised mutual information of probability and "
-              "label %f" % (int(intensity), float(np.mean([np.mean(intensity_log[i]["nmi"]) for i in intensity_log]))))
+        _intensity_report(inten, intensity_log, int(intensity))
     return scores
 
 
@@ -454,8 +476,6 @@ def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="
     The codes are then recorded as log["tta"].
     closing / fill_holes (--val_closing, --val_fill_holes): evaluation.postprocess cleans the sliding-window prediction up before dice_whole — closing, hole
     filling, then the component filter if it is on; recorded as log["closing"] / log["fill_holes"] when set."""
-    from . import data_gpu
-    from .evaluation import localise, postprocess, segmentation_model_fn, sliding_window_predict, tta_flips
     tta = tta_flips(tta)
     seg = model.Seg if hasattr(model, "Seg") else model
     model_fn = segmentation_model_fn(seg)
@@ -468,10 +488,9 @@ def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="
         if res["prob"].shape[0] != nc:
             raise ValueError("whole-volume validation: the network predicts %d classes, the labels have %d" % (res["prob"].shape[0], nc))
         hard = ops.hard_onehot(res["prob"][None])
-        if keep_largest > 0 or closing > 0 or fill_holes:
-            hard = postprocess(hard, closing=closing, fill_holes=fill_holes, keep_largest=keep_largest, min_size=min_component, lo_channel=lo)
+        cleaned = _cleaned(hard, nc, keep_largest, min_component, closing, fill_holes)
         gt = ops.onehot(lab[None, None], nc)
-        whole[i] = _hard_dice(hard[0], gt[0], lo, nc)
+        whole[i] = _hard_dice((hard if cleaned is None else cleaned)[0], gt[0], lo, nc)
         mask = localise(res["prob"], keep_largest=max(keep_largest, 1), min_size=min_component, lo_channel=lo)
         if data_gpu.bounding_box(mask) is None:
             free[i] = torch.zeros((), device=img.device)
@@ -488,10 +507,7 @@ def validate_whole_volume(model, cases, nc, patch, overlap=0.5, batch=1, blend="
     if log is not None:
         for i in w:
             log[i] = {"dice_whole": w[i], "dice_label_free": f[i]}
-        if tta:
-            log["tta"] = list(tta)
-        if closing > 0 or fill_holes:
-            log["closing"], log["fill_holes"] = int(closing), bool(fill_holes)
+        _log_options(log, tta, closing, fill_holes)
     return mw, mf
 
 
@@ -507,7 +523,6 @@ def validate_fine_whole(model, cases, nc, patch, overlap=0.5, batch=1, blend="ga
     closing / fill_holes (--val_closing, --val_fill_holes): evaluation.postprocess cleans the pasted label up before it is scored and saved — closing, hole
     filling, then the component filter if it is on; recorded as log["closing"] / log["fill_holes"] when set.
     -> mean dice_fine_whole"""
-    from .evaluation import coarse_to_fine_predict, postprocess, tta_flips
     tta = tta_flips(tta)
     seg = model.Seg if hasattr(model, "Seg") else model
     lo = min(1, nc - 1)
@@ -519,9 +534,9 @@ def validate_fine_whole(model, cases, nc, patch, overlap=0.5, batch=1, blend="ga
                                      interp=interp, tta=tta)
         label = res["label"]
         hard = ops.onehot(label.float()[None, None], nc)
-        if keep_largest > 0 or closing > 0 or fill_holes:
-            hard = postprocess(hard, closing=closing, fill_holes=fill_holes, keep_largest=keep_largest, min_size=min_component, lo_channel=lo)
-            label = hard[0].argmax(0).to(torch.uint8)
+        cleaned = _cleaned(hard, nc, keep_largest, min_component, closing, fill_holes)
+        if cleaned is not None:
+            hard, label = cleaned, cleaned[0].argmax(0).to(torch.uint8)
         fine[i] = _hard_dice(hard[0], ops.onehot(lab[None, None], nc)[0], lo, nc)
         found[i] = bool(res["found"])
         if save_dir is not None:
@@ -534,79 +549,69 @@ def validate_fine_whole(model, cases, nc, patch, overlap=0.5, batch=1, blend="ga
     if log is not None:
         for i in f:
             log[i] = {"dice_fine_whole": f[i]}
-        if tta:
-            log["tta"] = list(tta)
-        if closing > 0 or fill_holes:
-            log["closing"], log["fill_holes"] = int(closing), bool(fill_holes)
+        _log_options(log, tta, closing, fill_holes)
     return mean
+
+
+def _need(script, cond, what):
+    """the reference asserts its flag combinations; `python -O` strips asserts, an entry point must not"""
+    if not cond:
+        raise SystemExit("%s: inconsistent flags — %s" % (script, what))
 
 
 def check_fine_whole_flags(a, script="main_source.py"):
     """--val_fine_whole rides on the whole-volume pass; --save_whole_pred saves what --val_fine_whole makes"""
-    def need(cond, what):
-        if not cond:
-            raise SystemExit("%s: inconsistent flags — %s" % (script, what))
-    if getattr(a, "val_fine_whole", False):
-        need(getattr(a, "val_whole_volume", False), "--val_fine_whole scores the fine pass of the whole-volume chain: it needs --val_whole_volume")
-    if getattr(a, "save_whole_pred", None):
-        need(getattr(a, "val_fine_whole", False), "--save_whole_pred writes the labels that --val_fine_whole pastes: it needs --val_fine_whole")
+    if a.val_fine_whole:
+        _need(script, a.val_whole_volume, "--val_fine_whole scores the fine pass of the whole-volume chain: it needs --val_whole_volume")
+    if a.save_whole_pred:
+        _need(script, a.val_fine_whole, "--save_whole_pred writes the labels that --val_fine_whole pastes: it needs --val_fine_whole")
 
 
 def check_lesion_flags(a, script="main_source.py"):
     """--val_lesion scores the objects of the prediction validation already makes: it needs a validation pass that makes one"""
-    def need(cond, what):
-        if not cond:
-            raise SystemExit("%s: inconsistent flags — %s" % (script, what))
-    if not getattr(a, "val_lesion", False):
+    if not a.val_lesion:
         return
-    need(a.method != "discriminator_train", "--val_lesion scores a segmentation, --method discriminator_train predicts none")
-    need(not getattr(a, "val_finetune", 0), "--val_lesion rides on the plain validation pass: it cannot be combined with --val_finetune")
-    need(getattr(a, "val_min_component", 0) >= 0, "--val_min_component is a number of voxels: it cannot be negative")
+    _need(script, a.method != "discriminator_train", "--val_lesion scores a segmentation, --method discriminator_train predicts none")
+    _need(script, not a.val_finetune, "--val_lesion rides on the plain validation pass: it cannot be combined with --val_finetune")
+    _need(script, a.val_min_component >= 0, "--val_min_component is a number of voxels: it cannot be negative")
 
 
 def check_intensity_flags(a, script="main_source.py"):
     """--val_intensity reads the image inside the prediction validation already makes: it needs a validation pass that makes one"""
-    def need(cond, what):
-        if not cond:
-            raise SystemExit("%s: inconsistent flags — %s" % (script, what))
-    bins = getattr(a, "val_intensity", 0)
-    if not bins:
+    if not a.val_intensity:
         return
-    need(1 <= bins <= volume.HISTOGRAM_MAX_BINS, "--val_intensity is a number of bins between 1 and %d" % volume.HISTOGRAM_MAX_BINS)
-    need(a.method != "discriminator_train", "--val_intensity reads the image inside a segmentation, --method discriminator_train predicts none")
-    need(not getattr(a, "val_finetune", 0), "--val_intensity rides on the plain validation pass: it cannot be combined with --val_finetune")
+    _need(script, 1 <= a.val_intensity <= volume.HISTOGRAM_MAX_BINS, "--val_intensity is a number of bins between 1 and %d" % volume.HISTOGRAM_MAX_BINS)
+    _need(script, a.method != "discriminator_train", "--val_intensity reads the image inside a segmentation, --method discriminator_train predicts none")
+    _need(script, not a.val_finetune, "--val_intensity rides on the plain validation pass: it cannot be combined with --val_finetune")
 
 
 def check_whole_volume_flags(a, script="main_source.py"):
     """--val_whole_volume reads whole cases from disk and needs a segmentation network; --val_tta augments its sliding-window passes;
     --val_closing counts iterations"""
-    def need(cond, what):
-        if not cond:
-            raise SystemExit("%s: inconsistent flags — %s" % (script, what))
-    need(getattr(a, "val_closing", 0) >= 0, "--val_closing is a number of closing iterations: it cannot be negative")
-    if getattr(a, "val_tta", None):
-        need(getattr(a, "val_whole_volume", False), "--val_tta mirrors the windows of the whole-volume chain: it needs --val_whole_volume")
-        from .evaluation import tta_flips
+    _need(script, a.val_closing >= 0, "--val_closing is a number of closing iterations: it cannot be negative")
+    if a.val_tta:
+        _need(script, a.val_whole_volume, "--val_tta mirrors the windows of the whole-volume chain: it needs --val_whole_volume")
         try:
             tta_flips(a.val_tta)
         except ValueError as e:
-            need(False, "--val_tta: %s" % e)
-    if not getattr(a, "val_whole_volume", False):
+            _need(script, False, "--val_tta: %s" % e)
+    if not a.val_whole_volume:
         return
-    need(getattr(a, "real_data", False), "--val_whole_volume predicts whole merge.npy cases: it needs --real_data")
-    need(a.method not in ("vae_train", "discriminator_train", "embed_train", "refine_vae"), "--val_whole_volume needs a segmentation network, --method %s has none" % a.method)
-    need(0.0 <= a.sw_overlap < 1.0, "--sw_overlap must be in [0, 1)")
-    need(a.sw_batch >= 1, "--sw_batch must be at least 1")
+    _need(script, a.real_data, "--val_whole_volume predicts whole merge.npy cases: it needs --real_data")
+    _need(script, a.method not in ("vae_train", "discriminator_train", "embed_train", "refine_vae"),
+          "--val_whole_volume needs a segmentation network, --method %s has none" % a.method)
+    _need(script, 0.0 <= a.sw_overlap < 1.0, "--sw_overlap must be in [0, 1)")
+    _need(script, a.sw_batch >= 1, "--sw_batch must be at least 1")
+
 
 
 # ----------------------------------------------------------------------------------------------------
 # the loop
 # ----------------------------------------------------------------------------------------------------
-def run(args, side="source"):
-    check_fine_whole_flags(args, "main_%s.py" % side)
-    check_whole_volume_flags(args, "main_%s.py" % side)
-    check_lesion_flags(args, "main_%s.py" % side)
-    check_intensity_flags(args, "main_%s.py" % side)
+def start_process(args, side):
+    """the flag checks — ahead of the GPU check: they need no device — then this process's place among the ranks -> (rank, world)"""
+    for check in (check_fine_whole_flags, check_whole_volume_flags, check_lesion_flags, check_intensity_flags):
+        check(args, "main_%s.py" % side)
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if not torch.cuda.is_available():
         raise SystemExit("the native kernels need a GPU (there is no CPU path)")
@@ -616,40 +621,41 @@ def run(args, side="source"):
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     if args.save_epoch % args.eval_epoch != 0:                            # main_source.py asserts this; an assert would vanish under python -O
         raise SystemExit("--save_epoch must be a multiple of --eval_epoch")
-    nc = n_class_of(args)
-    method = args.method
-    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
-    eps = EPS_MAIN_SOURCE if side == "source" else EPS_EVALUATION          # the two scripts use different epsilons
+    return rank, world
 
-    teacher = None
+
+def build_models(args, nc):
+    """-> (model, the part of it that trains, the teacher or None) of --method, on the host and as initialised"""
+    method, teacher = args.method, None
     if method == "vae_train":
         model = VAE(n_channels=nc, n_class=nc, norm_type=1, dim=128, soft=bool(args.softrelu), spatial=args.size)
-        trainable = model
     elif method == "seg_train":
         model = Segmentation(n_channels=1, n_class=nc, norm_type=1)
-        trainable = model
     elif method in ("joint_train", "domain_adaptation", "sep_joint_train"):
         model = build_joint(args)
-        trainable = model.Seg
-        if method in ("domain_adaptation", "sep_joint_train"):
+        if method != "joint_train":
             teacher = build_joint(args)                                     # main_target.py:323-328 / main_source.py:270-273 (tea_model)
     elif method in ("embed_train", "refine_vae"):                          # main_source.py:259-264
         model = Embed(models=[Encoder(n_channels=1, dim=128, norm_type=1, spatial=args.size),
                               VAE(n_channels=nc, n_class=nc, norm_type=1, dim=128, spatial=args.size),
                               Fusion(n_channels_img=1, n_channels_mask=nc, n_class=nc, norm_type=1)])
-        trainable = model
     elif method == "discriminator_train":                                  # main_target.py:318-319
         model = Encoder(n_channels=1, dim=1, norm_type=1, spatial=args.size)
-        trainable = model
     elif method == "domain_adaptation_dis":                                # main_target.py:337-342
         model = Joint2(models=[Segmentation(n_channels=1, n_class=nc, norm_type=1), Encoder(n_channels=1, dim=1, norm_type=1, spatial=args.size)],
-                       seg_dropout=getattr(args, "seg_dropout", 0.0))
-        trainable = model.Seg
+                       seg_dropout=args.seg_dropout)
         teacher = Segmentation(n_channels=1, n_class=nc, norm_type=1)
     else:
         raise ValueError("Try a valid method.")                           # main_source.py:275 / main_target.py:343
+    return model, (model.Seg if isinstance(model, (Joint, Joint2)) else model), teacher
+
+
+def load_and_freeze(args, model, trainable, teacher, dtype):
+    """the checkpoints of --load_prefix*, the frozen sub-networks, the teacher's weights -> (model, trainable, teacher) on the device:
+    --only_pseudo swaps model and teacher"""
+    method = args.method
     model = model.cuda()
-    from_scratch = bool(getattr(args, "from_scratch", False)) and method == "domain_adaptation"
+    from_scratch = bool(args.from_scratch) and method == "domain_adaptation"
     if from_scratch:
         teacher = teacher.cuda()
     if args.load_prefix:                                                    # main_target.py:355-366: --from_scratch loads the TEACHER's Seg, the student keeps its initialisation
@@ -659,7 +665,7 @@ def run(args, side="source"):
         if from_scratch:
             load_prefix(teacher.Vae, args.load_prefix_vae)                  # :370-371
         load_prefix(model.Vae, args.load_prefix_vae)
-    if getattr(args, "load_prefix_encoder", None):                          # :384-390
+    if args.load_prefix_encoder:                                            # :384-390
         if method == "discriminator_train":
             load_prefix(model, args.load_prefix_encoder)
         elif hasattr(model, "Dis"):
@@ -668,7 +674,7 @@ def run(args, side="source"):
         load_prefix(model, args.load_prefix_joint, args.checkpoint_name)
     if hasattr(model, "Vae") and method != "refine_vae":
         freeze(model.Vae)                                                   # main_source.py:343-346
-    if getattr(args, "fix_layer", False) and method in ("joint_train", "domain_adaptation"):     # main_target.py:400-406: only the last decoder block and the head train
+    if args.fix_layer and method in ("joint_train", "domain_adaptation"):   # main_target.py:400-406: only the last decoder block and the head train
         for prm in model.Seg.parameters():
             prm.requires_grad = False
         for prm in list(model.Seg.up5.parameters()) + list(model.Seg.out_block.parameters()):
@@ -680,37 +686,33 @@ def run(args, side="source"):
             prm.requires_grad = False
     if method == "domain_adaptation_dis":
         freeze(model.Dis)                                                   # main_target.py:407-411
-    if teacher is not None and method in ("sep_joint_train", "domain_adaptation_dis"):
+    if teacher is not None:
         teacher = teacher.cuda()
-        teacher.load_state_dict(model.state_dict() if method == "sep_joint_train" else model.Seg.state_dict())   # main_source.py:330-340 / main_target.py:366
-        freeze(teacher)
-        set_kernel_dtype(teacher, dtype)
-    elif teacher is not None:
-        teacher = teacher.cuda()
-        if getattr(args, "only_pseudo", False):
+        if method in ("sep_joint_train", "domain_adaptation_dis"):
+            teacher.load_state_dict(model.state_dict() if method == "sep_joint_train" else model.Seg.state_dict())   # main_source.py:330-340 / main_target.py:366
+        elif args.only_pseudo:
             # main_target.py:421-425: the loaded network becomes the frozen pseudo-label teacher, a freshly initialised one is trained
             model, teacher = teacher, model
             freeze(model.Vae)
             trainable = model.Seg
-        elif not args.test_only and from_scratch:
-            pass                                                            # main_target.py:427: the teacher keeps what --load_prefix* gave it
-        elif not args.test_only:
-            teacher.load_state_dict(model.state_dict())                     # main_target.py:426-427
-        else:
-            teacher.load_state_dict(model.state_dict())                     # main_target.py:379-380
+        elif args.test_only or not from_scratch:                            # main_target.py:427: a --from_scratch teacher keeps what --load_prefix* gave it
+            teacher.load_state_dict(model.state_dict())                     # main_target.py:426-427 / :379-380
         freeze(teacher)
         set_kernel_dtype(teacher, dtype)
     set_kernel_dtype(model, dtype)
-    from . import modules as _modules
-    _modules.set_recompute(bool(getattr(args, "recompute", False)))
+    set_recompute(bool(args.recompute))
+    return model, trainable, teacher
 
+
+def build_optimizer(args, model, trainable, teacher, world):
+    """-> (the --deep_supervision heads or None, optimizer, the step's live parameters, the gradient all-reduce or None); under torchrun every replica
+    leaves with rank 0's tensors"""
     deep = None                                                             # --deep_supervision L: auxiliary heads on the decoder's coarse levels (DESIGN 3.21)
-    if getattr(args, "deep_supervision", 0) and method in SEG_LOSS_METHODS:
-        deep = _modules.DeepSupervision(trainable, args.deep_supervision).cuda()
-        resumed = args.load_prefix if method == "seg_train" else (args.load_prefix_joint or args.load_prefix)
+    if args.deep_supervision and args.method in SEG_LOSS_METHODS:
+        deep = DeepSupervision(trainable, args.deep_supervision).cuda()
+        resumed = args.load_prefix if args.method == "seg_train" else (args.load_prefix_joint or args.load_prefix)
         if resumed:
             load_ds_heads(deep, resumed, args.checkpoint_name)
-
     if hasattr(model, "Seg") and hasattr(model, "Vae"):
         groups = [{"params": list(model.Seg.parameters()), "lr": args.lr_seg, "model": "Seg"},
                   {"params": list(model.Vae.parameters()), "lr": args.lr_vae, "model": "Vae"}]
@@ -722,293 +724,333 @@ def run(args, side="source"):
     params = [p for p in trainable.parameters() if p.requires_grad]
     if deep is not None:
         params += list(deep.parameters())
-    sync = ddp.FlatGradSync(params) if world > 1 else None
-    if sync is not None:
-        sync.broadcast_parameters(0)
-        # the trainable list is not the whole replica: frozen or freshly initialised layers (--fix_layer, --from_scratch, a VAE without a checkpoint) and
-        # the teacher must agree across ranks too, or the replicas differ from the first forward on
-        seen = {id(p) for p in params}
-        for mod in (model, teacher):
-            if mod is None:
-                continue
-            for t in list(mod.parameters()) + list(mod.buffers()):
-                if id(t) not in seen and t.is_cuda:
-                    seen.add(id(t))
-                    dist.broadcast(t.data, 0)
-        ddp.note_eager_collective()
-        ops.weights_changed()
+    if world == 1:
+        return deep, optimizer, params, None
+    sync = ddp.FlatGradSync(params)
+    sync.broadcast_parameters(0)
+    # the trainable list is not the whole replica: frozen or freshly initialised layers (--fix_layer, --from_scratch, a VAE without a checkpoint) and
+    # the teacher must agree across ranks too, or the replicas differ from the first forward on
+    seen = {id(p) for p in params}
+    for mod in (model, teacher):
+        if mod is None:
+            continue
+        for t in list(mod.parameters()) + list(mod.buffers()):
+            if id(t) not in seen and t.is_cuda:
+                seen.add(id(t))
+                dist.broadcast(t.data, 0)
+    ddp.note_eager_collective()
+    ops.weights_changed()
+    return deep, optimizer, params, sync
+
+
+def loss_key(args, method, epoch):
+    """what of the loss expression depends on the epoch (main_target.py:583-592): a captured step is rebuilt when it changes"""
+    if method == "domain_adaptation_dis":                               # main_target.py:720-723: lambda ramps with the epoch during the warm-up
+        return min(epoch, args.lambda_vae_warmup)
+    if method == "embed_train":                                         # the Encoder's requires_grad follows the epoch's parity: another live parameter set
+        return epoch % 2
+    if method != "domain_adaptation" or args.domain_loss_type != 0 or args.only_pseudo:
+        return 0
+    if args.turn_epoch != -1:
+        return (epoch // args.turn_epoch) % 2
+    return min(epoch, args.lambda_vae_warmup)
+
+
+def _monte_carlo(draw, n):
+    """main_target.py:530-603 (--vae_mont_number N): N forward passes of student and teacher per step (they differ by their dropout draws),
+    the four loss terms averaged, one backward through all of them"""
+    final, aux = draw()
+    if n == 1:
+        return final, aux
+    tot = {k: v for k, v in aux.items() if k != "batch" and k != "kl_loss"}
+    for _ in range(n - 1):
+        f, aux = draw()
+        final = final + f
+        tot = {k: tot[k] + aux[k] for k in tot}
+    out = {k: v / n for k, v in tot.items()}
+    out["kl_loss"], out["batch"] = aux["kl_loss"], aux["batch"]             # the reference logs the LAST pass's KL (:605)
+    return final / n, out
+
+
+class TrainState:
+    """What a training step reads and the loop changes under it.  loss() is the step's loss expression — what a train.GraphedStep captures — so a
+    capture bakes in lambda_vae, the epoch-dependent branch (loss_key) and the live parameter list; whoever changes one of them sets stepper_key
+    to None, and the step is captured again before it next runs."""
+
+    def __init__(self, args, side, nc, rank, model, trainable, teacher, deep, optimizer, params, sync, scaler, pseudo_loader):
+        self.args, self.method, self.nc, self.rank = args, args.method, nc, rank
+        self.eps = EPS_MAIN_SOURCE if side == "source" else EPS_EVALUATION          # SURVEY F6: the two scripts use different epsilons
+        self.model, self.trainable, self.teacher, self.optimizer, self.sync, self.scaler = model, trainable, teacher, optimizer, sync, scaler
+        self.base_lrs = [grp["lr"] for grp in optimizer.param_groups]
+        self.n_outer = max(1, args.max_epoch // args.eval_epoch)
+        self.epoch, self.lambda_vae, self.params = 0, args.lambda_vae, params
+        self.stepper, self.stepper_key = None, None
+        self.pseudo_loader, self.pseudo_itr, self.pseudo_cycles = pseudo_loader, None, 0
+        bs, s = args.batch_size, args.size
+        self.img = torch.zeros(bs, 1, s, s, s, device="cuda")               # fixed-address inputs of the captured step
+        self.lab = torch.zeros(bs, 1, s, s, s, device="cuda")
+        self.score = torch.zeros(bs, 1, device="cuda")                      # discriminator_train's regression target (venous_score)
+        self.pimg = self.plab = None                                        # the logged-only pseudo-labelled batch, made on first use
+        self.use_graph = not args.no_graph and not (args.seg_dropout or args.vae_decoder_dropout)   # dropout draws fresh masks per call: eager (train.GraphedStep)
+        # the sampling methods draw VAE noise per call.  --latent_noise torch (the default): torch.randn, launched eagerly.  --latent_noise philox: one
+        # ops.LatentStream per rank, drawn inside the forward launch from a device-resident counter, so the step is captured like every other method's;
+        # embed_train's requires_grad toggle by epoch parity rebuilds the captured step (loss_key)
+        self.latent = None
+        if self.method in ("embed_train", "refine_vae", "vae_train"):
+            if args.latent_noise == "philox":
+                # 1000 rank + 700: the loaders' per-rank Philox streams are seeded base + 1000 rank (+ 500) with their own fixed bases; this one's base is 0
+                # (the entry points have no --seed flag)
+                self.latent = ops.LatentStream(1000 * rank + 700)
+            else:
+                self.use_graph = False
+        self.seg_loss = seg_loss_of(args)                                   # --seg_loss dice_ce: ops.seg_loss's arguments; None: the reference's Dice
+        self.seg_kw = {} if deep is None else {"deep": deep}
+        # --boundary_weight: the boundary term's weight is ONE device scalar, refilled at the top of every outer epoch (train.boundary_weight): the captured
+        # launches read it, so the ramp needs no re-capture.  With the flags at their defaults nothing is built and loss() passes nothing on
+        self.boundary_w = None
+        if boundary_enabled(args) and self.method in SEG_LOSS_METHODS and self.seg_loss is not None:
+            self.boundary_w = torch.zeros((), dtype=torch.float32, device="cuda")
+            self.seg_kw["boundary"] = {"weight": self.boundary_w, "spacing": None}
+
+    def loss(self):
+        a, m, model, teacher, img, lab = self.args, self.method, self.model, self.teacher, self.img, self.lab
+        kw = {"eps": self.eps, "n_class": self.nc}
+        if m == "vae_train":
+            return T.vae_train_losses(model, lab, scale=0.35, noise=self.latent, **kw)
+        if m == "seg_train":
+            return T.seg_train_losses(model, img, lab, loss=self.seg_loss, **kw, **self.seg_kw)
+        if m == "joint_train":
+            return T.joint_train_losses(model, img, lab, lambda_vae=self.lambda_vae, loss=self.seg_loss, **kw, **self.seg_kw)
+        if m == "sep_joint_train":
+            return T.sep_joint_train_losses(model, teacher, img, lab, **kw)
+        if m in ("embed_train", "refine_vae"):
+            return (T.embed_train_losses if m == "embed_train" else T.refine_vae_losses)(model, img, lab, noise=self.latent, **kw)
+        if m == "discriminator_train":
+            return T.discriminator_train_loss(model, lab, self.score)
+        kw.update(lambda_vae=self.lambda_vae, use_confident_binarize=a.use_confident_binarize)
+        if m == "domain_adaptation_dis":
+            return T.domain_adaptation_dis_losses(model, teacher, img, lab, epoch=self.epoch, lambda_vae_warmup=a.lambda_vae_warmup, **kw)
+        if self.pseudo_loader is not None:                                  # main_target.py:615-661: a --pseudo_list run has its own loss ladder
+            return T.domain_adaptation_pseudo_losses(model, teacher, img, lab, domain_loss_type=a.domain_loss_type, host_schedule=not self.use_graph, **kw)
+        return _monte_carlo(lambda: T.domain_adaptation_losses(model, teacher, img, lab, domain_loss_type=a.domain_loss_type, kl=a.kl,
+                                                               only_pseudo=a.only_pseudo, epoch=self.epoch, turn_epoch=a.turn_epoch,
+                                                               lambda_vae_warmup=a.lambda_vae_warmup, host_schedule=not self.use_graph, **kw),
+                            max(1, int(a.vae_mont_number)))
+
+    def begin_epoch(self, epoch):
+        a = self.args
+        self.epoch = epoch
+        if a.lr_schedule == "poly":                                         # a captured step follows through sync_hyper(): no re-capture
+            for grp, base in zip(self.optimizer.param_groups, self.base_lrs):
+                grp["lr"] = optim.poly_lr(base, epoch, self.n_outer, a.poly_power)
+        if self.boundary_w is not None:                                     # likewise: the captured launches read the scalar
+            self.boundary_w.fill_(T.boundary_weight(epoch, a.boundary_weight, a.boundary_ramp, a.boundary_max))
+        if self.method == "embed_train":                                    # main_source.py:550-554: the image encoder trains on odd epochs only
+            for prm in self.model.Encoder.parameters():
+                prm.requires_grad = epoch % 2 == 1
+            self.params = [p for p in self.trainable.parameters() if p.requires_grad]
+
+    def zero_grads(self):
+        """optimizer.zero_grad() over ALL parameters, as the reference does every iteration (main_source.py:660): a GraphedStep drops the gradients of
+        ITS parameters only, and an eager optimiser tail steps every parameter that holds one — a parameter frozen for this epoch (embed_train's
+        Encoder on even epochs) must not keep the gradient its last trained step, or the previous capture's last replay, left it"""
+        for grp in self.optimizer.param_groups:
+            for p in grp["params"]:
+                p.grad = None
+
+    def divide_lambda(self):
+        """--tag (main_target.py:635,712): ahead of this iteration's loss; lambda is baked into a captured loss expression"""
+        self.lambda_vae /= 10
+        self.stepper_key = None
+
+    def capture(self, zero_grads=False):
+        self.stepper = None                                                 # release the old capture's memory pool first
+        if zero_grads:
+            self.zero_grads()
+        self.stepper = T.GraphedStep(self.loss, self.params, self.optimizer, grad_sync=self.sync, warmup=1, scaler=self.scaler)
+        self.stepper_key = loss_key(self.args, self.method, self.epoch)
+
+    def step(self):
+        """one optimiser step on what the input buffers hold -> the step's aux dict"""
+        if self.stepper is not None:
+            self.stepper.step()
+            return self.stepper.aux
+        self.zero_grads()
+        loss, aux = self.loss()
+        if self.scaler is not None:
+            loss.backward(gradient=self.scaler.seed)
+        else:
+            loss.backward()
+        skw = {} if self.scaler is None else {"scaler": self.scaler}
+        if self.sync is not None:
+            self.sync()
+            self.optimizer.step_with(*self.sync.live(), **skw)
+        else:
+            self.optimizer.step(**skw)
+        return aux
+
+
+def _refresh_teacher(st, epoch, idx, n_iter):
+    """--pseudo_save_epoch: the three ways a pseudo-label network follows its student, ahead of the iteration's step -> the weights to load into the
+    teacher AFTER the step, or None"""
+    a, model, teacher = st.args, st.model, st.teacher
+    if not a.pseudo_save_epoch:
+        return None
+    due = epoch % a.pseudo_save_epoch == 0
+    if st.pseudo_loader is not None:
+        if due:
+            # main_target.py:633-635 (--pseudo_list runs): the pseudo-label network is re-loaded from the student AFTER this iteration's two forwards and
+            # BEFORE its optimizer step, i.e. the next iteration's pseudo-labels come from the weights this one started with: keep them, load after the step
+            with torch.no_grad():
+                teacher_next = {k: v.clone() for k, v in model.state_dict().items()}
+            if a.tag:
+                st.divide_lambda()
+            return teacher_next
+    elif st.method == "domain_adaptation":
+        # EMA teacher (main_target.py:508-518): every `pseudo_save_epoch` epochs, at the first iteration of an epoch slice or
+        # every iteration; never in epoch 0
+        every = max(1, a.pseudo_save_epoch // a.eval_epoch)
+        if epoch != 0 and epoch % every == 0 and (a.update_every_iteration or idx % max(1, n_iter // a.eval_epoch) == 0):
+            optim.ema_update(teacher.Seg, model.Seg, a.alpha)
+    elif st.method == "domain_adaptation_dis" and due:
+        # main_target.py:710-712: the pseudo-label network is re-loaded from the student (in place: a captured graph replays it)
+        _load_teacher(teacher, model.Seg.state_dict())
+        if a.tag:
+            st.divide_lambda()
+    return None
+
+
+def _load_teacher(teacher, state):
+    with torch.no_grad():
+        teacher.load_state_dict(state)                                      # in place: a captured graph replays the same storage
+    ops.clear_pack_cache()
+    ops.refresh_frozen_packs(teacher)
+
+
+def _pseudo_batch_losses(st):
+    """main_target.py:663-687: the next batch of the pseudo-labelled loader (cycled), student forward, two Dice terms — logged, never stepped on"""
+    pb = next(st.pseudo_itr, None) if st.pseudo_itr is not None else None
+    if pb is None:
+        st.pseudo_cycles += 1
+        if hasattr(st.pseudo_loader, "set_epoch"):
+            st.pseudo_loader.set_epoch(st.pseudo_cycles)                    # a DataLoader(shuffle=True) draws a new order per pass (main_target.py:299-307)
+        st.pseudo_itr = iter(st.pseudo_loader)
+        pb = next(st.pseudo_itr)
+    if st.pimg is None:
+        st.pimg, st.plab = torch.zeros_like(st.img), torch.zeros_like(st.lab)
+    st.pimg.copy_(pb[IMG_KEY], non_blocking=True)
+    st.plab.copy_(pb[LABEL_KEY], non_blocking=True)
+    return T.pseudo_batch_losses(st.model, st.pimg, st.plab, eps=st.eps, n_class=st.nc)
+
+
+def train_epoch(st, loader, epoch):
+    a, method, model, optimizer = st.args, st.method, st.model, st.optimizer
+    model.train()
+    if hasattr(model, "Vae"):
+        model.Vae.eval()
+    if st.use_graph and (st.stepper is None or st.stepper_key != loss_key(a, method, epoch)):
+        st.capture(zero_grads=True)
+        if st.rank == 0:
+            print("train step captured as a HIP graph (%s)" % ("2 graphs + bucketed all-reduce" if st.stepper.graph2 is not None else "1 graph"))
+    t0, seen = time.time(), 0
+    n_iter = len(loader)
+    for idx, batch in enumerate(loader):
+        st.img.copy_(batch[IMG_KEY], non_blocking=True)
+        st.lab.copy_(batch[LABEL_KEY], non_blocking=True)
+        if method == "discriminator_train":          # synthetic stand-in for the venous_score field: a function of the mask
+            st.score.copy_(batch[LABEL_KEY].float().mean((1, 2, 3, 4)).view(-1, 1) * 4, non_blocking=True)
+        teacher_next = _refresh_teacher(st, epoch, idx, n_iter)
+        if st.use_graph and st.stepper is not None and st.stepper_key is None:       # --tag divided lambda_vae: the step that follows already runs with it
+            st.capture()
+        aux = st.step()
+        if teacher_next is not None:
+            _load_teacher(st.teacher, teacher_next)
+        if st.pseudo_loader is not None:
+            aux = dict(aux, **_pseudo_batch_losses(st))
+        seen += a.batch_size
+        if st.rank == 0 and idx % a.display_freq == 0:              # logging syncs the host every display_freq steps only
+            parts = ", ".join("%s %.4f" % (k, v.item()) for k, v in aux.items() if k not in ("batch", "ds_losses"))
+            for lvl, (d_i, ce_i) in enumerate(aux.get("ds_losses", ()), 1):      # --deep_supervision: the coarse levels' terms
+                parts += ", ds%d_dice_loss %.4f, ds%d_ce_loss %.4f" % (lvl, d_i.item(), lvl, ce_i.item())
+            if optimizer.max_norm is not None and optimizer.grad_norm is not None:
+                parts += ", grad_norm %.4f" % optimizer.grad_norm.item()      # the last step's unclipped global norm, read where the losses are read
+            print("[%3d, %3d] loss: %s" % ((epoch + 1) * a.eval_epoch, idx + 1, parts))
+        if a.max_iters and idx + 1 >= a.max_iters:
+            break
+    torch.cuda.synchronize()
+    if st.rank == 0:
+        print("epoch %d: %.2f volumes/s per rank (%s)" % (epoch + 1, seen / max(time.time() - t0, 1e-9), "graph replay" if st.stepper is not None else "eager"))
+
+
+def _write_json(prefix, name, epoch, obj):
+    os.makedirs(os.path.join("tensorboard", prefix), exist_ok=True)
+    with open(os.path.join("tensorboard", prefix, "%s_%d.json" % (name, epoch)), "w") as f:
+        json.dump(obj, f)
+
+
+def validate_epoch(args, model, val_loader, nc, runner, epoch):
+    """rank 0's validation of one outer epoch and its tensorboard/<prefix>/*_<epoch>.json files -> the mean score"""
+    model.eval()
+    logs = {"surface": {}, "lesion": {}, "intensity": {}}                  # --val_surface / --val_lesion / --val_intensity: per-case records, filled by validate
+    clean = {"keep_largest": args.val_keep_largest, "min_component": args.val_min_component, "closing": args.val_closing,
+             "fill_holes": bool(args.val_fill_holes)}
+    if runner is not None and (epoch != 0 or args.test_only):             # main_target.py:811
+        scores, scores_noft = validate_finetune(runner, val_loader)
+        print("epoch %d validation result without finetuning: %f" % (epoch + 1, float(np.mean(list(scores_noft.values())))))
+    else:
+        save_dir = os.path.join("result", args.prefix) if args.save_eval_result and epoch % 10 == 0 else None
+        scores = validate(args.method, model, val_loader, nc, save_dir=save_dir, epoch=epoch, surface=bool(args.val_surface), surface_log=logs["surface"],
+                          lesion=bool(args.val_lesion), lesion_log=logs["lesion"], intensity=int(args.val_intensity or 0),
+                          intensity_log=logs["intensity"], **clean)
+    _write_json(args.prefix, "score", epoch, scores)
+    for name, log in logs.items():
+        if log:
+            _write_json(args.prefix, name, epoch, log)
+    if args.val_whole_volume:                                              # after validation, which it leaves as it is
+        sw = {"overlap": args.sw_overlap, "batch": args.sw_batch, "blend": args.sw_blend, "tta": args.val_tta}
+        whole_log = {}
+        validate_whole_volume(model, val_loader.whole_cases(), nc, args.size, log=whole_log, **sw, **clean)
+        _write_json(args.prefix, "whole", epoch, whole_log)
+        if args.val_fine_whole:
+            fine_log = {}
+            validate_fine_whole(model, val_loader.whole_cases(), nc, args.size, interp=args.fine_interp, log=fine_log, save_dir=args.save_whole_pred,
+                                names=val_loader.names, **sw, **clean)
+            _write_json(args.prefix, "fine", epoch, fine_log)
+    return float(np.mean(list(scores.values()))) if scores else 0.0
+
+
+def run(args, side="source"):
+    """start_process -> build_models -> load_and_freeze -> build_optimizer -> a TrainState, then per outer epoch train_epoch on every rank and
+    validate_epoch and the checkpoint on rank 0 -> the best validation score"""
+    rank, world = start_process(args, side)
+    nc, method = n_class_of(args), args.method
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
+    model, trainable, teacher = load_and_freeze(args, *build_models(args, nc), dtype)
+    deep, optimizer, params, sync = build_optimizer(args, model, trainable, teacher, world)
     # fp16 storage: Dice gradients are O(1e-6), below fp16's normal range — dynamic loss scaling on the device (optim.LossScaler, DESIGN 4.3)
     scaler = optim.LossScaler() if dtype == torch.float16 else None
-    skw = {} if scaler is None else {"scaler": scaler}
 
     runner = None
-    if method == "domain_adaptation" and getattr(args, "val_finetune", 0) and rank == 0:
+    if method == "domain_adaptation" and args.val_finetune and rank == 0:
         model_ft = build_joint(args).cuda()
         set_kernel_dtype(model_ft, dtype)
-        runner = T.TestTimeFinetune(model, model_ft, teacher, args.size, steps=args.val_finetune, lr=args.lr_finetune,
-                                    lambda_vae=args.lambda_vae, domain_loss_type=getattr(args, "domain_loss_type", 0),
-                                    kl=getattr(args, "kl", False), only_pseudo=getattr(args, "only_pseudo", False),
-                                    use_confident_binarize=getattr(args, "use_confident_binarize", False), n_class=nc)
+        runner = T.TestTimeFinetune(model, model_ft, teacher, args.size, steps=args.val_finetune, lr=args.lr_finetune, lambda_vae=args.lambda_vae,
+                                    domain_loss_type=args.domain_loss_type, kl=args.kl, only_pseudo=args.only_pseudo,
+                                    use_confident_binarize=args.use_confident_binarize, n_class=nc)
 
     train_loader, val_loader, sampler = make_loaders(args, rank, world)
-    pseudo_loader = make_pseudo_loader(args, rank, world) if (method == "domain_adaptation" and getattr(args, "pseudo_list", None) is not None) else None
-    pseudo_itr, pseudo_cycles = None, 0
-    pimg_buf = plab_buf = None
-    lambda_vae = args.lambda_vae
-    turn_epoch, warmup_epochs = getattr(args, "turn_epoch", -1), getattr(args, "lambda_vae_warmup", 0)
-    has_dropout = bool(getattr(args, "seg_dropout", 0.0) or getattr(args, "vae_decoder_dropout", 0.0))
-    use_graph = not getattr(args, "no_graph", False) and not has_dropout      # dropout draws fresh masks per call: eager (train.GraphedStep)
-    bs, side_ = args.batch_size, args.size
-    img_buf = torch.zeros(bs, 1, side_, side_, side_, device="cuda")         # fixed-address inputs of the captured step
-    lab_buf = torch.zeros(bs, 1, side_, side_, side_, device="cuda")
-    score_buf = torch.zeros(bs, 1, device="cuda")                           # discriminator_train's regression target (venous_score)
-    cur = {"epoch": 0}
-    # the sampling methods draw VAE noise per call.  --latent_noise torch (the default): torch.randn, launched eagerly.  --latent_noise philox: one
-    # ops.LatentStream per rank, drawn inside the forward launch from a device-resident counter, so the step is captured like every other method's;
-    # embed_train's requires_grad toggle by epoch parity rebuilds the captured step (loss_key below)
-    latent = None
-    if method in ("embed_train", "refine_vae", "vae_train"):
-        if getattr(args, "latent_noise", "torch") == "philox":
-            # 1000 rank + 700: the loaders' per-rank Philox streams are seeded base + 1000 rank (+ 500) with their own fixed bases; this one's base is 0
-            # (the entry points have no --seed flag)
-            latent = ops.LatentStream(1000 * rank + 700)
-        else:
-            use_graph = False
-
-    seg_loss = seg_loss_of(args)                                            # --seg_loss dice_ce: ops.seg_loss's arguments; None: the reference's Dice
-    deep_kw = {} if deep is None else {"deep": deep}
-    # --boundary_weight: the boundary term's weight is ONE device scalar, refilled at the top of every outer epoch (train.boundary_weight): the captured
-    # launches read it, so the ramp needs no re-capture.  With the flags at their defaults nothing is built and loss_fn passes nothing on
-    boundary_on = boundary_enabled(args) and method in SEG_LOSS_METHODS and seg_loss is not None
-    boundary_w = torch.zeros((), dtype=torch.float32, device="cuda") if boundary_on else None
-    if boundary_on:
-        deep_kw = dict(deep_kw, boundary={"weight": boundary_w, "spacing": None})
-
-    def loss_fn():
-        if method == "vae_train":
-            return T.vae_train_losses(model, lab_buf, scale=0.35, noise=latent, eps=eps, n_class=nc)
-        if method == "seg_train":
-            return T.seg_train_losses(model, img_buf, lab_buf, eps=eps, n_class=nc, loss=seg_loss, **deep_kw)
-        if method == "joint_train":
-            return T.joint_train_losses(model, img_buf, lab_buf, lambda_vae=lambda_vae, eps=eps, n_class=nc, loss=seg_loss, **deep_kw)
-        if method == "sep_joint_train":
-            return T.sep_joint_train_losses(model, teacher, img_buf, lab_buf, eps=eps, n_class=nc)
-        if method == "embed_train":
-            return T.embed_train_losses(model, img_buf, lab_buf, eps=eps, n_class=nc, noise=latent)
-        if method == "refine_vae":
-            return T.refine_vae_losses(model, img_buf, lab_buf, eps=eps, n_class=nc, noise=latent)
-        if method == "discriminator_train":
-            return T.discriminator_train_loss(model, lab_buf, score_buf)
-        if method == "domain_adaptation_dis":
-            return T.domain_adaptation_dis_losses(model, teacher, img_buf, lab_buf, lambda_vae=lambda_vae, epoch=cur["epoch"],
-                                                  lambda_vae_warmup=warmup_epochs,
-                                                  use_confident_binarize=getattr(args, "use_confident_binarize", False), eps=eps, n_class=nc)
-        if pseudo_loader is not None:                                       # main_target.py:615-661: a --pseudo_list run has its own loss ladder
-            return T.domain_adaptation_pseudo_losses(model, teacher, img_buf, lab_buf, lambda_vae=lambda_vae,
-                                                     domain_loss_type=getattr(args, "domain_loss_type", 0),
-                                                     use_confident_binarize=getattr(args, "use_confident_binarize", False), eps=eps, n_class=nc,
-                                                     host_schedule=not use_graph)
-
-        def da():
-            return T.domain_adaptation_losses(model, teacher, img_buf, lab_buf, lambda_vae=lambda_vae,
-                                              domain_loss_type=getattr(args, "domain_loss_type", 0), kl=getattr(args, "kl", False),
-                                              use_confident_binarize=getattr(args, "use_confident_binarize", False), eps=eps, n_class=nc,
-                                              only_pseudo=getattr(args, "only_pseudo", False), epoch=cur["epoch"], turn_epoch=turn_epoch,
-                                              lambda_vae_warmup=warmup_epochs, host_schedule=not use_graph)
-        n_mc = max(1, int(getattr(args, "vae_mont_number", 1)))
-        if n_mc == 1:
-            return da()
-        # main_target.py:530-603 (--vae_mont_number N): N forward passes of student and teacher per step (they differ by their dropout draws),
-        # the four loss terms averaged, one backward through all of them
-        final, aux = da()
-        tot = {k: v for k, v in aux.items() if k != "batch" and k != "kl_loss"}
-        for _ in range(n_mc - 1):
-            f, a = da()
-            final = final + f
-            tot = {k: tot[k] + a[k] for k in tot}
-            aux = a
-        out = {k: v / n_mc for k, v in tot.items()}
-        out["kl_loss"], out["batch"] = aux["kl_loss"], aux["batch"]         # the reference logs the LAST pass's KL (:605)
-        return final / n_mc, out
-
-    def loss_key(epoch):
-        """what of the loss expression depends on the epoch (main_target.py:583-592): a captured step is rebuilt when it changes"""
-        if method == "domain_adaptation_dis":                               # main_target.py:720-723: lambda ramps with the epoch during the warm-up
-            return min(epoch, warmup_epochs)
-        if method == "embed_train":                                         # the Encoder's requires_grad follows the epoch's parity: another live parameter set
-            return epoch % 2
-        if method != "domain_adaptation" or getattr(args, "domain_loss_type", 0) != 0 or getattr(args, "only_pseudo", False):
-            return 0
-        if turn_epoch != -1:
-            return (epoch // turn_epoch) % 2
-        return min(epoch, warmup_epochs)
-
-    stepper, stepper_key = None, None
-    best, n_outer = 0.0, max(1, args.max_epoch // args.eval_epoch)
-    base_lrs = [grp["lr"] for grp in optimizer.param_groups]
-    for epoch in range(n_outer):
-        cur["epoch"] = epoch
-        if getattr(args, "lr_schedule", "constant") == "poly":          # a captured step follows through sync_hyper(): no re-capture
-            for grp, base in zip(optimizer.param_groups, base_lrs):
-                grp["lr"] = optim.poly_lr(base, epoch, n_outer, args.poly_power)
-        if boundary_w is not None:                                      # likewise: the captured launches read the scalar
-            boundary_w.fill_(T.boundary_weight(epoch, args.boundary_weight, args.boundary_ramp, args.boundary_max))
+    pseudo_loader = make_pseudo_loader(args, rank, world) if method == "domain_adaptation" and args.pseudo_list is not None else None
+    st = TrainState(args, side, nc, rank, model, trainable, teacher, deep, optimizer, params, sync, scaler, pseudo_loader)
+    best = 0.0
+    for epoch in range(st.n_outer):
+        st.begin_epoch(epoch)
         if sampler is not None:
             sampler.set_epoch(epoch)
-        skip_da = method in ("domain_adaptation", "domain_adaptation_dis") and epoch == 0 and not getattr(args, "train_first_epoch", False)    # main_target.py:506,697: `if epoch == 0: continue`
-        if method == "embed_train":                                         # main_source.py:550-554: the image encoder trains on odd epochs only
-            for prm in model.Encoder.parameters():
-                prm.requires_grad = epoch % 2 == 1
-            params = [p for p in trainable.parameters() if p.requires_grad]
+        skip_da = method in ("domain_adaptation", "domain_adaptation_dis") and epoch == 0 and not args.train_first_epoch    # main_target.py:506,697: `if epoch == 0: continue`
         if not args.test_only and not skip_da:
-            model.train()
-            if hasattr(model, "Vae"):
-                model.Vae.eval()
-            if use_graph and (stepper is None or stepper_key != loss_key(epoch)):
-                stepper = None                                        # release the old capture's memory pool first
-                # a GraphedStep drops the gradients of ITS parameters only, and an eager optimiser tail steps every parameter that holds one: a parameter
-                # frozen for this epoch (embed_train's Encoder on even epochs) must not keep the gradient the previous capture's last replay left it
-                for grp in optimizer.param_groups:
-                    for p in grp["params"]:
-                        p.grad = None
-                stepper = T.GraphedStep(loss_fn, params, optimizer, grad_sync=sync, warmup=1, scaler=scaler)
-                stepper_key = loss_key(epoch)
-                if rank == 0:
-                    print("train step captured as a HIP graph (%s)" % ("2 graphs + bucketed all-reduce" if stepper.graph2 is not None else "1 graph"))
-            t0, seen = time.time(), 0
-            n_iter = len(train_loader)
-            for idx, batch in enumerate(train_loader):
-                img_buf.copy_(batch[IMG_KEY], non_blocking=True)
-                lab_buf.copy_(batch[LABEL_KEY], non_blocking=True)
-                if method == "discriminator_train":          # synthetic stand-in for the venous_score field: a function of the mask
-                    score_buf.copy_(batch[LABEL_KEY].float().mean((1, 2, 3, 4)).view(-1, 1) * 4, non_blocking=True)
-                teacher_next = None
-                if pseudo_loader is not None and getattr(args, "pseudo_save_epoch", 0) and epoch % args.pseudo_save_epoch == 0:
-                    # main_target.py:633-635 (--pseudo_list runs): the pseudo-label network is re-loaded from the student AFTER this iteration's two forwards and
-                    # BEFORE its optimizer step, i.e. the next iteration's pseudo-labels come from the weights this one started with: keep them, load after the step
-                    with torch.no_grad():
-                        teacher_next = {k: v.clone() for k, v in model.state_dict().items()}
-                    if getattr(args, "tag", False):                                  # :635 — ahead of this iteration's loss
-                        lambda_vae /= 10
-                        stepper_key = None
-                elif pseudo_loader is None and method == "domain_adaptation" and getattr(args, "pseudo_save_epoch", 0):
-                    # EMA teacher (main_target.py:508-518): every `pseudo_save_epoch` epochs, at the first iteration of an epoch slice or
-                    # every iteration; never in epoch 0
-                    every = max(1, args.pseudo_save_epoch // args.eval_epoch)
-                    if epoch != 0 and epoch % every == 0 and (getattr(args, "update_every_iteration", False) or idx % max(1, n_iter // args.eval_epoch) == 0):
-                        optim.ema_update(teacher.Seg, model.Seg, args.alpha)
-                if method == "domain_adaptation_dis" and getattr(args, "pseudo_save_epoch", 0) and epoch % args.pseudo_save_epoch == 0:
-                    # main_target.py:710-712: the pseudo-label network is re-loaded from the student (in place: a captured graph replays it)
-                    with torch.no_grad():
-                        teacher.load_state_dict(model.Seg.state_dict())
-                    ops.clear_pack_cache()
-                    ops.refresh_frozen_packs(teacher)
-                    if getattr(args, "tag", False):
-                        lambda_vae /= 10
-                        stepper_key = None                                   # lambda is baked into the captured loss expression
-                if use_graph and stepper is not None and stepper_key is None:
-                    stepper = None
-                    stepper = T.GraphedStep(loss_fn, params, optimizer, grad_sync=sync, warmup=1, scaler=scaler)
-                    stepper_key = loss_key(epoch)
-                if stepper is not None:
-                    stepper.step()
-                    aux = stepper.aux
-                else:
-                    # optimizer.zero_grad() over ALL parameters, as the reference does every iteration (main_source.py:660): a parameter that is
-                    # frozen for this epoch (embed_train's Encoder on even epochs) must not keep the gradient of its last trained step
-                    for grp in optimizer.param_groups:
-                        for p in grp["params"]:
-                            p.grad = None
-                    loss, aux = loss_fn()
-                    if scaler is not None:
-                        loss.backward(gradient=scaler.seed)
-                    else:
-                        loss.backward()
-                    if sync is not None:
-                        sync()
-                        optimizer.step_with(*sync.live(), **skw)
-                    else:
-                        optimizer.step(**skw)
-                if teacher_next is not None:
-                    with torch.no_grad():
-                        teacher.load_state_dict(teacher_next)                        # in place: a captured graph replays the same storage
-                    ops.clear_pack_cache()
-                    ops.refresh_frozen_packs(teacher)
-                if pseudo_loader is not None:
-                    # main_target.py:663-687: the next batch of the pseudo-labelled loader (cycled), student forward, two Dice terms — logged, never stepped on
-                    pb = next(pseudo_itr, None) if pseudo_itr is not None else None
-                    if pb is None:
-                        pseudo_cycles += 1
-                        if hasattr(pseudo_loader, "set_epoch"):
-                            pseudo_loader.set_epoch(pseudo_cycles)                  # a DataLoader(shuffle=True) draws a new order per pass (main_target.py:299-307)
-                        pseudo_itr = iter(pseudo_loader)
-                        pb = next(pseudo_itr)
-                    if pimg_buf is None:
-                        pimg_buf, plab_buf = torch.zeros_like(img_buf), torch.zeros_like(lab_buf)
-                    pimg_buf.copy_(pb[IMG_KEY], non_blocking=True)
-                    plab_buf.copy_(pb[LABEL_KEY], non_blocking=True)
-                    aux = dict(aux)
-                    aux.update(T.pseudo_batch_losses(model, pimg_buf, plab_buf, eps=eps, n_class=nc))
-                seen += bs
-                if rank == 0 and idx % args.display_freq == 0:              # logging syncs the host every display_freq steps only
-                    parts = ", ".join("%s %.4f" % (k, v.item()) for k, v in aux.items() if k not in ("batch", "ds_losses"))
-                    for lvl, (d_i, ce_i) in enumerate(aux.get("ds_losses", ()), 1):      # --deep_supervision: the coarse levels' terms
-                        parts += ", ds%d_dice_loss %.4f, ds%d_ce_loss %.4f" % (lvl, d_i.item(), lvl, ce_i.item())
-                    if optimizer.max_norm is not None and optimizer.grad_norm is not None:
-                        parts += ", grad_norm %.4f" % optimizer.grad_norm.item()      # the last step's unclipped global norm, read where the losses are read
-                    print("[%3d, %3d] loss: %s" % ((epoch + 1) * args.eval_epoch, idx + 1, parts))
-                if args.max_iters and idx + 1 >= args.max_iters:
-                    break
-            torch.cuda.synchronize()
-            if rank == 0:
-                print("epoch %d: %.2f volumes/s per rank (%s)" % (epoch + 1, seen / max(time.time() - t0, 1e-9),
-                                                                   "graph replay" if stepper is not None else "eager"))
+            train_epoch(st, train_loader, epoch)
         if rank == 0:
-            model.eval()
-            surface_log = {}                                                       # --val_surface: per-case ASSD / HD95, filled by validate
-            lesion_log = {}                                                        # --val_lesion: per-case lesion records and confusion scores
-            intensity_log = {}                                                     # --val_intensity: per-case histograms and mutual information
-            if runner is not None and (epoch != 0 or args.test_only):             # main_target.py:811
-                scores, scores_noft = validate_finetune(runner, val_loader)
-                print("epoch %d validation result without finetuning: %f" % (epoch + 1, float(np.mean(list(scores_noft.values())))))
-            else:
-                save_dir = os.path.join("result", args.prefix) if getattr(args, "save_eval_result", False) and epoch % 10 == 0 else None
-                scores = validate(method, model, val_loader, nc, keep_largest=getattr(args, "val_keep_largest", 0),
-                                  min_component=getattr(args, "val_min_component", 0), save_dir=save_dir, epoch=epoch,
-                                  surface=bool(getattr(args, "val_surface", False)), surface_log=surface_log,
-                                  closing=getattr(args, "val_closing", 0), fill_holes=bool(getattr(args, "val_fill_holes", False)),
-                                  lesion=bool(getattr(args, "val_lesion", False)), lesion_log=lesion_log,
-                                  intensity=int(getattr(args, "val_intensity", 0) or 0), intensity_log=intensity_log)
-            mean = float(np.mean(list(scores.values()))) if scores else 0.0
-            os.makedirs(os.path.join("tensorboard", args.prefix), exist_ok=True)
-            with open(os.path.join("tensorboard", args.prefix, "score_%d.json" % epoch), "w") as f:
-                json.dump(scores, f)
-            if surface_log:
-                with open(os.path.join("tensorboard", args.prefix, "surface_%d.json" % epoch), "w") as f:
-                    json.dump(surface_log, f)
-            if lesion_log:
-                with open(os.path.join("tensorboard", args.prefix, "lesion_%d.json" % epoch), "w") as f:
-                    json.dump(lesion_log, f)
-            if intensity_log:
-                with open(os.path.join("tensorboard", args.prefix, "intensity_%d.json" % epoch), "w") as f:
-                    json.dump(intensity_log, f)
-            if getattr(args, "val_whole_volume", False):                           # after validation, which it leaves as it is
-                whole_log = {}
-                validate_whole_volume(model, val_loader.whole_cases(), nc, args.size, overlap=args.sw_overlap, batch=args.sw_batch, blend=args.sw_blend,
-                                      keep_largest=getattr(args, "val_keep_largest", 0), min_component=getattr(args, "val_min_component", 0), log=whole_log,
-                                      tta=getattr(args, "val_tta", None), closing=getattr(args, "val_closing", 0),
-                                      fill_holes=bool(getattr(args, "val_fill_holes", False)))
-                with open(os.path.join("tensorboard", args.prefix, "whole_%d.json" % epoch), "w") as f:
-                    json.dump(whole_log, f)
-                if getattr(args, "val_fine_whole", False):
-                    fine_log = {}
-                    validate_fine_whole(model, val_loader.whole_cases(), nc, args.size, overlap=args.sw_overlap, batch=args.sw_batch, blend=args.sw_blend,
-                                        keep_largest=getattr(args, "val_keep_largest", 0), min_component=getattr(args, "val_min_component", 0),
-                                        interp=args.fine_interp, log=fine_log, save_dir=getattr(args, "save_whole_pred", None), names=val_loader.names,
-                                        tta=getattr(args, "val_tta", None), closing=getattr(args, "val_closing", 0),
-                                        fill_holes=bool(getattr(args, "val_fill_holes", False)))
-                    with open(os.path.join("tensorboard", args.prefix, "fine_%d.json" % epoch), "w") as f:
-                        json.dump(fine_log, f)
+            mean = validate_epoch(args, model, val_loader, nc, runner, epoch)
             print("epoch %d validation result: %f, best result %f." % (epoch + 1, mean, best))
             if not args.test_only and (epoch + 1) % max(1, args.save_epoch // args.eval_epoch) == 0:
                 save_checkpoint(args.prefix, (epoch + 1) * args.eval_epoch, model, optimizer, mean > best, deep=deep)
@@ -1027,22 +1069,18 @@ def run(args, side="source"):
 
 def check_target_flags(a):
     """main_target.py:145-170: the reference's own consistency asserts, plus what this entry point does with the flags it does not act on."""
-    import sys
-    def need(cond, what):                                                    # the reference asserts; `python -O` strips asserts, an entry point must not
-        if not cond:
-            raise SystemExit("main_target.py: inconsistent flags — " + what)
     if a.vae_mont_number != 1:
-        need(a.vae_forward_scale != 0.0, "--vae_mont_number != 1 needs a non-zero --vae_forward_scale")                                 # main_target.py:145
+        _need("main_target.py", a.vae_forward_scale != 0.0, "--vae_mont_number != 1 needs a non-zero --vae_forward_scale")                                 # main_target.py:145
     if a.from_scratch:
-        need(a.method == "domain_adaptation" and not a.test_only, "--from_scratch belongs to --method domain_adaptation, not to --test_only")   # :157-159
+        _need("main_target.py", a.method == "domain_adaptation" and not a.test_only, "--from_scratch belongs to --method domain_adaptation, not to --test_only")   # :157-159
     if a.kl:
-        need(a.method == "domain_adaptation" and a.domain_loss_type in (0, 8), "--kl belongs to domain_adaptation with --domain_loss_type 0 or 8")   # :162-164
+        _need("main_target.py", a.method == "domain_adaptation" and a.domain_loss_type in (0, 8), "--kl belongs to domain_adaptation with --domain_loss_type 0 or 8")   # :162-164
     if a.update_every_iteration:
-        need(a.pseudo_save_epoch == 1, "--update_every_iteration needs --pseudo_save_epoch 1")                                           # :168
+        _need("main_target.py", a.pseudo_save_epoch == 1, "--update_every_iteration needs --pseudo_save_epoch 1")                                           # :168
     if a.generate_bounding_boxes:
-        need(a.method == "domain_adaptation", "--generate_bounding_boxes belongs to --method domain_adaptation")                        # :170
+        _need("main_target.py", a.method == "domain_adaptation", "--generate_bounding_boxes belongs to --method domain_adaptation")                        # :170
     if a.pseudo_list is not None:
-        need(a.method == "domain_adaptation", "--pseudo_list is read by --method domain_adaptation only (main_target.py:615; domain_adaptation_dis runs "
+        _need("main_target.py", a.method == "domain_adaptation", "--pseudo_list is read by --method domain_adaptation only (main_target.py:615; domain_adaptation_dis runs "
                                               "without it, :689)")
     ignored = [n for n in ("save_more_reference", "analysis_figure_name", "generate_bounding_boxes", "resume") if getattr(a, n)]
     if ignored:
@@ -1050,52 +1088,35 @@ def check_target_flags(a):
               % ", ".join("--" + n for n in ignored), file=sys.stderr)
 
 
-def _probability(text):
-    import argparse
+def _typed(text, convert, accept, what):
+    """an argparse type: convert(text) where accept() holds for it, else the error `what, got <text>`"""
     try:
-        v = float(text)
+        v = convert(text)
+        if accept(v):
+            return v
     except ValueError:
-        v = float("nan")
-    if not 0.0 <= v <= 1.0:
-        raise argparse.ArgumentTypeError("a probability in [0, 1], got %r" % text)
-    return v
+        pass
+    raise argparse.ArgumentTypeError("%s, got %r" % (what, text))
+
+
+def _probability(text):
+    return _typed(text, float, lambda v: 0.0 <= v <= 1.0, "a probability in [0, 1]")
 
 
 def _margin(text):
-    import argparse
-    try:
-        v = int(text)
-    except ValueError:
-        v = -1
-    if v < 0:
-        raise argparse.ArgumentTypeError("a non-negative number of voxels, got %r" % text)
-    return v
+    return _typed(text, int, lambda v: v >= 0, "a non-negative number of voxels")
 
 
 def _percentile_pair(text):
-    import argparse
-    try:
-        lo, hi = (float(v) for v in text.split(","))
-    except ValueError:
-        lo = hi = float("nan")
-    if not 0.0 <= lo < hi <= 100.0:
-        raise argparse.ArgumentTypeError("two ascending percentiles P_LO,P_HI in [0, 100], got %r" % text)
-    return lo, hi
+    return _typed(text, lambda t: tuple(float(v) for v in t.split(",")), lambda p: len(p) == 2 and 0.0 <= p[0] < p[1] <= 100.0,
+                  "two ascending percentiles P_LO,P_HI in [0, 100]")
 
 
 def _nonnegative(text):
-    import argparse
-    try:
-        v = float(text)
-    except ValueError:
-        v = float("nan")
-    if not 0.0 <= v < float("inf"):
-        raise argparse.ArgumentTypeError("a finite number >= 0, got %r" % text)
-    return v
+    return _typed(text, float, lambda v: 0.0 <= v < float("inf"), "a finite number >= 0")
 
 
 def _class_weights(text):
-    import argparse
     try:
         ws = [_nonnegative(t) for t in text.split(",")]
     except argparse.ArgumentTypeError:
@@ -1111,7 +1132,7 @@ def check_seg_loss_flags(parser, a, methods=SEG_LOSS_METHODS):
     of main_source.py (main_target.py passes methods=())"""
     given = [n for n, default in (("seg_loss", "dice"), ("ce_weight", 1.0), ("batch_dice", False), ("focal_gamma", 0.0), ("class_weights", None),
                                   ("deep_supervision", 0))
-             if getattr(a, n, default) != default]
+             if getattr(a, n) != default]
     if not given:
         return a
     if a.method not in methods:
@@ -1132,19 +1153,19 @@ BOUNDARY_FLAGS = (("boundary_weight", 0.0), ("boundary_ramp", 0.0), ("boundary_m
 
 def boundary_enabled(args):
     """--boundary_weight / --boundary_ramp switch the boundary term on (a ramp from weight 0 is a schedule too)"""
-    return getattr(args, "boundary_weight", 0.0) > 0 or getattr(args, "boundary_ramp", 0.0) > 0
+    return args.boundary_weight > 0 or args.boundary_ramp > 0
 
 
 def check_boundary_flags(parser, a, methods=SEG_LOSS_METHODS):
     """--boundary_weight, --boundary_ramp and --boundary_max add the boundary term to the compound loss: they belong where --seg_loss dice_ce does
     (seg_train and joint_train of main_source.py; main_target.py passes methods=())"""
-    given = [n for n, default in BOUNDARY_FLAGS if getattr(a, n, default) != default]
+    given = [n for n, default in BOUNDARY_FLAGS if getattr(a, n) != default]
     if not given:
         return a
     names = ", ".join("--" + n for n in given)
     if a.method not in methods:
         parser.error("%s: the boundary loss belongs to --method seg_train and joint_train of main_source.py, not to --method %s" % (names, a.method))
-    if getattr(a, "seg_loss", "dice") != "dice_ce":
+    if a.seg_loss != "dice_ce":
         parser.error("%s add(s) the boundary term to the compound loss: add --seg_loss dice_ce" % names)
     if not boundary_enabled(a):
         parser.error("%s: the boundary term is off — give --boundary_weight or --boundary_ramp above 0" % names)
@@ -1153,35 +1174,47 @@ def check_boundary_flags(parser, a, methods=SEG_LOSS_METHODS):
 
 def seg_loss_of(args):
     """the `loss` argument of train.seg_train_losses / joint_train_losses from the flags; None for --seg_loss dice (the default): the reference's Dice"""
-    if getattr(args, "seg_loss", "dice") != "dice_ce":
+    if args.seg_loss != "dice_ce":
         return None
     return {"dice_weight": 1.0, "ce_weight": args.ce_weight, "batch_dice": bool(args.batch_dice), "class_weights": args.class_weights,
             "gamma": args.focal_gamma}
 
 
+# the flags main_target.py declares and main_source.py lacks, with main_target.py's defaults (tests/test_host_driver.py holds the two against each other):
+# check_aug_flags, the tail of both parse() functions, gives a namespace those it lacks, so every read below is a plain attribute
+TARGET_ONLY_DEFAULTS = {
+    "pseudo_data_root": "../nih_data/numpy_data/", "pseudo_list": None, "load_prefix_encoder": None, "pseudo_pan_index": "1", "domain_loss_type": 0, "kl": False,
+    "use_confident_binarize": False, "pseudo_save_epoch": 0, "update_every_iteration": False, "alpha": 0.995, "seg_dropout": 0.0, "vae_decoder_dropout": 0.0,
+    "val_finetune": 0, "lr_finetune": 1e-2, "only_pseudo": False, "fix_layer": False, "vae_mont_number": 1, "vae_forward_scale": 0.0, "tag": False,
+    "from_scratch": False, "shift": 0}
+
+
 def check_aug_flags(parser, a, seg_loss_methods=SEG_LOSS_METHODS):
     """--aug_elastic and --aug_intensity act on the augmented training samples: with --no_aug there are none; --standardize reads real cases;
-    the compound-loss flags belong to seg_loss_methods (check_seg_loss_flags)"""
+    the compound-loss flags belong to seg_loss_methods (check_seg_loss_flags).  -> a, completed by TARGET_ONLY_DEFAULTS"""
     check_seg_loss_flags(parser, a, seg_loss_methods)
     check_boundary_flags(parser, a, seg_loss_methods)
-    if getattr(a, "aug_elastic", 0.0) > 0 and getattr(a, "no_aug", False):
+    if a.aug_elastic > 0 and a.no_aug:
         parser.error("--aug_elastic deforms the augmented training samples: it cannot be combined with --no_aug")
-    if getattr(a, "aug_intensity", False) and getattr(a, "no_aug", False):
+    if a.aug_intensity and a.no_aug:
         parser.error("--aug_intensity changes the grey values of the augmented training samples: it cannot be combined with --no_aug")
-    if getattr(a, "aug_lowres", 0.0) > 0 and not getattr(a, "aug_intensity", False):
+    if a.aug_lowres > 0 and not a.aug_intensity:
         parser.error("--aug_lowres is a stage of the intensity augmentation: it needs --aug_intensity")
-    if getattr(a, "standardize", None) is not None and not getattr(a, "real_data", False):
+    if a.standardize is not None and not a.real_data:
         parser.error("--standardize reads the percentiles of merge.npy cases: it needs --real_data")
-    if getattr(a, "standardize_above", None) is not None and getattr(a, "standardize", None) is None:
+    if a.standardize_above is not None and a.standardize is None:
         parser.error("--standardize_above selects the voxels --standardize reads: it needs --standardize")
-    if getattr(a, "nesterov", False) and getattr(a, "adam", False):
+    if a.nesterov and a.adam:
         parser.error("--nesterov is a form of SGD's momentum: it cannot be combined with --adam")
-    if getattr(a, "nesterov", False) and not getattr(a, "momentum", 0.9) > 0:
+    if a.nesterov and not a.momentum > 0:
         parser.error("--nesterov needs a --momentum above 0")
-    if getattr(a, "train_patches", False) and not getattr(a, "real_data", False):
+    if a.train_patches and not a.real_data:
         parser.error("--train_patches cuts its windows from merge.npy cases: it needs --real_data")
-    if getattr(a, "train_patches", False) and len(str(a.pan_index).split(",")) + 1 > 8:
+    if a.train_patches and len(str(a.pan_index).split(",")) + 1 > 8:
         parser.error("--train_patches indexes at most 8 classes, the background included")
+    for name, default in TARGET_ONLY_DEFAULTS.items():
+        if not hasattr(a, name):
+            setattr(a, name, default)
     return a
 
 
