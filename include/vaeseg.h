@@ -423,7 +423,9 @@ int vs_data_crop_pad(const float* src, float* dst, int sd, int sh, int sw, int d
 /* scipy.ndimage.gaussian_filter1d(mode='mirror', truncate=4.0) along one axis (src != dst) */
 int vs_data_gaussian_axis(const float* src, float* dst, int d, int h, int w, int axis, float sigma, void* stream);
 int vs_data_minmax(const float* x, long long total, float* minmax2, void* stream);
-/* scipy.ndimage.zoom(mode='mirror', grid_mode=True), order 0 or 1; order 1 results are clamped to [clip_lo, clip_hi] unless clip_lo > clip_hi */
+/* scipy.ndimage.zoom(mode='mirror', grid_mode=True), order 0 or 1; order 1 results are clamped to [clip_lo, clip_hi] unless clip_lo > clip_hi.
+ * Output index o of an axis reads the input at c = (o + 0.5) * (n_in / n_out) - 0.5, the division first as in scipy (it decides exact order-0 ties);
+ * order 0 takes the voxel floor(c + 0.5), mirrored. */
 int vs_data_zoom(const float* src, float* dst, int sd, int sh, int sw, int dd, int dh, int dw, int order, float clip_lo, float clip_hi, void* stream);
 /* order-3 B-spline coefficients of x in fp64 (scipy.ndimage.spline_filter, mirror boundary) */
 int vs_data_spline3_prefilter(const float* x, double* coef, int d, int h, int w, void* stream);

@@ -112,15 +112,22 @@ def to_native(src, raw_shape, spacing, interp="linear"):
 
 # ---- the cases of the kernel tests ---------------------------------------------------------------------------------------------------------------
 SIGNS = list(itertools.product((-1.0, 1.0), repeat=3))
-# (name, raw shape, |spacing|): tie-free under the forward order-0 resize (test_host_scan.py asserts it, with the zoom's output shapes)
+# (name, raw shape, |spacing|); test_host_scan.py asserts the tie distances, with the zoom's output shapes
 #   down-in-plane   oriented (9, 12, 7) -> 1 mm (7, 8, 17): anti-aliased in-plane, upsampled through-plane; tie distance 0.029
 #   up-in-plane     oriented (6, 9, 15) -> 1 mm (10, 12, 10): the other way round; tie distance 0.1
-KERNEL_CASES = [
+TIE_FREE_CASES = [
     ("down-in-plane", (12, 9, 7), (0.8, 0.7, 2.5)),
     ("up-in-plane", (9, 6, 15), (1.7, 1.4, 0.7)),
 ]
+#   tie             oriented (8, 6, 30) -> 1 mm (11, 7, 11): (o + 0.5) 30 / 11 and (o + 0.5) 8 / 11 are whole numbers at o = 5 ((o + 0.5) 6 / 7 at o = 3), so the forward order-0
+#                   resize of the label turns on an exact tie there; 30 -> 11 is a pair on which only the division-first coordinate,
+#                   (o + 0.5) (n_in / n_out) - 0.5, picks scipy's voxel (tests/test_host_data.py)
+TIE_CASES = [
+    ("tie", (6, 8, 30), (1.4, 1.2, 0.37)),
+]
+KERNEL_CASES = TIE_FREE_CASES + TIE_CASES
 # further geometries of the inverse alone, where a forward tie plays no part: a 64-long contiguous axis, a one-row 1 mm axis, an identity grid
-NATIVE_CASES = KERNEL_CASES + [
+NATIVE_CASES = TIE_FREE_CASES + [
     ("z64", (5, 7, 64), (1.3, 0.9, 0.55)),
     ("thin", (6, 5, 3), (1.1, 2.0, 0.4)),
     ("identity", (7, 6, 9), (1.0, 1.0, 1.0)),

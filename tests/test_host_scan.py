@@ -1,6 +1,6 @@
 """CPU: the host arithmetic of scan geometry (data_gpu.ScanGeometry, data_gpu.cube_slices) against known answers, and the properties of the numpy / scipy
-restatement (tests/scan_util.py) that tests/test_gpu_scan.py relies on: the oracle's zoom returns the requested shapes, the forward order-0 resize of every
-kernel case has no tie, and the label rule of the linear inverse leaves at most 1 % of the voxels out."""
+restatement (tests/scan_util.py) that tests/test_gpu_scan.py relies on: the oracle's zoom returns the requested shapes, the forward order-0 resize of the
+first two kernel cases has no tie and that of the third turns on an exact one, and the label rule of the linear inverse leaves at most 1 % of the voxels out."""
 import numpy as np
 import pytest
 
@@ -81,9 +81,9 @@ def test_cube_slices_against_hand_computed_answers():
         assert data_gpu.cube_slices(box, shape, pad) == S.foreground_cube(label, pad), (box, shape, pad)
 
 
-@pytest.mark.parametrize("case", S.KERNEL_CASES, ids=lambda c: c[0])
+@pytest.mark.parametrize("case", S.TIE_FREE_CASES, ids=lambda c: c[0])
 def test_kernel_cases_have_exact_shapes_and_no_forward_tie(case):
-    """the order-0 forward resize turns on floor(q + 0.5): a case is usable only if no q + 0.5 comes within 1e-6 of an integer"""
+    """the order-0 forward resize turns on floor(q + 0.5): in these cases no q + 0.5 comes within 1e-6 of an integer"""
     name, shape, spacing = case
     g = S.geometry(shape, spacing)
     dist = S.forward_tie_distance(shape, spacing)
@@ -96,6 +96,32 @@ def test_kernel_cases_have_exact_shapes_and_no_forward_tie(case):
     assert raw.min() <= pre["image"].min() and pre["image"].max() <= raw.max()             # skimage's clip=True
     up = [o < n for o, n in zip(g["oriented_shape"], g["shape_1mm"])]
     assert up == ([False, False, True] if name == "down-in-plane" else [True, True, False])
+
+
+@pytest.mark.parametrize("case", S.TIE_CASES, ids=lambda c: c[0])
+def test_tie_case_has_exact_shapes_and_an_exact_forward_tie(case):
+    """the case the kernels may not step around: its tie distance is 0, the oracle (scipy) resolves the tie by the division-first coordinate, and the
+    product-first one would move a whole plane of the label"""
+    from tests import data_util as U
+    name, shape, spacing = case
+    g = S.geometry(shape, spacing)
+    assert g["oriented_shape"] == (8, 6, 30) and g["shape_1mm"] == (11, 7, 11)
+    assert S.forward_tie_distance(shape, spacing) == 0.0
+    assert S.tie_distance(30, 11) == 0.0 and S.tie_distance(8, 11) == 0.0 and S.tie_distance(6, 7) == 0.0       # every axis: an odd output length
+    assert S.KERNEL_CASES == S.TIE_FREE_CASES + S.TIE_CASES and case in S.KERNEL_CASES and case not in S.NATIVE_CASES
+    raw, label = S.smooth_scan(shape, 1)
+    pre = S.preprocess(raw, spacing, label)
+    assert pre["image"].shape == g["shape_1mm"] and pre["label"].shape == g["shape_1mm"]
+    assert set(np.unique(pre["label"])) == {0.0, 1.0, 2.0}
+    # the smooth blob is mirror-symmetric about the tied plane, so the noisy scan itself goes through the label path as well (tests/test_gpu_scan.py does the same)
+    for name_, vol in (("label", label), ("scan as label", raw)):
+        want = S.preprocess(raw, spacing, vol)["label"]
+        oriented = S.orient(vol, spacing).astype(np.float64)
+        picks = {rule: oriented[np.ix_(*[U.zoom_pick0(m, n, rule) for m, n in zip(g["oriented_shape"], g["shape_1mm"])])] for rule in ("division", "product")}
+        assert np.array_equal(picks["division"], want)
+        differing = int((picks["product"] != want).sum())
+        print(name, name_, "voxels the product-first coordinate would get wrong: %d of %d" % (differing, want.size))
+    assert differing >= want.size // 11                                     # a whole plane of the 1 mm grid
 
 
 def test_the_issues_rejected_candidates_do_have_ties():

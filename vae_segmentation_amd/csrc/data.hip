@@ -84,14 +84,22 @@ __global__ __launch_bounds__(256) void dp_gauss_axis_kernel(const float* __restr
     }
 }
 
-// ---- scipy.ndimage.zoom(order, mode='mirror', grid_mode=True): input coordinate of output o = (o + 0.5) * n_in / n_out - 0.5 ------------------
+// ---- scipy.ndimage.zoom(order, mode='mirror', grid_mode=True): input coordinate of output o = (o + 0.5) * (n_in / n_out) - 0.5, the zoom ONE fp64
+// division made first, as scipy makes it: the product-first form ((o + 0.5) * n_in) / n_out differs in the last bit and falls on the other side of
+// exact order-0 ties (30 -> 11, 112 -> 40, 272 -> 56, ...; tests/test_host_data.py checks every pair of lengths in 1..160 against scipy)
 // order 0: nearest (floor(x + 0.5)); order 1: trilinear; [clip_lo, clip_hi]: skimage's clip=True (to the input's range), skipped when lo > hi
+__device__ __forceinline__ double dp_zoom_coord(int o, double zoom) {
+#pragma clang fp contract(off)                          // product and difference each rounded, as in scipy's C: a fused multiply-add rounds once
+    const double p = ((double)o + 0.5) * zoom;
+    return p - 0.5;
+}
 __global__ __launch_bounds__(256) void dp_zoom_kernel(const float* __restrict__ src, float* __restrict__ dst, int sd, int sh, int sw, int dd, int dh,
                                                      int dw, int order, float clip_lo, float clip_hi) {
     const long long total = (long long)dd * dh * dw;
+    const double zoom_z = (double)sd / (double)dd, zoom_y = (double)sh / (double)dh, zoom_x = (double)sw / (double)dw;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int ox = (int)(i % dw), oy = (int)((i / dw) % dh), oz = (int)(i / ((long long)dw * dh));
-        const double cz = ((double)oz + 0.5) * sd / dd - 0.5, cy = ((double)oy + 0.5) * sh / dh - 0.5, cx = ((double)ox + 0.5) * sw / dw - 0.5;
+        const double cz = dp_zoom_coord(oz, zoom_z), cy = dp_zoom_coord(oy, zoom_y), cx = dp_zoom_coord(ox, zoom_x);
         float v;
         if (order == 0) {
             const int z = dp_mirror((int)floor(cz + 0.5), sd), y = dp_mirror((int)floor(cy + 0.5), sh), x = dp_mirror((int)floor(cx + 0.5), sw);
