@@ -948,6 +948,34 @@ int vs_seg_loss_fwd(const float* p, const float* label, const float* class_w, do
                     long long voxels, int bot, int top, float eps, float dice_w, float ce_w, int batch_dice, float gamma, void* stream);
 int vs_seg_loss_bwd(const float* p, const float* label, const float* class_w, const double* scratch, const float* gout, float* gp, int batch, int channels,
                     long long voxels, int bot, int top, float eps, float dice_w, float ce_w, int batch_dice, float gamma, void* stream);
+/* The same loss with a TOP-K cross-entropy, K found on the device (csrc/topk.hip).  Validity, f_v, S / I / T and dice_term are those of
+ * vs_seg_loss_fwd; the cross-entropy term is the mean of the K largest voxel losses of the POOL, the N valid voxels of the whole batch:
+ *   key    g_v = (float)(w[l_v] f_v), the fp64 product rounded once; keys are ordered as real numbers (-0.0 equals 0.0)
+ *   rank   K = max(1, floor(r * (double)N)), r a host double in (0, 1];  N == 0: ce_term = 0 and every gradient is 0
+ *   tau    the K-th largest key;  n_gt = #{g > tau}, n_eq = #{g = tau}  (n_gt < K <= n_gt + n_eq)
+ *   term   ce_term = (A + (K - n_gt) * (E / n_eq)) / K,  A = sum_{g > tau} w f,  E = sum_{g = tau} w f  in fp64: the K - n_gt places left at the
+ *          threshold are shared equally by all voxels tied there — no tie-break by position.  NOT divided by sum w, unlike vs_seg_loss_fwd's term.
+ *   final = (dice_w * dice_term) + ce_w * ce_term in fp32.
+ * The backward is the exact derivative with tau, K and the membership held fixed: the cross-entropy part of gp[b][l_v][v] is
+ * gout[0] * ce_w * (c_v / K) * w[l_v] * df/dp_l, c_v = 1 above tau, (K - n_gt) / n_eq at tau, 0 below; added to the Dice part in fp64, rounded once;
+ * an ignored voxel gets exactly 0 in every channel.
+ * A NaN key (a NaN probability with gamma > 0; with gamma == 0 fmax gives the clamp's 100) is ordered above +inf: the voxel counts among the hardest and
+ * the term it enters is NaN.
+ * workspace: vs_seg_topk_workspace_bytes() bytes, 16-byte aligned, contents undefined on entry (the first launch writes its initial state); the forward
+ * leaves the keys, the totals and the selection there for the backward, which reads nothing else of the forward's.  record: NULL, or 4 doubles in
+ * DEVICE memory the forward fills for the caller (it may be reused at once: the backward reads the workspace's own copy) —
+ *   record[0] = N,  record[1] = K,  record[2] = tau (0 when N == 0),  record[3] = n_gt * 2^26 + n_eq   (n_gt = floor(record[3] / 2^26)).
+ * Forward: seven launches whatever the data; backward: one.  No memset, nothing allocated, synchronised or read back; counts are integer atomics, no
+ * floating-point sum uses one: the same bits eagerly, under graph replay and in both builds.  Errors are vs_seg_loss_fwd's, answered on the host before
+ * any launch; in addition r NaN or outside (0, 1] or an infinite class weight: VS_EINVAL; batch * voxels >= 2^26: VS_ESHAPE (vs_seg_topk_workspace_bytes: 0);
+ * workspace not 16-byte or record not 8-byte aligned: VS_EALIGN. */
+size_t vs_seg_topk_workspace_bytes(int batch, long long voxels);
+int vs_seg_loss_topk_fwd(const float* p, const float* label, const float* class_w, void* workspace, double* record, float* terms, float* final_out,
+                         int batch, int channels, long long voxels, int bot, int top, float eps, float dice_w, float ce_w, int batch_dice, float gamma,
+                         double r, void* stream);
+int vs_seg_loss_topk_bwd(const float* p, const float* label, const float* class_w, const void* workspace, const float* gout, float* gp,
+                         int batch, int channels, long long voxels, int bot, int top, float eps, float dice_w, float ce_w, int batch_dice,
+                         float gamma, double r, void* stream);
 /* Deep-supervision head (csrc/dshead.hip): the 1x1x1 convolution of a coarse channels-last feature map, the softmax of its logits and the
  * loss of vs_seg_loss_* against the FULL-resolution label picked at stride s, fused: no logit or probability is stored.
  *   feat   [batch][d][h][w][channels], dtype VS_F32 / VS_BF16 / VS_F16, channels 8 / 16 / 32 / 64;   weight fp32 [classes][channels], bias fp32 [classes],

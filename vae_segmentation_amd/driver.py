@@ -969,7 +969,10 @@ def train_epoch(st, loader, epoch):
             aux = dict(aux, **_pseudo_batch_losses(st))
         seen += a.batch_size
         if st.rank == 0 and idx % a.display_freq == 0:              # logging syncs the host every display_freq steps only
-            parts = ", ".join("%s %.4f" % (k, v.item()) for k, v in aux.items() if k not in ("batch", "ds_losses"))
+            parts = ", ".join("%s %.4f" % (k, v.item()) for k, v in aux.items() if k not in ("batch", "ds_losses", "topk_record"))
+            if "topk_record" in aux:                                  # --ce_topk: the selection of the last step
+                rec = ops.topk_record(aux["topk_record"])
+                parts += ", topk %d/%d, tau %.4g" % (rec["K"], rec["N"], rec["tau"])
             for lvl, (d_i, ce_i) in enumerate(aux.get("ds_losses", ()), 1):      # --deep_supervision: the coarse levels' terms
                 parts += ", ds%d_dice_loss %.4f, ds%d_ce_loss %.4f" % (lvl, d_i.item(), lvl, ce_i.item())
             if optimizer.max_norm is not None and optimizer.grad_norm is not None:
@@ -1112,6 +1115,10 @@ def _percentile_pair(text):
                   "two ascending percentiles P_LO,P_HI in [0, 100]")
 
 
+def _percent(text):
+    return _typed(text, float, lambda v: 0.0 < v <= 100.0, "a percentage in (0, 100]")
+
+
 def _nonnegative(text):
     return _typed(text, float, lambda v: 0.0 <= v < float("inf"), "a finite number >= 0")
 
@@ -1131,7 +1138,7 @@ def check_seg_loss_flags(parser, a, methods=SEG_LOSS_METHODS):
     """--seg_loss and the flags that shape the compound loss belong to the methods whose loss is a Dice against the label: seg_train and joint_train
     of main_source.py (main_target.py passes methods=())"""
     given = [n for n, default in (("seg_loss", "dice"), ("ce_weight", 1.0), ("batch_dice", False), ("focal_gamma", 0.0), ("class_weights", None),
-                                  ("deep_supervision", 0))
+                                  ("deep_supervision", 0), ("ce_topk", None))
              if getattr(a, n) != default]
     if not given:
         return a
@@ -1145,6 +1152,8 @@ def check_seg_loss_flags(parser, a, methods=SEG_LOSS_METHODS):
         parser.error("--seg_loss dice_ce handles at most 8 classes, the background included")
     if a.class_weights is not None and len(a.class_weights) != nc:
         parser.error("--class_weights takes exactly %d numbers (one per class, the background included), got %d" % (nc, len(a.class_weights)))
+    if a.ce_topk is not None and a.deep_supervision:
+        parser.error("--ce_topk selects among stored probabilities, and the heads of --deep_supervision store none: the two cannot be combined")
     return a
 
 
@@ -1176,8 +1185,11 @@ def seg_loss_of(args):
     """the `loss` argument of train.seg_train_losses / joint_train_losses from the flags; None for --seg_loss dice (the default): the reference's Dice"""
     if args.seg_loss != "dice_ce":
         return None
-    return {"dice_weight": 1.0, "ce_weight": args.ce_weight, "batch_dice": bool(args.batch_dice), "class_weights": args.class_weights,
-            "gamma": args.focal_gamma}
+    kw = {"dice_weight": 1.0, "ce_weight": args.ce_weight, "batch_dice": bool(args.batch_dice), "class_weights": args.class_weights,
+          "gamma": args.focal_gamma}
+    if args.ce_topk is not None:                                            # off: the dict is what it was, and so is every launch
+        kw["topk"] = args.ce_topk / 100.0
+    return kw
 
 
 # the flags main_target.py declares and main_source.py lacks, with main_target.py's defaults (tests/test_host_driver.py holds the two against each other):
@@ -1255,6 +1267,9 @@ def add_native_flags(parser):
                    "-(1 - p)^G ln p; 0 = plain cross-entropy")
     g.add_argument("--class_weights", type=_class_weights, default=None, metavar="W0,W1,...", help="with --seg_loss dice_ce: one cross-entropy weight "
                    ">= 0 per class, the background first — exactly n_class numbers (torch's weighted mean); default all 1")
+    g.add_argument("--ce_topk", type=_percent, default=None, metavar="PCT", help="with --seg_loss dice_ce: the cross-entropy term is the mean over the "
+                   "hardest PCT percent of the rank's valid voxels only (nnU-Net's DC_and_topk_loss: 10), selected on the device inside the captured step "
+                   "(ops.seg_loss(topk=), DESIGN 3.23); the loss line then also prints K/N and the threshold.  Not with --deep_supervision.  Default: off")
     g.add_argument("--deep_supervision", type=int, default=0, choices=[0, 1, 2], metavar="L", help="with --seg_loss dice_ce: the same loss on L coarser "
                    "levels of the decoder — 1: the half-resolution skip sum, 2: the quarter-resolution one as well — through 1x1x1 heads fused with their "
                    "loss (ops.ds_head, DESIGN 3.21), against the label picked at stride 2 / 4, the levels weighted 2^-i and normalised (L = 2: 4/7, "

@@ -2419,10 +2419,78 @@ class SegLoss(torch.autograd.Function):
         return (_unpad_quads(gp, ctx.shape),) + (None,) * 9
 
 
-def seg_loss(p, target, dice_weight=1.0, ce_weight=1.0, batch_dice=False, class_weights=None, gamma=0.0, botindex=0, topindex=2, eps=1e-6):
+class SegLossTopK(torch.autograd.Function):
+    """SegLoss with a TOP-K cross-entropy (csrc/topk.hip): ce_term is the mean of the K = max(1, floor(r N)) largest voxel losses
+    w[l] f of the N valid voxels of the whole batch, the places left at the threshold tau shared equally by the voxels tied there; K is found on the
+    device, so the step stays one replayed graph — SEVEN forward launches and ONE backward launch whatever the data.  `record`: None, or an fp64 (4,)
+    device tensor the forward fills with (N, K, tau, n_gt * 2^26 + n_eq) (topk_record() takes it apart); the backward reads the workspace's own copy, so one
+    record tensor may serve several calls.
+    -> (final, terms[2] = (dice_term, ce_term)); the only gradient is p's."""
+
+    @staticmethod
+    def forward(ctx, p, label, bot, top, eps, dice_weight, ce_weight, batch_dice, class_weights, gamma, r, record):
+        _require_cuda(p, label)
+        p, label = _contig(p.float()), _contig(label.float())
+        b, c = p.shape[0], p.shape[1]
+        voxels = p.numel() // (b * c)
+        if label.numel() != b * voxels:
+            raise ValueError("label target: expected %d x %d labels, got %s" % (b, voxels, tuple(label.shape)))
+        if record is not None and (record.dtype != torch.float64 or record.numel() != 4 or not record.is_cuda or not record.is_contiguous()):
+            raise ValueError("record: a contiguous fp64 (4,) device tensor")
+        ctx.shape = tuple(p.shape)
+        p, label = _pad_quads(p, b, c, 0.0), _pad_quads(label, b, 1, -1.0)
+        voxels = p.numel() // (b * c)
+        nbytes = lib.vs_seg_topk_workspace_bytes(b, voxels)
+        if nbytes == 0:
+            raise ValueError("seg_loss(topk=): batch %d x %d voxels is outside what the top-k selection handles (batch <= 64, batch * voxels < 2^26)"
+                             % (b, voxels))
+        ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=p.device)
+        terms = torch.empty(2, dtype=torch.float32, device=p.device)
+        final = torch.empty((), dtype=torch.float32, device=p.device)
+        cfg = (b, c, voxels, int(bot), int(top), float(eps), float(dice_weight), float(ce_weight), 1 if batch_dice else 0, float(gamma), float(r))
+        wp = (_ctypes.c_float * 8)(*([float(w) for w in class_weights] + [0.0] * 8)[:8])
+        check(lib.vs_seg_loss_topk_fwd(p.data_ptr(), label.data_ptr(), _ctypes.addressof(wp), ws.data_ptr(), None if record is None else record.data_ptr(),
+                                       terms.data_ptr(), final.data_ptr(), *cfg, _stream()), "seg_loss_topk_fwd")
+        ctx.save_for_backward(p, label, ws)
+        ctx.cfg, ctx.class_weights = cfg, [float(w) for w in class_weights]
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)      # no zero-fill launch for the terms' gradient
+        return final, terms
+
+    @staticmethod
+    def backward(ctx, g, _gterms):
+        p, label, ws = ctx.saved_tensors
+        gp = None
+        if g is not None and ctx.needs_input_grad[0]:
+            g = _contig(g.float())
+            gp = torch.empty_like(p)
+            wp = (_ctypes.c_float * 8)(*(ctx.class_weights + [0.0] * 8)[:8])
+            check(lib.vs_seg_loss_topk_bwd(p.data_ptr(), label.data_ptr(), _ctypes.addressof(wp), ws.data_ptr(), g.data_ptr(),
+                                           gp.data_ptr(), *ctx.cfg, _stream()), "seg_loss_topk_bwd")
+        return (_unpad_quads(gp, ctx.shape),) + (None,) * 11
+
+
+TOPK_PACK = float(1 << 26)
+
+
+def topk_record(record):
+    """SegLossTopK's record (a host copy or a device tensor: this reads it back) -> {"N", "K", "tau", "n_gt", "n_eq"}"""
+    n, k, tau, packed = (float(v) for v in record.tolist())
+    n_gt = int(packed // TOPK_PACK)
+    return {"N": int(n), "K": int(k), "tau": tau, "n_gt": n_gt, "n_eq": int(packed - n_gt * TOPK_PACK)}
+
+
+def seg_loss(p, target, dice_weight=1.0, ce_weight=1.0, batch_dice=False, class_weights=None, gamma=0.0, botindex=0, topindex=2, eps=1e-6, topk=None,
+             record=None):
     """dice_weight * (1 - Dice(p, target)) + ce_weight * CE(p, target) -> (final, (dice_term, ce_term)) for the softmax output p (B, C, ...), 1 <= C <= 8,
     and an ops.LabelTarget; the rule is SegLoss's (DESIGN 3.20).  Channel selection as dice_loss_sum; batch_dice pools the Dice sums over the batch;
-    class_weights: C numbers >= 0 (default all 1) weighting the cross-entropy as torch's weighted mean does; gamma >= 0: the focal exponent."""
+    class_weights: C numbers >= 0 (default all 1) weighting the cross-entropy as torch's weighted mean does; gamma >= 0: the focal exponent.
+    topk=r, 0 < r <= 1: the cross-entropy term becomes the mean of the hardest floor(r N) of the batch's N valid voxels, NOT divided by the sum of the
+    weights (SegLossTopK); record: an fp64 (4,) device tensor it fills (topk_record)."""
+    if topk is None and record is not None:
+        raise TypeError("seg_loss: record= is what topk= fills")
+    if topk is not None and not 0.0 < float(topk) <= 1.0:         # NaN fails both
+        raise ValueError("seg_loss: topk is the kept fraction, 0 < topk <= 1, got %r" % (topk,))
     if not isinstance(target, LabelTarget):
         raise TypeError("seg_loss takes its target as an ops.LabelTarget (a label volume); for a tensor target use dice_loss_sum")
     channels = p.shape[1]
@@ -2432,6 +2500,9 @@ def seg_loss(p, target, dice_weight=1.0, ce_weight=1.0, batch_dice=False, class_
     class_weights = [float(w) for w in class_weights]
     if len(class_weights) != channels:
         raise ValueError("seg_loss: %d class weights for %d channels" % (len(class_weights), channels))
+    if topk is not None:
+        final, terms = SegLossTopK.apply(p, target.label, bot, top, eps, dice_weight, ce_weight, bool(batch_dice), class_weights, gamma, float(topk), record)
+        return final, tuple(terms.unbind(0))
     final, terms = SegLoss.apply(p, target.label, bot, top, eps, dice_weight, ce_weight, bool(batch_dice), class_weights, gamma)
     return final, tuple(terms.unbind(0))
 

@@ -33,12 +33,25 @@ def _gt(batch, label, n_class):
 
 def _seg_loss_args(loss):
     """`loss` of seg_train_losses / joint_train_losses: a dict or namedtuple of ops.seg_loss's keyword arguments (dice_weight, ce_weight, batch_dice,
-    class_weights, gamma) -> the dict"""
+    class_weights, gamma, topk) -> the dict; "topk": None is the same as leaving it out"""
     kw = dict(loss._asdict() if hasattr(loss, "_asdict") else loss)
-    unknown = set(kw) - {"dice_weight", "ce_weight", "batch_dice", "class_weights", "gamma"}
+    unknown = set(kw) - {"dice_weight", "ce_weight", "batch_dice", "class_weights", "gamma", "topk"}
     if unknown:
         raise TypeError("loss: unknown argument(s) %s" % ", ".join(sorted(unknown)))
+    if kw.get("topk", 0) is None:
+        del kw["topk"]
     return kw
+
+
+def _seg_loss(pred, label, kw, n_class, eps):
+    """the compound loss of the full-resolution prediction -> (final, (dice_term, ce_term), what it adds to aux): with "topk" the record of the
+    selection (ops.topk_record), filled on the device"""
+    extra = {}
+    if "topk" in kw:
+        extra["topk_record"] = torch.empty(4, dtype=torch.float64, device=pred.device)
+        kw = dict(kw, record=extra["topk_record"])
+    final, terms = ops.seg_loss(pred, ops.LabelTarget(label), botindex=1, topindex=n_class, eps=eps, **kw)
+    return final, terms, extra
 
 
 def ds_weights(levels):
@@ -52,6 +65,8 @@ def ds_weights(levels):
 def _deep_seg_loss(pred, batch, label, deep, kw, n_class, eps):
     """the compound loss with deep supervision: w0 * seg_loss(pred) + sum_i ds_head_i(scale = w_i), added in that order
     -> (final, (dice_term, ce_term) of the full resolution, [(dice_term_i, ce_term_i) per level])"""
+    if "topk" in kw:
+        raise TypeError("top-k cross-entropy is not defined on the deep-supervision levels (their heads store no probability): drop topk or deep")
     w = ds_weights(len(deep.heads))
     target = ops.LabelTarget(label)
     kw0 = dict(kw, dice_weight=kw.get("dice_weight", 1.0) * w[0], ce_weight=kw.get("ce_weight", 1.0) * w[0])
@@ -111,8 +126,8 @@ def joint_train_losses(joint, img, label, lambda_vae=0.1, eps=EPS_MAIN_SOURCE, n
         batch["label"] = label
         batch = joint(batch, "img", "pred", "recon")
         vae_part, (recon_loss,) = ops.dice_loss_sum(batch["pred"], [(batch["recon"], lambda_vae)], botindex=1, topindex=n_class, eps=eps)
-        seg_part, (dsc_loss, ce_loss) = ops.seg_loss(batch["pred"], ops.LabelTarget(label), botindex=1, topindex=n_class, eps=eps, **_seg_loss_args(loss))
-        return vae_part + seg_part, {"recon_loss": recon_loss, "dice_loss": dsc_loss, "ce_loss": ce_loss, "batch": batch}
+        seg_part, (dsc_loss, ce_loss), extra = _seg_loss(batch["pred"], label, _seg_loss_args(loss), n_class, eps)
+        return vae_part + seg_part, {"recon_loss": recon_loss, "dice_loss": dsc_loss, "ce_loss": ce_loss, "batch": batch, **extra}
     gt = _gt(batch, label, n_class)
     batch = joint(batch, "img", "pred", "recon")
     # final = lambda_vae * (1 - avg_dsc(pred, recon)) + (1 - avg_dsc(pred, gt))        (main_source.py:469-471), one launch each way
@@ -141,8 +156,8 @@ def seg_train_losses(seg, img, label, eps=EPS_MAIN_SOURCE, n_class=2, loss=None,
     if loss is not None:
         batch["label"] = label
         batch = seg(batch, "img", "pred")
-        final, (dsc_loss, ce_loss) = ops.seg_loss(batch["pred"], ops.LabelTarget(label), botindex=1, topindex=n_class, eps=eps, **_seg_loss_args(loss))
-        return final, {"dice_loss": dsc_loss, "ce_loss": ce_loss, "batch": batch}
+        final, (dsc_loss, ce_loss), extra = _seg_loss(batch["pred"], label, _seg_loss_args(loss), n_class, eps)
+        return final, {"dice_loss": dsc_loss, "ce_loss": ce_loss, "batch": batch, **extra}
     gt = _gt(batch, label, n_class)
     batch = seg(batch, "img", "pred")
     final, (dsc_loss,) = ops.dice_loss_sum(batch["pred"], [(gt, 1.0)], botindex=1, topindex=n_class, eps=eps)
